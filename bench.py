@@ -6,18 +6,25 @@ particles (8 per cell) in a 128^3-cell domain, floor cuboid, fp32, synthetic lat
 substep of MpmPipeline::queue_step (sort -> P2G -> grid update -> fused G2P + particle update; three launches on a single
 domain: the grid update rides in the P2G launch and the fused G2P bins its output for the next sort), inputs resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
+A plain run does only what the headline figure needs: it builds the workload, pre-warms the clocks, steps W warm-up
+substeps, times exactly K substeps and prints one JSON line (`value` in particle-steps/s, `ms_per_step`).
+--dump-outputs DIR: after the timed substeps, the particle state they left (what a caller reads back) as DIR/<name>.npy
+in float32 (see dump_outputs). The inputs are seeded: the same arguments give the same inputs in every run.
 --config: c2 (default, the headline), c3 = Drucker-Prager sand column, 4M, standing between the floor and four walls,
 c4 = corotated cube on the floor hit by a kinematic rotating cuboid, 8M, c5 = pressure-only neo-Hookean fluid block, 16M
 (BASELINE.json configs[2], configs[3], configs[4]).
 N > 1: one process per GPU, x-slab domain decomposition; per substep each rank swaps ONE message with each of its two
 neighbours — the partial node sums of the interface layers and the particles changing owner — over RCCL point-to-point
-issued from inside the library (wgs_sharded_step, include/wgsparkl_hip.h), no collective on the data path. Before
-anything is timed the decomposition validates itself against a single-domain run (validation_sharded; exit 3 on a
-mismatch). --scaling weak (default): N
-copies of the config side by side along x (fixed work per GPU); strong: the named size cut into N slabs (north_star's
-16M target: --config c5 --scaling strong). Without flags, the line also carries `extra` legs: the same cube after it
+issued from inside the library (wgs_sharded_step, include/wgsparkl_hip.h), no collective on the data path. --scaling weak
+(default): N copies of the config side by side along x (fixed work per GPU); strong: the named size cut into N slabs
+(north_star's 16M target: --config c5 --scaling strong).
+--full adds everything else the benchmark measures and checks, after the timed substeps: per-pass device times and the
+G2P roofline figure of the headline (64 more event-timed substeps), for N > 1 the validation of the decomposition against
+a single-domain run before anything is timed (validation_sharded; exit 3 on a mismatch), the CPU baseline and the check
+of the HIP path against the oracle on the bench data (exit 3 on a mismatch; --no-cpu-baseline skips both), the live PMC
+traffic of the fused G2P (--no-live-pmc skips it) and `extra` legs (--no-extra skips them): the same cube after it
 landed on the floor, c3, c4 on one GPU, the reference's own sand3 (202 k particles) and sand2 (490 k, 2D) scenes, c2_stirred (the cube
 crossing the grid and spinning: > 10 % of its particles change cell per substep), c2_frames (20 substeps per wgs_step call
 with the pose read-back between calls) and c5 (strong over the N GPUs), each with its pass times, its own G2P roofline figure
@@ -48,10 +55,15 @@ def parse_args():
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5"), default="c2")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--n-side", type=int, default=None, help="particles per cube edge (c2: 100 -> 1M, the named config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (landed cube, c3, sand3, sand2, stirred, frames, c5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the particle state the timed substeps left as DIR/<name>.npy (float32; a seeded sample of the particles above 56 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: pass times and roofline, CPU baseline and oracle check, "
+                         "sharded validation, live PMC traffic, extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle check")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs (landed cube, c3, sand3, sand2, stirred, frames, c5)")
     ap.add_argument("--no-floor", action="store_true", help="c2 without the floor cuboid of SURVEY 8d (no CPIC passes)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed rocprofv3 passes instead of two child runs under rocprofv3 --pmc")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: roofline.traffic from the committed rocprofv3 passes instead of two child runs under rocprofv3 --pmc")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the ~0.1 s of throwaway substeps that bring the GPU clocks up before the measured leg")
     ap.add_argument("--allow-debug-switches", action="store_true", help="run although WGS_DEBUG is set (A/B of launch shapes)")
     return ap.parse_args()
@@ -148,6 +160,40 @@ def g2p_roofline(timings, k_ts, mark_ms, n, n_nodes, bytes_per_particle, kernel)
             "event_interval_ms": interval, "event_mark_ms": mark_ms}
 
 
+DUMP_BUDGET_BYTES = 56_000_000   # --dump-outputs writes at most this much (all ranks together)
+
+
+def dump_outputs(leg, out_dir, rank, world):
+    """--dump-outputs: the particle state the timed substeps left, as a caller reads it back (wgs_read_particles; a slab of
+    a decomposition: wgs_shard_export, rows ordered by global id), one DIR/<name>.npy per field in float32: pos, vel,
+    def_grad, affine, plastic_state (Drucker-Prager scenes) and bodies (rotation, translation, linvel, angvel per collider).
+    Above DUMP_BUDGET_BYTES the particle fields hold a fixed sample of the rows (seed 0, ascending row order), the same
+    for the same arguments. N > 1: every rank writes its own slab as rank<r>_<name>.npy."""
+    import numpy as np
+    if leg.sharded:
+        rec = leg.data.export()
+        order = np.argsort(rec["ids"], kind="stable")
+        fields = {k: rec[k][order] for k in ("pos", "vel", "def_grad", "affine")}
+    else:
+        ps = leg.data.read_particles()
+        fields = dict(pos=ps.pos, vel=ps.vel, def_grad=ps.def_grad, affine=ps.affine)
+        if ps.has_plasticity.any():
+            fields["plastic_state"] = ps.dp_state
+    n = len(fields["pos"])
+    row_bytes = sum(a.reshape(n, -1).shape[1] * 4 for a in fields.values()) if n else 1
+    keep = DUMP_BUDGET_BYTES // world // row_bytes
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        fields = {k: a[rows] for k, a in fields.items()}
+    if leg.scene["colliders"]:
+        fields["bodies"] = np.array([np.concatenate([b[k] for k in ("rotation", "translation", "linvel", "angvel")])
+                                     for b in leg.data.read_body_poses()])
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for k, a in fields.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 class Leg:
     """One timed workload on this rank: single-domain data (world == 1) or one slab of the decomposition."""
 
@@ -228,38 +274,45 @@ class Leg:
             assert int(cnt.item()) == self.n_total, f"particles lost in the exchange: {int(cnt.item())} != {self.n_total}"
         return elapsed
 
-    def result(self, steps, elapsed, kernel_name):
-        """Throughput + per-pass device times (HIP events on the data's own stream) of up to 64 more substeps of the local
-        data (a slab steps without its neighbours here: kernel timing only, after the timed region)."""
+    def result(self, steps, elapsed, kernel_name, pass_timings=True):
+        """Throughput of the timed region; with `pass_timings` (--full) also the per-pass device times (HIP events on the data's
+        own stream) of up to 64 more substeps of the local data (a slab steps without its neighbours here: kernel timing only,
+        after the timed region) and the G2P roofline figure made from them."""
         from wgsparkl_amd import _ffi
         pipe = self.pipe
-        k_ts = min(steps, 64)
-        _ffi.check(pipe.lib, pipe.lib.wgs_step(pipe._h, self.handle, k_ts, 1))
-        self.data.sync()
-        ms = (C.c_float * _ffi.WGS_NUM_PASSES)()
-        _ffi.check(pipe.lib, pipe.lib.wgs_read_timings(self.handle, ms))
-        timings = dict(zip(_ffi.PASS_NAMES, [float(x) for x in ms]))
+        if pass_timings:
+            k_ts = min(steps, 64)
+            _ffi.check(pipe.lib, pipe.lib.wgs_step(pipe._h, self.handle, k_ts, 1))
+            self.data.sync()
+            ms = (C.c_float * _ffi.WGS_NUM_PASSES)()
+            _ffi.check(pipe.lib, pipe.lib.wgs_read_timings(self.handle, ms))
+            timings = dict(zip(_ffi.PASS_NAMES, [float(x) for x in ms]))
+            ovh = C.c_float(0.0)
+            pipe.lib.wgs_read_timing_overhead(self.handle, C.byref(ovh))   # cost of one timing mark, measured in the same substeps
         st = pipe.T.Stats()
         _ffi.check(pipe.lib, pipe.lib.wgs_get_stats(self.handle, C.byref(st)))
-        ovh = C.c_float(0.0)
-        pipe.lib.wgs_read_timing_overhead(self.handle, C.byref(ovh))   # cost of one timing mark, measured in the same substeps
         nblocks = int(st.num_active_blocks)
-        return {"value": self.n_total * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps,
-                "global_particles": self.n_total, "active_blocks_rank0": nblocks, "near_collider_blocks_rank0": int(st.num_near_collider_blocks),
-                "mover_fraction": self.mover_fraction, "events_in_timed_region": getattr(self, "events", None),
-                "parallelism": self.parallelism,
-                "roofline": g2p_roofline(timings, k_ts, float(ovh.value), self.n, nblocks * 64, self.bytes_per_particle, kernel_name),
-                "pass_ms_per_step": {k: v / k_ts for k, v in timings.items()}}
+        res = {"value": self.n_total * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps,
+               "global_particles": self.n_total, "active_blocks_rank0": nblocks, "near_collider_blocks_rank0": int(st.num_near_collider_blocks),
+               "mover_fraction": self.mover_fraction, "events_in_timed_region": getattr(self, "events", None),
+               "parallelism": self.parallelism}
+        if pass_timings:
+            res["roofline"] = g2p_roofline(timings, k_ts, float(ovh.value), self.n, nblocks * 64, self.bytes_per_particle, kernel_name)
+            res["pass_ms_per_step"] = {k: v / k_ts for k, v in timings.items()}
+        return res
 
     def close(self):
         self.data.close()
 
 
-def measure(env, scene, world, rank, steps, warmup, kernel_name, settle=0, frame=0):
+def measure(env, scene, world, rank, steps, warmup, kernel_name, settle=0, frame=0, pass_timings=True, dump_dir=None):
     leg = Leg(env, scene, world, rank, frame=frame)
     if settle:
         leg.run(settle)
-    res = leg.result(steps, leg.timed(steps, warmup), kernel_name)
+    elapsed = leg.timed(steps, warmup)
+    if dump_dir is not None:
+        dump_outputs(leg, dump_dir, rank, world)     # before anything else steps the data
+    res = leg.result(steps, elapsed, kernel_name, pass_timings)
     leg.close()
     return res
 
@@ -342,10 +395,10 @@ def main():
             sys.exit(4)
         env["comm"] = comm
 
-    # ---- N > 1: the decomposition validates itself before anything is timed (a small bar on all ranks through
+    # ---- N > 1, --full: the decomposition validates itself before anything is timed (a small bar on all ranks through
     # wgs_sharded_step against the single-domain run of the same bar on rank 0: ids exact, pos / vel rel RMS < 1e-5)
     validation_sharded = None
-    if sharded_path and world > 1:
+    if args.full and sharded_path and world > 1:
         from wgsparkl_amd.selfcheck import bar_check
         validation_sharded = bar_check(pipe, dist, env["comm"], world, rank)
         if not validation_sharded["ok"]:
@@ -411,10 +464,28 @@ def main():
         pw.close()
         del pw
     main_res = measure(env, scene, world, rank, args.steps, args.warmup,
-                       ("k_g2p_pair<plastic>" if args.config == "c3" else KERNEL_ELASTIC) if scene["colliders"] else "k_g2p_update (fused G2P + particle update)")
+                       ("k_g2p_pair<plastic>" if args.config == "c3" else KERNEL_ELASTIC) if scene["colliders"] else "k_g2p_update (fused G2P + particle update)",
+                       pass_timings=args.full, dump_dir=args.dump_outputs)
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "particle-steps/sec", "value": main_res["value"], "unit": "particle-steps/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic", "full": args.full,
+            "config": {"workload": scene["name"], "config": args.config, "particles_per_gpu": main_res["global_particles"] // world,
+                       "global_particles": main_res["global_particles"], "active_blocks_rank0": main_res["active_blocks_rank0"],
+                       "parallelism": main_res["parallelism"]},
+            "events_in_timed_region": main_res["events_in_timed_region"], "mover_fraction": main_res["mover_fraction"],
+            "prewarm_substeps": prewarm_substeps,
+            "build": {"info": build_info, "WGS_DEBUG": dbg_env, "transport_note": transport_note},
+            "validation_sharded": validation_sharded,
+            "notes": "the table of block ids is built by the first substep (a k_bin launch in front of the sort, ~+0.25 ms once at this size); blocks "
+                     "nobody activated for 8 substeps are evicted from it and their ids reused, so it is rebuilt again only when the grid grows "
+                     "(events_in_timed_region counts such substeps per leg).",
+        }
+    if rank == 0 and args.full:
         rl = main_res["roofline"]
         prof = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_pmc_g2p.json")))[-1:]
         # (the live measurement — two child runs under rocprofv3 — comes after every timed leg, below: the children use this GPU;
@@ -425,29 +496,14 @@ def main():
                 rl["traffic_source"] = os.path.relpath(prof[0], ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed; not measured in this run)"
             except Exception:
                 pass
-        out = {
-            "metric": "particle-steps/sec", "value": main_res["value"], "unit": "particle-steps/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": scene["name"], "config": args.config, "particles_per_gpu": main_res["global_particles"] // world,
-                       "global_particles": main_res["global_particles"], "active_blocks_rank0": main_res["active_blocks_rank0"],
-                       "parallelism": main_res["parallelism"]},
-            "roofline": rl,
-            "pass_ms_per_step": main_res["pass_ms_per_step"],
-            "events_in_timed_region": main_res["events_in_timed_region"], "mover_fraction": main_res["mover_fraction"],
-            "prewarm_substeps": prewarm_substeps,
-            "build": {"info": build_info, "WGS_DEBUG": dbg_env, "transport_note": transport_note},
-            "validation_sharded": validation_sharded,
-            "notes": "the table of block ids is built by the first substep (a k_bin launch in front of the sort, ~+0.25 ms once at this size); blocks "
-                     "nobody activated for 8 substeps are evicted from it and their ids reused, so it is rebuilt again only when the grid grows "
-                     "(events_in_timed_region counts such substeps per leg). "
-                     "pass_ms_per_step: on single-domain data the grid update runs as workgroups of the P2G launch and the fused G2P bins its output for the "
-                     "next substep's sort (DESIGN.md 4): 'p2g' holds P2G + grid update, 'g2p' holds the binning, 'grid sort' is the one regroup launch, "
-                     "'grid_update' is then an empty interval between two event marks (~0.004 ms, like every pass without a launch)",        }
+        out["roofline"] = rl
+        out["pass_ms_per_step"] = main_res["pass_ms_per_step"]
+        out["notes"] += (" pass_ms_per_step: on single-domain data the grid update runs as workgroups of the P2G launch and the fused G2P bins its output for the "
+                         "next substep's sort (DESIGN.md 4): 'p2g' holds P2G + grid update, 'g2p' holds the binning, 'grid sort' is the one regroup launch, "
+                         "'grid_update' is then an empty interval between two event marks (~0.004 ms, like every pass without a launch)")
 
-    # ---- CPU baseline + validation of the HIP path on the bench data itself (rank 0, N = 1)
-    if rank == 0 and not args.no_cpu_baseline and not sharded_path:
+    # ---- --full: CPU baseline + validation of the HIP path on the bench data itself (rank 0, N = 1)
+    if args.full and rank == 0 and not args.no_cpu_baseline and not sharded_path:
         from wgsparkl_amd import MpmData
         sub = 20 if scene["particles"].n <= 2_000_000 else 4
         v, secs, threads, st = cpu_baseline(scene, sub)
@@ -475,8 +531,8 @@ def main():
             print("bench.py: the HIP path disagrees with the oracle on the bench data", file=sys.stderr)
             sys.exit(3)
 
-    # ---- extra legs (default command only): other states of the solver, each with its own G2P roofline figure
-    if not args.no_extra and default_workload:
+    # ---- --full, extra legs (default workload only): other states of the solver, each with its own G2P roofline figure
+    if args.full and not args.no_extra and default_workload:
         extra = {}
         k, w = min(args.steps, 50), 5
         slim = lambda r, name: {"workload": name, "value": r["value"], "unit": "particle-steps/s", "ms_per_step": r["ms_per_step"],
@@ -555,7 +611,7 @@ def main():
         if rank == 0:
             out["extra"] = extra
 
-    if rank == 0 and default_workload and world == 1 and not sharded_path and not args.no_live_pmc and not args.no_extra:
+    if args.full and rank == 0 and default_workload and world == 1 and not sharded_path and not args.no_live_pmc and not args.no_extra:
         live = live_pmc_traffic()   # two short child runs of the headline workload under rocprofv3 --pmc (one counter each)
         if live is not None:
             out["roofline"]["traffic"] = live["bytes"]

@@ -5,7 +5,7 @@ D=gpurun_out/check; mkdir -p $D
 timeout 2400 python -X faulthandler -m pytest tests -m gpu -q -x --deselect tests/test_multi_gpu.py > $D/pytest_full.log 2>&1
 grep -n "FAILED\|Fatal\|Error\|passed\|failed\|File \"/tmp" $D/pytest_full.log | tail -20
 for sc in sand3 stirred; do SCENE=$sc bash tools/gpu_scene_kstats.sh 2>&1 | grep -v amdgpu.ids | grep "k_regroup\|k_g2p_pair\|k_p2g" | cut -c1-160 | tee -a $D/kstats.log; done
-timeout 900 python bench.py --no-cpu-baseline --no-live-pmc > $D/bench_default.json 2> $D/bench_default.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-live-pmc > $D/bench_default.json 2> $D/bench_default.err
 python - <<'PY'
 import json
 for name in ("default",):

@@ -1,9 +1,9 @@
-"""Turns gpurun_out/<round>/ (made by tools/gpu_round_profile.sh on the GPU box) into the small files
+"""Turns $RAW_DIR/<round>/ (default build/profiles/<round>/, made by tools/gpu_round_profile.sh on the GPU box) into the small files
 committed under profiles/: per-kernel rocprofv3 --stats table, PMC byte counters per launch with the
 gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md (x2 for 16-B-per-lane streams), the bench line."""
 import csv, glob, json, os, sys, collections
 R = sys.argv[1] if len(sys.argv) > 1 else "r02"
-src = f"gpurun_out/{R}"
+src = os.path.join(os.environ.get("RAW_DIR", "build/profiles"), R)
 os.makedirs("profiles", exist_ok=True)
 st = sorted(glob.glob(f"{src}/stats/**/*_kernel_stats.csv", recursive=True), key=os.path.getmtime)[-1]
 rows = list(csv.DictReader(open(st)))
