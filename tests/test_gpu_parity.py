@@ -345,7 +345,39 @@ def test_random_scenes_match_oracle(hip_libs, oracle_libs, seed, chunk):
     12 substeps, against the fp32 oracle (same arithmetic): active cells and node affinity / sign bits exact,
     bodies and particles within fp32 round-off growth. chunk = 3: the same substeps in four calls with a wgs_sync
     after each, so that the launch shapes that follow the near-collider list the host last saw are the ones compared."""
+    _fuzz_parity(_random_scene(seed), chunk)
+
+
+def _breakable_scene(seed):
+    """_random_scene(seed) (its random stream untouched) with every particle made plastic and breakable: Drucker-Prager
+    sand parameters and phase (1, max_stretch) with max_stretch inside the spread of the initial F (perturbed by 0.02),
+    so that some particles break in the first substep, some later, and most never; odd seeds give a quarter of the
+    particles another max_stretch and other Lame parameters of the projection (the per-particle plasticity layout)."""
     sc = _random_scene(seed)
+    ps = sc["particles"]
+    rng = np.random.default_rng(5000 + seed)
+    ps.dp[:] = DruckerPrager.new(1e6, 0.25).as_array()
+    ps.has_plasticity[:] = True
+    ps.phase[:] = (1.0, 1.025)
+    ps.has_phase[:] = True
+    if seed % 2:
+        q = rng.random(ps.n) < 0.25
+        ps.phase[q, 1] = np.float32(1.04)
+        ps.dp[q, 4:6] = DruckerPrager.new(3e5, 0.3).as_array()[4:6]
+    return sc
+
+
+@pytest.mark.parametrize("seed", [24, 25, 26, 27, 28, 29])
+def test_random_breakable_plastic_scenes_match_oracle(hip_libs, oracle_libs, seed):
+    """The fuzz of test_random_scenes_match_oracle over scenes whose particles break (max_stretch) and then flow
+    (Drucker-Prager): the fracture switch and the projection against the oracle over many substeps and collider contacts."""
+    sc = _breakable_scene(seed)
+    got, st64 = _fuzz_parity(sc, 0)
+    broke = (got.phase[:, 0] == 0.0).sum()
+    assert 0 < broke < got.n, "some particles must break and some must not"
+
+
+def _fuzz_parity(sc, chunk):
     dim = sc["particles"].dim
     k = 12
     if chunk:
@@ -375,6 +407,17 @@ def test_random_scenes_match_oracle(hip_libs, oracle_libs, seed, chunk):
         err32 = rel_rms(st.arr[f][same], st64.arr[f][same])
         report_margin(f"fuzz {f} rel rms vs fp64", err, tol, fp32_oracle_err=err32)
         assert err < tol, (f, err, err32)
+    # the plastic and breakable state, and what the particle update leaves in F and C': phase exactly — a particle whose
+    # fracture decision went the other way (s within round-off of max_stretch after 12 substeps of fp32 drift) is counted,
+    # bounded like the affinity mismatches and left out of the floating-point fields, which then hold to the velocity bound
+    # (F and C' are advanced from the same grid velocities)
+    pmis = got.phase[same, 0] != st64.arr["phase"][same, 0]
+    report_margin("fuzz phase mismatch fraction", float(pmis.mean()), FUZZ_PART_MISMATCH, count=int(pmis.sum()))
+    assert pmis.mean() <= FUZZ_PART_MISMATCH
+    assert np.array_equal(got.phase[:, 1], st64.arr["phase"][:, 1].astype(np.float32))
+    keep = np.nonzero(same)[0][~pmis]
+    for f in ("def_grad", "affine", "dp_state"):
+        assert_close_to_truth(f"{f} (fuzz)", getattr(got, f)[keep], st.arr[f][keep], st64.arr[f][keep], FUZZ_VEL_TOL)
     if sc["colliders"]:
         st.update_world_mass_properties()
         worst = 0.0
@@ -383,6 +426,7 @@ def test_random_scenes_match_oracle(hip_libs, oracle_libs, seed, chunk):
                 worst = max(worst, float(np.abs(np.asarray(gb[key]) - np.asarray(ob[key])).max()))
         report_margin("fuzz body state abs err", worst, FUZZ_BODY_ATOL)
         assert worst <= FUZZ_BODY_ATOL
+    return got, st64
 
 
 def test_long_near_collider_list_paths_match_the_separate_launches_and_the_oracle(hip_libs, monkeypatch):
