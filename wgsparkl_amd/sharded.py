@@ -199,6 +199,8 @@ class NativeShard:
         """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now (blocking)."""
         import torch
         buf = torch.zeros(self.hdr + self.capacity * self.part_rec, dtype=torch.float32, device=torch.device("cuda", self.pipeline.device))
+        # the library writes on its own non-blocking stream: torch's fill must be done first, or it can land on the export
+        torch.cuda.current_stream(buf.device).synchronize()
         cnt = C.c_uint32(0)
         _ffi.check(self.lib, self.lib.wgs_shard_export(self._h, C.c_void_p(buf.data_ptr()), self.capacity, C.byref(cnt)))
         rec = buf[self.hdr: self.hdr + cnt.value * self.part_rec].cpu().numpy().reshape(cnt.value, self.part_rec)
