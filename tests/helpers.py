@@ -1,12 +1,26 @@
 """Shared helpers of the parity tests: run the same scene through the CPU oracle
 (fp32 restatement + fp64 "truth") and through the HIP path (C ABI), then compare
 by VIRTUAL ids (world cell coordinates), never by physical node index."""
+import os
+import re
+
 import numpy as np
 
 from oracle.orc import Oracle
 from wgsparkl_amd import MpmData, MpmPipeline
 
 _ORACLES = {}
+_LAYOUT_H = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wgsparkl_amd", "csrc", "layout.h")
+
+
+def debug_switches(*names):
+    """The WGS_DEBUG value that turns on the named developer switches: the DBG_* bits of layout.h, named without the prefix."""
+    with open(_LAYOUT_H) as f:
+        bits = {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"^\s*DBG_(\w+) = 1u << (\d+),", f.read(), re.M)}
+    value = 0
+    for name in names:
+        value |= bits[name]
+    return str(value)
 
 
 def oracle(dim, dtype):

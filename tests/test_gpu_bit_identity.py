@@ -7,7 +7,7 @@ from wgsparkl_amd import scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
+from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
 from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
                         _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
 
@@ -25,7 +25,7 @@ def test_determinism(hip_libs):
 def test_uniform_material_mode_is_bit_identical(hip_libs, monkeypatch):
     """One material for all particles: the four per-particle constants (mass, V0, lambda, mu) become kernel arguments
     and F[8] rides in their place (layout.h, Dev::uniform) — 32 bytes per particle and substep less through HBM. Same
-    arithmetic on the same values: bit-identical to the general layout (WGS_DEBUG = 65536 keeps that one), incl. the
+    arithmetic on the same values: bit-identical to the general layout (WGS_DEBUG NO_UNIFORM keeps that one), incl. the
     CPIC passes and Drucker-Prager, and the read-back shows the caller's constants."""
     for make in (lambda: scenes.neo_hookean_cube(n_side=20, with_floor=True), lambda: scenes.sand_column(nx=12, ny=20, nz=12, with_floor=True)):
         def run():
@@ -35,7 +35,7 @@ def test_uniform_material_mode_is_bit_identical(hip_libs, monkeypatch):
             data = run_gpu(sc, 30)
             return sc, data.read_particles(), data.read_grid()
         sc, a, ga = run()
-        monkeypatch.setenv("WGS_DEBUG", "65536")
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_UNIFORM"))
         _, b, gb = run()
         monkeypatch.delenv("WGS_DEBUG")
         for f in ("pos", "vel", "def_grad", "affine", "mass", "init_volume", "lambda_", "mu", "cdf_affinity", "dp_state"):
@@ -50,7 +50,7 @@ def test_uniform_plasticity_parameters_give_the_bits_of_the_general_layout(hip_l
     as kernel arguments and leaves the DP0 quad alone (mode 1); when lambda, mu of the plasticity and max_stretch are shared as well,
     the per-particle plastic state is ONE quad (mode 2). Decided at creation, bitwise. Four clouds — everything shared with a
     breakable phase (mode 2), every other particle with its own plastic lambda / mu (mode 1), with its own max_stretch (mode 1),
-    with its own h0 (general layout) — against WGS_DEBUG = 65536 (never a uniform mode): same bits, and the read-back shows the
+    with its own h0 (general layout) — against WGS_DEBUG NO_UNIFORM (never a uniform mode): same bits, and the read-back shows the
     caller's parameters."""
     def cloud(kind):
         ps = scenes.random_cloud(2500, dim=dim, seed=11 + kind, extent=9.0, young=1e6, plasticity=DruckerPrager.new(1e6, 0.25),
@@ -66,7 +66,7 @@ def test_uniform_plasticity_parameters_give_the_bits_of_the_general_layout(hip_l
             sc = dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0)[:dim], 5e-4), colliders=cols, cell_width=1.0, grid_capacity=4096, model=MODEL_COROTATED)
             return ps, run_gpu(sc, 30).read_particles()
         ps, a = run()
-        monkeypatch.setenv("WGS_DEBUG", "65536")
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_UNIFORM"))
         _, b = run()
         monkeypatch.delenv("WGS_DEBUG")
         for f in ("pos", "vel", "def_grad", "affine", "dp", "dp_state", "phase"):
@@ -78,7 +78,7 @@ def test_uniform_plasticity_parameters_give_the_bits_of_the_general_layout(hip_l
 def test_g2p_launch_shapes_are_bit_identical(hip_libs, monkeypatch):
     """The fused G2P advances one chunk of 64 sorted particles per wave, or — from 1.5 M particles on, where the launch is
     bound by latency x occupancy — two, with both chunks' particle state requested up front (kernels_transfer.h). The
-    large-scene shape forced on small scenes (WGS_DEBUG = 131072) must give the same bits: elastic with the floor
+    large-scene shape forced on small scenes (WGS_DEBUG G2P_TWO_PASSES) must give the same bits: elastic with the floor
     (both bodies of the paired launch), plastic, 2D."""
     makes = (lambda: scenes.neo_hookean_cube(n_side=24, with_floor=True), lambda: scenes.sand_column(nx=12, ny=20, nz=12, with_floor=True),
              lambda: scenes.elastic_block_2d(nx=50, ny=40))
@@ -89,7 +89,7 @@ def test_g2p_launch_shapes_are_bit_identical(hip_libs, monkeypatch):
             sc["particles"].vel[:, 0] = 1.5
             return run_gpu(sc, 25).read_particles()
         a = run()
-        monkeypatch.setenv("WGS_DEBUG", "131072")
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_PASSES"))
         b = run()
         monkeypatch.delenv("WGS_DEBUG")
         for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
@@ -99,8 +99,8 @@ def test_g2p_launch_shapes_are_bit_identical(hip_libs, monkeypatch):
 @pytest.mark.parametrize("seed", [1, 4, 9, 12])
 def test_binning_inside_the_fused_g2p_is_bit_identical_to_the_rebin_launch(hip_libs, seed, monkeypatch):
     """Single-domain data: the fused G2P bins its own output for the next substep (new cell ids, block activation and totals,
-    mover lists: g2p_body.inc, Dev::bin_next), and launch 1 of that substep's sort (k_rebin) is not launched. WGS_DEBUG =
-    1048576 brings k_rebin back. The sort is only a permutation with a canonical order inside a cell, so 150 substeps — random
+    mover lists: g2p_body.inc, Dev::bin_next), and launch 1 of that substep's sort (k_rebin) is not launched. WGS_DEBUG
+    REBIN_LAUNCH brings k_rebin back. The sort is only a permutation with a canonical order inside a cell, so 150 substeps — random
     colliders, particles flying through blocks, two table rebuilds, the calls cut at odd places with a wgs_sync between them —
     must end bit-identical, particles, grid, block set and counts; and both must have counted the same cell-changers."""
     from helpers import pipeline
@@ -117,9 +117,9 @@ def test_binning_inside_the_fused_g2p_is_bit_identical_to_the_rebin_launch(hip_l
         return data.read_particles(), data.read_grid(), data.read_blocks(), data.stats()
     a, ga, ka, sa = run()
     # (... and launch 2 of the sort puts the members of a dirty block's cells in order by ranking the newcomers among the stayers;
-    # WGS_DEBUG = 16777216 keeps the insertion sort that covers the cases the ranking does not: the same order)
-    for switch in ("1048576", "16777216"):
-        monkeypatch.setenv("WGS_DEBUG", switch)
+    # WGS_DEBUG CELL_INSERTION_SORT keeps the insertion sort that covers the cases the ranking does not: the same order)
+    for switch in ("REBIN_LAUNCH", "CELL_INSERTION_SORT"):
+        monkeypatch.setenv("WGS_DEBUG", debug_switches(switch))
         b, gb, kb, sb = run()
         for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
             assert np.array_equal(getattr(a, f), getattr(b, f)), (switch, f)
@@ -172,7 +172,7 @@ def test_data_stepped_concurrently_on_their_own_streams_stay_bit_identical(hip_l
 def test_grid_update_inside_the_p2g_launch_is_bit_identical_to_its_own_launch(hip_libs, monkeypatch):
     """Single-domain simulations run the grid update as waves of the (last) P2G launch: P2G hands its slabs over
     inside the launch (write-through stores, one word per block), the waves gather past their XCD's L2
-    (kernels_transfer.h gu_waves). WGS_DEBUG = 262144 brings the launch of its own back: same sums in the same order, so
+    (kernels_transfer.h gu_waves). WGS_DEBUG GU_OWN_LAUNCH brings the launch of its own back: same sums in the same order, so
     the same bits — no colliders (one P2G launch), a floor in contact (two launches, then the paired one after the
     host has seen the list), plastic between walls, 2D; particles AND the grid (nodes, slabs' velocities feed the G2P)."""
     makes = (lambda: scenes.neo_hookean_cube(n_side=24), lambda: scenes.neo_hookean_cube(n_side=40, with_floor=True),
@@ -193,7 +193,7 @@ def test_grid_update_inside_the_p2g_launch_is_bit_identical_to_its_own_launch(hi
             pipe.step(data, 13)
             return data.read_particles(), data.read_grid(), data.read_body_poses()
         a, ga, ba = run()
-        monkeypatch.setenv("WGS_DEBUG", "262144")
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("GU_OWN_LAUNCH"))
         b, gb, bb = run()
         monkeypatch.delenv("WGS_DEBUG")
         for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
@@ -204,7 +204,7 @@ def test_grid_update_inside_the_p2g_launch_is_bit_identical_to_its_own_launch(hi
             for key in ("translation", "rotation", "linvel", "angvel"):
                 assert np.array_equal(x[key], y[key]), key
         if len(ba) > 1:      # moving bodies: integrate_bodies rides in the next substep's first sort launch (524288: a launch of its own)
-            monkeypatch.setenv("WGS_DEBUG", "524288")
+            monkeypatch.setenv("WGS_DEBUG", debug_switches("BODIES_OWN_LAUNCH"))
             c, _, bc = run()
             monkeypatch.delenv("WGS_DEBUG")
             for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
@@ -217,13 +217,13 @@ def test_grid_update_inside_the_p2g_launch_is_bit_identical_to_its_own_launch(hi
 @pytest.mark.parametrize("seed", [0, 3, 8])
 def test_steady_state_rebinning_is_bit_identical_to_full_binning(hip_libs, seed, monkeypatch):
     """k_rebin (re-binning relative to the previous substep's blocks) against the general k_bin forced on every
-    substep (WGS_DEBUG=128, read when the data is created): the sort is only a permutation, so 150 substeps —
+    substep (WGS_DEBUG NO_REBIN, read when the data is created): the sort is only a permutation, so 150 substeps —
     across two table rebuilds — must end bit-identical."""
     sc = _random_scene(seed)
     k = 150
     monkeypatch.setenv("WGS_REHASH_PERIOD", "64")             # (developer override, same results; the default is 1024)
     a = run_gpu(sc, k).read_particles()
-    monkeypatch.setenv("WGS_DEBUG", "128")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_REBIN"))
     b = run_gpu(sc, k).read_particles()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
@@ -232,7 +232,7 @@ def test_steady_state_rebinning_is_bit_identical_to_full_binning(hip_libs, seed,
 def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
     """Drucker-Prager sand between a floor and four walls, half of the blocks near a collider: after the first wgs_sync
     the fused G2P runs the variant compiled for 2 waves per SIMD (no spills in the CPIC body). Same source, another
-    register budget: the results must be the bits of the 3-waves variant (WGS_DEBUG = 16384 keeps that one), because
+    register budget: the results must be the bits of the 3-waves variant (WGS_DEBUG NO_G2P_DENSE keeps that one), because
     which of the two runs depends on when the host synchronised."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -250,7 +250,7 @@ def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
         data.sync()
         return data.read_particles()
     a = run()
-    monkeypatch.setenv("WGS_DEBUG", "16384")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_G2P_DENSE"))
     b = run()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
@@ -258,7 +258,7 @@ def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
     # the one-way P2G pair has two register budgets too (chosen from the particle count and the list length): force the
     # small one by making the scene "large" is not possible at this size, so compare the large budget (this scene's
     # choice) with the separate launches, and the small budget at a size that selects it below
-    monkeypatch.setenv("WGS_DEBUG", "8192")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("P2G_TWO_LAUNCHES"))
     c = run()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
         assert np.array_equal(getattr(a, f), getattr(c, f)), f
@@ -270,7 +270,7 @@ def test_large_one_way_scenes_do_not_depend_on_when_the_host_synchronised(hip_li
     """From 600 k particles on, one-way collider simulations always run the paired P2G launch with the CPIC body cut to
     168 VGPRs — a budget that differs from the unconstrained one in the last bit here and there, so it must not follow
     the near-collider list the host last saw. 640 k neo-Hookean particles lying on the floor: eight substeps in one call
-    and the same eight with a wgs_sync after the third end bit-identical; the unconstrained budget (WGS_DEBUG = 32768)
+    and the same eight with a wgs_sync after the third end bit-identical; the unconstrained budget (WGS_DEBUG NO_P2G_SMALL_BUDGET)
     agrees to round-off."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -289,7 +289,7 @@ def test_large_one_way_scenes_do_not_depend_on_when_the_host_synchronised(hip_li
     a, b = run((8,)), run((3, 5))
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    monkeypatch.setenv("WGS_DEBUG", "32768")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_P2G_SMALL_BUDGET"))
     c = run((3, 5))
     assert np.array_equal(a.cdf_affinity, c.cdf_affinity)
     for f in ("pos", "vel", "def_grad"):
@@ -405,7 +405,7 @@ def test_checkpoint_restart_with_a_rotated_fixed_collider_next_to_a_moving_one(h
 def test_a_body_crossing_the_grid_evicts_blocks_and_stays_bit_identical_to_the_rebuild_path(hip_libs, plastic, monkeypatch):
     """A cube flies through the grid and spins for 2 000 substeps: it leaves a trail of blocks nobody activates any more. Launch 2 of
     the sort evicts them (their table slots are marked, their ids reused: kernels_sort.h regroup_block) — no table rebuild but the
-    periodic ones; with WGS_DEBUG=1024 nothing is evicted and the table is rebuilt whenever three quarters of the ids are handed out.
+    periodic ones; with WGS_DEBUG NO_EVICTION nothing is evicted and the table is rebuilt whenever three quarters of the ids are handed out.
     The sort is only a permutation: the same bits either way, and the evicting run rebuilds less often."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -429,7 +429,7 @@ def test_a_body_crossing_the_grid_evicts_blocks_and_stays_bit_identical_to_the_r
             data.sync()
         return data.read_particles(), data.stats()
     a, sa = run()
-    monkeypatch.setenv("WGS_DEBUG", "1024")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_EVICTION"))
     b, sb = run()
     for f in ("pos", "vel", "def_grad", "affine", "dp_state"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
@@ -443,7 +443,7 @@ def test_node_cdf_summaries_shared_between_blocks_give_the_bits_of_whole_tile_ev
     """Where a collider moves, launch 2 of the sort evaluates every block's OWN nodes against the colliders and lets the block's
     neighbours know which of them have an affinity (Dev::block_cdf_summ, kernels_sort.h) instead of evaluating the (BW+2)^3 tile of
     every block — each node up to eight times. The class of a block (listed for the CPIC bodies or not) and everything downstream must
-    be what the whole-tile evaluation gives (WGS_DEBUG=2048), also when no word is ever waited for (WGS_DEBUG=2: every neighbour whose
+    be what the whole-tile evaluation gives (WGS_DEBUG NO_CDF_SUMM), also when no word is ever waited for (WGS_DEBUG CDF_SUMM_NO_WAIT: every neighbour whose
     word is late is evaluated locally — the path taken when a neighbour's wave is not resident)."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -467,8 +467,8 @@ def test_node_cdf_summaries_shared_between_blocks_give_the_bits_of_whole_tile_ev
     a, sa = run()
     assert sa["overflow"] == 0
     assert np.any(a.cdf_affinity != 0)   # (somebody is within reach of a collider)
-    for dbg in ("2048", "2"):
-        monkeypatch.setenv("WGS_DEBUG", dbg)
+    for dbg in ("NO_CDF_SUMM", "CDF_SUMM_NO_WAIT"):
+        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
         b, sb = run()
         for f in ("pos", "vel", "def_grad", "affine", "dp_state", "cdf_affinity", "cdf_normal", "cdf_dist"):
             assert np.array_equal(getattr(a, f), getattr(b, f)), (dbg, f)
@@ -479,7 +479,7 @@ def test_particle_cdf_by_prologue_waves_of_the_p2g_launch_gives_the_bits_of_the_
     """With a short near-collider list (as of the host's last look) the paired P2G launch computes the particle cdf of the listed
     blocks in prologue WAVES, one per visit-list entry, ahead of its workgroups, and hands the quads over inside the launch
     (written through, counted per block, fetched past the L2: kernels_transfer.h pcdf_waves) instead of in three to six rounds inside
-    each block's CPIC workgroup. Same particles, same arithmetic: the same bits as with WGS_DEBUG=4 (never prologue waves), substep
+    each block's CPIC workgroup. Same particles, same arithmetic: the same bits as with WGS_DEBUG NO_PCDF_WAVES (never prologue waves), substep
     after substep across host looks."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -503,8 +503,8 @@ def test_particle_cdf_by_prologue_waves_of_the_p2g_launch_gives_the_bits_of_the_
     assert sa["overflow"] == 0 and sa["num_near_collider_blocks"] > 0
     # 4: never prologue waves; 8: prologue workgroups sized for an empty list whatever the host saw — the launch then decides from the
     # lists of the substep itself (too long for so few waves: the blocks' workgroups do the work; short enough: the waves do)
-    for dbg in ("4", "8"):
-        monkeypatch.setenv("WGS_DEBUG", dbg)
+    for dbg in ("NO_PCDF_WAVES", "PCDF_WAVES_UNSIZED"):
+        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
         b, sb, bb = run()
         for f in ("pos", "vel", "def_grad", "affine", "dp_state", "cdf_affinity", "cdf_normal", "cdf_dist"):
             assert np.array_equal(getattr(a, f), getattr(b, f)), (dbg, f)
@@ -519,7 +519,7 @@ def test_direct_runs_of_unchanged_blocks_give_the_bits_of_the_gather_through_the
     """A block whose run is its previous run member for member (nobody moved, nobody arrived) is handed to the plain body of P2G with
     its cells' runs in the buffer's own coordinates: the particles are read where they are, without the gather through `perm`
     (layout.h CELL_DIRECT; one dependent round trip less per block). The same particles in the same order: the same bits as with
-    WGS_DEBUG = 33554432 (every block through the permutation) — a cube in free fall (every block direct), the cube landing on the floor
+    WGS_DEBUG NO_DIRECT_RUNS (every block through the permutation) — a cube in free fall (every block direct), the cube landing on the floor
     (direct and gathered blocks side by side, listed blocks beside them) and the cube crossing the grid and spinning (hardly any direct
     block; blocks becoming direct and dirty again), with a host look in between."""
     from helpers import pipeline
@@ -547,7 +547,7 @@ def test_direct_runs_of_unchanged_blocks_give_the_bits_of_the_gather_through_the
         assert st["overflow"] == 0
         return data.read_particles(), data.read_grid(), st
     a, ga, sta = run()
-    monkeypatch.setenv("WGS_DEBUG", "33554432")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_DIRECT_RUNS"))
     b, gb, stb = run()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f
@@ -560,7 +560,7 @@ def test_direct_runs_of_unchanged_blocks_give_the_bits_of_the_gather_through_the
 def test_large_two_way_scenes_with_the_near_collider_launch_first_give_the_bits_of_the_other_order(hip_libs, monkeypatch):
     """Large simulations with a body that moves (>= 600 k particles: BASELINE.json configs[3]) run P2G as two launches; since round 6 the
     near-collider launch goes FIRST and the grid update rides behind the plain launch (at the plain body's occupancy instead of the two-way
-    body's). Same slabs, same gather: the bits of the plain-launch-first order (WGS_DEBUG = 67108864), also across a host look."""
+    body's). Same slabs, same gather: the bits of the plain-launch-first order (WGS_DEBUG PLAIN_P2G_FIRST), also across a host look."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
     sc = scenes.config_scene("c4", n_side=86)
@@ -577,7 +577,7 @@ def test_large_two_way_scenes_with_the_near_collider_launch_first_give_the_bits_
         assert st["overflow"] == 0 and st["num_near_collider_blocks"] > 0
         return data.read_particles(), data.read_grid(), data.read_body_poses()
     a, ga, pa = run()
-    monkeypatch.setenv("WGS_DEBUG", "67108864")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("PLAIN_P2G_FIRST"))
     b, gb, pb = run()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
         assert np.array_equal(getattr(a, f), getattr(b, f)), f

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import devmath_truth as T
-from helpers import pipeline, report_margin
+from helpers import debug_switches, pipeline, report_margin
 from wgsparkl_amd import MpmData
 from wgsparkl_amd.models import MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
@@ -92,7 +92,7 @@ def _run(sc, state=None):
 
 
 CASES = {
-    # name: (model, plastic, uni_dp mode, per-particle material, collider, fracture, WGS_DEBUG)
+    # name: (model, plastic, uni_dp mode, per-particle material, collider, fracture, WGS_DEBUG switch)
     "elastic_corotated_uniform": (MODEL_COROTATED, False, None, False, False, False, None),
     "elastic_neo_hookean_fluid_uniform": (MODEL_NEO_HOOKEAN, False, None, False, False, False, None),
     "elastic_neo_hookean_per_particle": (MODEL_NEO_HOOKEAN, False, None, True, False, False, None),
@@ -101,9 +101,9 @@ CASES = {
     "plastic_mode2_fracture_collider": (MODEL_COROTATED, True, 2, False, True, True, None),
     "plastic_mode1_fracture_neo_hookean": (MODEL_NEO_HOOKEAN, True, 1, True, False, True, None),
     "plastic_mode0_per_particle_state": (MODEL_COROTATED, True, 0, True, False, False, None),
-    "plastic_forced_mode0_collider": (MODEL_COROTATED, True, 2, False, True, True, "65536"),
-    "plastic_mode2_two_pass": (MODEL_COROTATED, True, 2, False, False, True, "131072"),
-    "elastic_two_pass_collider": (MODEL_NEO_HOOKEAN, False, None, True, True, False, "131072"),
+    "plastic_forced_mode0_collider": (MODEL_COROTATED, True, 2, False, True, True, "NO_UNIFORM"),
+    "plastic_mode2_two_pass": (MODEL_COROTATED, True, 2, False, False, True, "G2P_TWO_PASSES"),
+    "elastic_two_pass_collider": (MODEL_NEO_HOOKEAN, False, None, True, True, False, "G2P_TWO_PASSES"),
 }
 
 
@@ -112,7 +112,7 @@ CASES = {
 def test_one_substep_constitutive_update_per_particle(hip_libs, monkeypatch, case, dim):
     model, plastic, mode, per_particle, collider, fracture, dbg = CASES[case]
     if dbg is not None:
-        monkeypatch.setenv("WGS_DEBUG", dbg)
+        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
     else:
         monkeypatch.delenv("WGS_DEBUG", raising=False)
     sc, fam = _scene(dim, model, plastic, mode, per_particle, collider, fracture, seed=zlib.crc32(case.encode()) % 1000 + dim)

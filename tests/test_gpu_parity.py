@@ -8,7 +8,7 @@ from wgsparkl_amd import scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, oracle, pipeline, rel_rms, report_margin, run_gpu, run_oracle
+from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, oracle, pipeline, rel_rms, report_margin, run_gpu, run_oracle
 from wgsparkl_amd import MpmData
 from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
                         _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
@@ -247,7 +247,7 @@ def test_visit_list_many_listed_blocks_per_chunk(hip_libs, oracle_libs, monkeypa
     check_blocks(data, st32)
     got, same = compare_cpic(data, st32, st64, 3, CPIC_GRID_V_TOL, CPIC_PART_TOL, min_same=0.995)
     assert (got.cdf_affinity & 1).sum() > 500
-    monkeypatch.setenv("WGS_DEBUG", "131072")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_PASSES"))
     b = run_gpu(sc, k).read_particles()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
         assert np.array_equal(getattr(got, f), getattr(b, f)), f
@@ -433,8 +433,8 @@ def test_long_near_collider_list_paths_match_the_separate_launches_and_the_oracl
     """Once wgs_sync has seen a long near-collider list, P2G runs its plain and its CPIC body in one launch (k_p2g_pair)
     and G2P sizes the list half of k_g2p_pair from it. A 262 k-particle corotated cube resting on the floor under a
     kinematic paddle (well over 8 listed blocks, two-way impulses on): the paired P2G ends bit-identical to the two separate
-    launches (WGS_DEBUG = 8192) — which path runs depends on when the host last synchronised, so the result must not —,
-    the paired G2P agrees with the separate kernels (WGS_DEBUG = 4096, a debug path; another compilation of the same
+    launches (WGS_DEBUG P2G_TWO_LAUNCHES) — which path runs depends on when the host last synchronised, so the result must not —,
+    the paired G2P agrees with the separate kernels (WGS_DEBUG G2P_TWO_LAUNCHES, a debug path; another compilation of the same
     source, one ulp apart), and the run matches the oracle."""
     from helpers import pipeline
     from wgsparkl_amd import MpmData
@@ -450,14 +450,14 @@ def test_long_near_collider_list_paths_match_the_separate_launches_and_the_oracl
         assert data.stats()["num_near_collider_blocks"] > 100  # a long list: the paired P2G launch is the one that ran
         return data.read_particles(), data.read_body_poses()
     pa, ba = run()
-    monkeypatch.setenv("WGS_DEBUG", "8192")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("P2G_TWO_LAUNCHES"))
     pb, bb = run()
     for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
         assert np.array_equal(getattr(pa, f), getattr(pb, f)), f
     for x, y in zip(ba, bb):
         for key in ("translation", "rotation", "linvel", "angvel"):
             assert np.array_equal(x[key], y[key]), key
-    monkeypatch.setenv("WGS_DEBUG", "4096")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_LAUNCHES"))
     pc, _ = run()
     assert np.array_equal(pa.cdf_affinity, pc.cdf_affinity)
     for f in ("pos", "vel", "def_grad"):

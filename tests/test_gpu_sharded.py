@@ -7,7 +7,7 @@ from wgsparkl_amd import scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
+from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
 from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
                         _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
 import os as _os
@@ -198,7 +198,7 @@ def test_dynamic_bodies_on_sharded_data(hip_libs, name):
 def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launch_is_bit_identical(hip_libs, dim, monkeypatch):
     """Inside wgs_sharded_step the waves that pack the outgoing messages and the grid update of the interior blocks ride in
     the P2G launch (GU = 3: slabs handed over word by word); the interface layers are updated after the
-    exchange. WGS_DEBUG = 262144 brings the k_pack_face launch and the one grid update back: the same bits on every slab
+    exchange. WGS_DEBUG GU_OWN_LAUNCH brings the k_pack_face launch and the one grid update back: the same bits on every slab
     (3 slabs in lockstep, a floor, particles migrating, a table rebuild inside the run)."""
     from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
@@ -226,19 +226,19 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
             sh.sync()
         return [sh.export() for sh in shards]
     a = run()
-    monkeypatch.setenv("WGS_DEBUG", "262144")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("GU_OWN_LAUNCH"))
     b = run()
     monkeypatch.delenv("WGS_DEBUG")
     # wgs_sharded_step with neighbours splits P2G: the two block layers at each cut first (their slabs are what the messages
     # are gathered from: they run beside the exchange on a stream of their own), every other block and the interior's grid
-    # update in a second launch. WGS_DEBUG = 4194304 splits the lockstep slabs the same way (on their one stream): same bits.
-    monkeypatch.setenv("WGS_DEBUG", "4194304")
+    # update in a second launch. WGS_DEBUG SHARD_SPLIT_LAYERS splits the lockstep slabs the same way (on their one stream): same bits.
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("SHARD_SPLIT_LAYERS"))
     c = run()
     monkeypatch.delenv("WGS_DEBUG")
     # A slab's fused G2P bins its residents for the next substep (the guests it drops leave their block's total) and
-    # k_g2p_arrivals the particles that arrive (Dev::bin_next); WGS_DEBUG = 1048576 brings launch 1 of the sort, k_rebin, back:
+    # k_g2p_arrivals the particles that arrive (Dev::bin_next); WGS_DEBUG REBIN_LAUNCH brings launch 1 of the sort, k_rebin, back:
     # the same bits, the same storage order.
-    monkeypatch.setenv("WGS_DEBUG", "1048576")
+    monkeypatch.setenv("WGS_DEBUG", debug_switches("REBIN_LAUNCH"))
     e = run()
     monkeypatch.delenv("WGS_DEBUG")
     for other in (b, c, e):

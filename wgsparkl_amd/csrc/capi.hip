@@ -91,8 +91,6 @@ struct wgs_data {
     wgs_pipeline *pipeline = nullptr;
     hipStream_t stream = nullptr;
     bool owns_stream = true;
-    hipStream_t stream2 = nullptr;   // wgs_sharded_step: the boundary layers' P2G and the exchange run here, beside the interior's P2G (capi_sharded.inc)
-    hipEvent_t ev_sorted = nullptr, ev_exchanged = nullptr;
     Dev dev{};
     int side = 0;
     bool plastic = false;
@@ -194,7 +192,7 @@ wgs_status alloc_grid(wgs_data *d) {
     GRID_ALLOC(&dev.hkeys, hcap);
     GRID_ALLOC(&dev.hvals, hcap);
     GRID_ALLOC(&dev.block_key, cap);
-    if (!(dev.dbg & 1024u)) {   // (eviction of blocks long inactive — slabs of a decomposition too since round 6; WGS_DEBUG bit 10 = never, the table is rebuilt instead)
+    if (!(dev.dbg & DBG_NO_EVICTION)) {   // (eviction of blocks long inactive — slabs of a decomposition too since round 6)
         GRID_ALLOC(&dev.block_slot, cap);
         GRID_ALLOC(&dev.free_ids, cap);
     }
@@ -342,7 +340,6 @@ void fill_collider(ColliderDev &c, const wgs_collider &in) {
     for (int k = 0; k < 3; k++) c.com[k] = in.com[k];
 }
 
-constexpr uint32_t WGS_LAUNCH_SHAPE_SWITCHES = 2u | 4u | 8u | 128u | 1024u | 2048u | 4096u | 8192u | 16384u | 32768u | 65536u | 131072u | 262144u | 524288u | 1048576u | 4194304u | 8388608u | 16777216u | 33554432u | 67108864u;  // WGS_DEBUG bits the shipped library honours
 #ifndef WGS_PCDF_WAVES_MAX_VISITS
 #define WGS_PCDF_WAVES_MAX_VISITS 256
 #endif
@@ -353,6 +350,12 @@ constexpr uint32_t P2G_SMALL_BUDGET_MIN_PARTICLES = 600000;  // one-way CPIC P2G
 #endif
 #ifndef WGS_GU_WG_PER_CU
 #define WGS_GU_WG_PER_CU 8
+#endif
+#ifndef WGS_PLASTIC_WPE_DENSE
+#define WGS_PLASTIC_WPE_DENSE 2
+#endif
+#ifndef WGS_PLASTIC_WPE
+#define WGS_PLASTIC_WPE G2P_WAVES_PER_EU
 #endif
 constexpr uint32_t P2G_PAIR_MIN_BLOCKS = 8;  // near-collider blocks from which P2G runs both bodies in one launch
 int grid_for(const wgs_data *d, int blocks_per_cu) { return d->pipeline->num_cus * blocks_per_cu; }
@@ -700,14 +703,272 @@ void resolve_timings(wgs_data *d) {
     d->timings_pending = false;
 }
 
+// ---- launch ladders of enqueue_substep: each takes the shape enqueue_substep decided and lists exactly the instantiations
+// that exist. (Templates on the dimension: they are instantiated where enqueue_substep reaches them, which keeps the kernels
+// in the code object in the order of their first use — placement alone moves a kernel by a few percent)
+
+// pack waves of a slab with neighbours: one per interface block as the host last saw the grid (a face holds a fraction of the
+// active blocks), plus a few for the guests
+struct PackWaves {
+    uint32_t blocks, guests;
+};
+PackWaves pack_waves(const wgs_data *d) {
+    return {std::max(64u, std::min(2048u, d->seen_nblocks ? d->seen_nblocks : 2048u)), std::max(1u, std::min(64u, (2u * d->link->mig_cap + 63u) / 64u))};
+}
+
+// launch 2 of the sort (kernels_sort.h): CDF = the node cdfs and block classes ride in it; SUMM = blocks share node-cdf summaries
+template <int DIM> void launch_regroup(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, uint32_t nscan, int have_old, bool cdf, bool summ) {
+    const dim3 b(SORT_THREADS);
+    if (cdf && dev.sharded && summ) hipLaunchKernelGGL((k_regroup<DIM, true, true, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf && dev.sharded) hipLaunchKernelGGL((k_regroup<DIM, true, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf && summ) hipLaunchKernelGGL((k_regroup<DIM, true, false, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf) hipLaunchKernelGGL((k_regroup<DIM, true, false>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (dev.sharded) hipLaunchKernelGGL((k_regroup<DIM, false, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else hipLaunchKernelGGL((k_regroup<DIM, false, false>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+}
+
+enum class P2gShape {
+    plain,       // no collider: the plain body
+    separate,    // the plain body, then the CPIC body (particle cdf in its prologue) in a launch of its own
+    cpic_first,  // the CPIC body first, then the plain body with the grid update riding in it
+    pair,        // both bodies in one launch (k_p2g_pair)
+};
+struct P2gLaunch {
+    P2gShape shape;
+    bool two_way;       // the two-way CPIC body
+    bool small_budget;  // pair, one-way: the CPIC body cut to 168 VGPRs
+    int gu;             // what rides in the last launch (kernels_transfer.h GU): 0 nothing, 2 the grid update, 3 a slab's pack waves + interior update
+    uint32_t wgs;       // workgroups per body
+    uint32_t ride;      // workgroups behind the P2G workgroups of the last launch: npack + the grid update's
+    uint32_t npack, npack_blk, layer_sel;
+    uint32_t npro;      // prologue workgroups (kernels_transfer.h pcdf_waves)
+};
+
+template <int DIM, bool TW, int WPE> void launch_p2g_pair(Dev &dev, hipStream_t s, int side, uint32_t epoch, const P2gLaunch &p) {
+    const dim3 g(p.npro + 2u * p.wgs + p.ride), b(P2GCfg<DIM>::NW * 64);
+    dev.pcdf_waves = p.npro;
+    if (p.gu == 2) hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 2>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    else if (p.gu == 3) hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 3>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    else hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 0>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    dev.pcdf_waves = 0u;
+}
+
+// the last P2G launch of the substep, with what rides behind its workgroups
+template <int DIM, bool CP, bool TW, bool PC> void launch_p2g_last(Dev &dev, hipStream_t s, int side, int filter, uint32_t epoch, const P2gLaunch &p) {
+    const uint32_t npro = PC ? p.npro : 0u;
+    const dim3 g(npro + p.wgs + p.ride), b(P2GCfg<DIM>::NW * 64);
+    dev.pcdf_waves = npro;
+    if (p.gu == 2) hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 2>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    else if (p.gu == 3) hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 3>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    else hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 0>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    dev.pcdf_waves = 0u;
+}
+
+template <int DIM> void launch_p2g(Dev &dev, hipStream_t s, int side, uint32_t epoch, const P2gLaunch &p) {
+    const dim3 g(p.wgs), b(P2GCfg<DIM>::NW * 64);
+    switch (p.shape) {
+        case P2gShape::pair:
+            if (p.two_way) launch_p2g_pair<DIM, true, 1>(dev, s, side, epoch, p);
+            else if (p.small_budget) launch_p2g_pair<DIM, false, 3>(dev, s, side, epoch, p);
+            else launch_p2g_pair<DIM, false, 1>(dev, s, side, epoch, p);
+            break;
+        case P2gShape::cpic_first:
+            dev.pcdf_waves = p.npro;
+            hipLaunchKernelGGL((k_p2g<DIM, true, true, true, 1>), dim3(p.npro + p.wgs), b, 0, s, dev, side, 2, epoch, p.wgs, 0u, 0u, p.layer_sel, p.npro);
+            dev.pcdf_waves = 0u;
+            hipLaunchKernelGGL((k_p2g<DIM, false, false, false, 2, true>), dim3(p.wgs + p.ride), b, 0, s, dev, side, 1, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, 0u);
+            break;
+        case P2gShape::separate:
+            // (the first of the two launches hands its slabs over like the last one when anything rides in that one)
+            if (p.gu != 0) hipLaunchKernelGGL((k_p2g<DIM, false, false, false, 1>), g, b, 0, s, dev, side, 1, epoch, p.wgs, 0u, 0u, p.layer_sel, 0u);
+            else hipLaunchKernelGGL((k_p2g<DIM, false>), g, b, 0, s, dev, side, 1, epoch, p.wgs, 0u, 0u, p.layer_sel, 0u);
+            // near-collider list: particle cdf in the prologue (the node cdfs are complete: k_setup_scatter<CDF>, or
+            // k_cdf after k_p2g_cdf with mesh colliders), then the CPIC transfer
+            if (p.two_way) launch_p2g_last<DIM, true, true, true>(dev, s, side, 2, epoch, p);
+            else launch_p2g_last<DIM, true, false, true>(dev, s, side, 2, epoch, p);
+            break;
+        case P2gShape::plain:
+            launch_p2g_last<DIM, false, false, false>(dev, s, side, 0, epoch, p);
+            break;
+    }
+}
+
+// PHASE 0: every block of single-domain data; 3: a slab's blocks after the exchange (iface_only: the interior's rode in P2G)
+template <int DIM> void launch_grid_update(const Dev &dev, hipStream_t s, dim3 g, uint32_t epoch, bool slab, bool two_way, uint32_t iface_only) {
+    if (!slab && two_way) hipLaunchKernelGGL((k_grid_update<DIM, 0, true>), g, dim3(256), 0, s, dev, epoch, 0u);
+    else if (!slab) hipLaunchKernelGGL((k_grid_update<DIM, 0>), g, dim3(256), 0, s, dev, epoch, 0u);
+    else if (two_way) hipLaunchKernelGGL((k_grid_update<DIM, 3, true>), g, dim3(256), 0, s, dev, epoch, iface_only);
+    else hipLaunchKernelGGL((k_grid_update<DIM, 3>), g, dim3(256), 0, s, dev, epoch, iface_only);
+}
+
+enum class G2pShape {
+    single,        // no collider: one launch
+    two_launches,  // the plain body, then the CPIC body in a launch of its own
+    pair,          // both bodies in one launch (k_g2p_pair)
+    pair_dense,    // ... in the spill-free plastic variant
+};
+struct G2pLaunch {
+    G2pShape shape;
+    bool shard;
+    uint32_t g;      // main-body waves: one per `npass` chunks of 64 sorted particles, a multiple of 8 (XCD-aware mapping)
+    uint32_t nlist;  // list waves per XCD of the CPIC body (8 x nlist in all)
+};
+
+// (the decomposition is a template parameter of the fused G2P: kernels_transfer.h; BIN: not the plastic variants)
+template <int DIM, int MODEL, bool PL, int NP, class Mark>
+void launch_g2p_shape(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
+    constexpr int WPE = PL ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, WPE_DENSE = PL ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU;
+    const dim3 g(p.g), pg(p.g + 8u * p.nlist), t(G2P_THREADS);
+    switch (p.shape) {
+        case G2pShape::pair_dense:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            break;
+        case G2pShape::pair:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            break;
+        case G2pShape::two_launches:
+            hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 1, NP, false, !PL>), g, t, 0, s, dev, side, epoch);
+            mark(6);
+            hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 2, 1, false, !PL>), dim3(8u * p.nlist), t, 0, s, dev, side, epoch);
+            break;
+        case G2pShape::single:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, true, !PL>), g, t, 0, s, dev, side, epoch);
+            else hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, false, !PL>), g, t, 0, s, dev, side, epoch);
+            break;
+    }
+}
+
+template <int DIM, int MODEL, bool PL, class Mark>
+void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
+    if (dev.g2p_npass == (uint32_t)G2P_MANY_PASSES) launch_g2p_shape<DIM, MODEL, PL, G2P_MANY_PASSES>(dev, s, side, epoch, p, mark);
+    else if (dev.g2p_npass == 2u) launch_g2p_shape<DIM, MODEL, PL, 2>(dev, s, side, epoch, p, mark);
+    else launch_g2p_shape<DIM, MODEL, PL, 1>(dev, s, side, epoch, p, mark);
+}
+
+// the fused G2P; `mark(6)` between the two launches of that shape
+template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
+    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+        case 0: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
+        case 1: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
+        case 2: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
+        default: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
+    }
+}
+
+template <int DIM> void launch_arrivals(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, bool plastic) {
+    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case 1: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case 2: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        default: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+    }
+}
+
+// The shape of this substep's P2G (`part`, `p2g_sel`: enqueue_substep). Sets what the grid update that follows needs to know.
+P2gLaunch plan_p2g(wgs_data *d, int part, int p2g_sel) {
+    const Dev &dev = d->dev;
+    const uint32_t n = dev.n;
+    const uint32_t NW = (uint32_t)P2GCfg<D>::NW;
+    P2gLaunch p{};
+    p.two_way = d->two_way;
+    p.layer_sel = p2g_sel == 2 ? 1u : p2g_sel == 3 ? 2u : 0u;   // (kernels_transfer.h: boundary layers / the others)
+    // Workgroups per body: about one per two entries of the block list (as the host last saw it), between 8 and
+    // 32 per CU. A workgroup strides over the list, and the dispatcher balances better than a fixed stride does:
+    // blocks differ in cost, and with 5 per CU — one resident round and a quarter — the quarter started when the
+    // first workgroups retired (C5, 16 M particles: P2G 472 -> 346 us; C2: 35.6 -> 31.8 us). Same results for
+    // any grid: a block's slab is the work of one workgroup.
+    p.wgs = std::min((uint32_t)grid_for(d, 32), std::max((uint32_t)grid_for(d, 8), (d->seen_nblocks / 2u + 255u) & ~255u));
+    // Single-domain simulations: the grid update rides in the (last) P2G launch as workgroups of its own
+    // behind the P2G workgroups (kernels_transfer.h gu_waves; GU = 2), one wave per active block as the host last saw
+    // them; a P2G launch before it hands its slabs over the same way (GU = 1). Same results as the launch of its own
+    // (DBG_GU_OWN_LAUNCH): the same sums in the same order.
+    const bool fuse_gu = part == 0 && !dev.sharded && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    // Inside wgs_sharded_step (part 1 of a slab's substep): behind the P2G workgroups ride the waves that pack the
+    // outgoing messages (no k_pack_face launch) and the grid update of the INTERIOR blocks — everything that does
+    // not wait for the exchange; the interface layers are updated after it (GU = 3).
+    const bool fuse_shard = part == 1 && d->in_sharded_step && d->link && d->link->attached && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    p.gu = fuse_gu ? 2 : fuse_shard ? 3 : 0;
+    d->gu_fused = fuse_gu;
+    d->shard_fused = fuse_shard;
+    // (8, 16, 32 or 64 workgroups per CU at most: the same times at C2 / C3 / C5)
+    const uint32_t gu_wgs = (p.gu == 0 || p2g_sel == 2) ? 0u : std::min((uint32_t)grid_for(d, 8), std::max((uint32_t)grid_for(d, 1), ((d->seen_nblocks + NW - 1u) / NW + 7u) & ~7u));
+    if (fuse_shard && (d->link->has_lower || d->link->has_upper) && p2g_sel != 3) {   // (they ride behind the boundary layers' P2G)
+        const PackWaves pw = pack_waves(d);
+        p.npack_blk = pw.blocks;
+        p.npack = (pw.blocks + pw.guests + NW - 1u) / NW;
+    }
+    p.ride = p.npack + gu_wgs;
+    // Prologue waves (kernels_transfer.h pcdf_waves): the particle cdf of the listed blocks by one wave per visit-list entry in front
+    // of the paired launch, while the lists are short enough for the idle part of the chip to take them at once (as of the
+    // host's last look: the waves stride over whatever the lists hold now). Single-domain data only: a slab's pack waves read
+    // the guests' quads inside the launch.
+    if (d->cpic && !dev.sharded && d->last_nvisit != UINT32_MAX && d->last_nvisit != 0u && d->last_nvisit <= PCDF_WAVES_MAX_VISITS && !(dev.dbg & DBG_NO_PCDF_WAVES))
+        p.npro = 8u * ((std::min(d->last_nvisit + 8u, dev.visit_cap) + NW - 1u) / NW);
+    if (d->cpic && !dev.sharded && (dev.dbg & DBG_PCDF_WAVES_UNSIZED)) p.npro = 8u;   // (the launch itself then decides, device_math.h pcdf_waves_on)
+    if (!d->cpic) {
+        p.shape = P2gShape::plain;
+        return p;
+    }
+    // Large one-way collider simulations ALWAYS run the paired launch, with the CPIC body cut to 168 VGPRs: the
+    // plain body then keeps its occupancy, so the pair costs nothing while the list is empty, and the choice
+    // does not follow the host's syncs (the two budgets differ in the last bit here and there).
+    p.small_budget = !d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES && !(dev.dbg & DBG_NO_P2G_SMALL_BUDGET);
+    // Large TWO-WAY simulations never pair: the kernel would take the two-way CPIC body's 225 registers and the plain
+    // body — nearly every block — would run at two thirds of its occupancy (C4, 8 M particles: P2G 416 -> 347 us
+    // with the two launches). Bit-identical either way (the same body text under -ffp-contract=on).
+    const bool big_two_way = d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES;
+    // (small two-way scenes pair whatever the list length: they fill less than one round of workgroups, so the plain body's lost
+    // occupancy costs nothing and a launch goes — the reference's sand2, 490 k particles, 2D: 76-79 -> 67-68 us per substep;
+    // the one-way 262 k cube: P2G 20.4 + a boundary -> 18.3 us, not taken: its fused G2P then ran 27 us every other run against 21-22)
+    const bool small_two_way = d->two_way && n < P2G_SMALL_BUDGET_MIN_PARTICLES;
+    // many blocks near colliders (as of the last wgs_sync): both bodies in one launch
+    const bool many_listed = d->last_ncpic != UINT32_MAX && d->last_ncpic >= P2G_PAIR_MIN_BLOCKS;
+    if (!big_two_way && (p.small_budget || small_two_way || many_listed) && !(dev.dbg & DBG_P2G_TWO_LAUNCHES))
+        p.shape = P2gShape::pair;
+    // Large two-way simulations on a single domain: the near-collider launch FIRST, the plain launch behind it with the grid
+    // update riding in IT. The grid-update waves take the registers of the launch they ride in: behind the two-way body (209
+    // registers, two waves per SIMD) the update of every block of the scene ran at two thirds of the occupancy it has behind
+    // the plain body (160), and started only when the last near-collider workgroup — a 30 us chain each — had a slot. Same
+    // sums in the same order (DBG_PLAIN_P2G_FIRST = the plain launch first, as before: tested bit-identical).
+    else if (big_two_way && p.gu == 2 && !(dev.dbg & DBG_PLAIN_P2G_FIRST))
+        p.shape = P2gShape::cpic_first;
+    else
+        p.shape = P2gShape::separate;
+    return p;
+}
+
+// The shape of this substep's fused G2P (dev.g2p_npass set).
+G2pLaunch plan_g2p(const wgs_data *d) {
+    const Dev &dev = d->dev;
+    const uint32_t npass = dev.g2p_npass;
+    // the list walk of the CPIC body: a wave and a half per SIMD unless the host saw the visit lists
+    const uint32_t full = (uint32_t)grid_for(d, 1) * 3u / 2u;
+    G2pLaunch p{G2pShape::single, dev.sharded != 0u, ((dev.nv + G2P_THREADS * npass - 1) / (G2P_THREADS * npass) + 7) / 8 * 8, full};
+    // (a slab always takes the paired / single-body launch shapes, the two-launch debug shape exists for single-domain data only)
+    if (d->cpic && (p.shard || !(dev.dbg & DBG_G2P_TWO_LAUNCHES))) {
+        // both bodies in one launch; list waves (8 x nlist; the waves of an XCD stride over the runs of its visit list): 2 x the
+        // runs of the longest list as the host last saw it
+        const uint32_t per_run = std::min<uint32_t>(npass, WGS_G2P_LIST_PASSES);
+        if (d->last_nvisit != UINT32_MAX) p.nlist = std::min(full, std::max(8u, 2u * ((d->last_nvisit + per_run - 1u) / per_run)));
+        // plastic scenes with a large share of listed blocks: the spill-free variant (kernels_transfer.h)
+        const bool dense = d->plastic && d->last_ncpic != UINT32_MAX && d->last_ncpic * 2u >= std::max(1u, d->last_nblocks) && !(dev.dbg & DBG_NO_G2P_DENSE);
+        p.shape = dense ? G2pShape::pair_dense : G2pShape::pair;
+    } else if (d->cpic) {
+        p.shape = G2pShape::two_launches;
+    }
+    return p;
+}
+
 // One substep = pipeline.rs:201-280 (MPM passes), enqueued on the data's stream.
 // part 0 = the whole substep (single GPU, or a slab stepped without its neighbours); the sharded step splits it around
 // its one neighbour exchange: part 1 = sort .. P2G, part 2 = grid update + fused G2P (+ the arrivals' G2P) + bodies.
-// `p2g_sel` splits part 1 further (wgs_sharded_step with neighbours): 0 = all of it; 1 = the sort only; 2 = P2G of the boundary
-// layers with the pack waves behind it, on the data's SECOND stream; 3 = P2G of all other blocks with the interior's grid update.
+// `p2g_sel` splits part 1 further (DBG_SHARD_SPLIT_LAYERS on lockstep slabs): 0 = all of it; 1 = the sort only; 2 = P2G of the
+// boundary layers with the pack waves behind it; 3 = P2G of all other blocks with the interior's grid update.
 template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part, int p2g_sel = 0) {
     Dev &dev = d->dev;
-    hipStream_t s = (p2g_sel == 2 && d->stream2) ? d->stream2 : d->stream;
+    hipStream_t s = d->stream;
     const bool first = part != 2 && p2g_sel <= 1;   // the first call of this substep
     const int side = d->side;
     const uint32_t n = dev.n;
@@ -728,7 +989,7 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
     // (2D: the body keeps no state of the chunk after the next one — at most two chunks per wave)
     const uint32_t nv_now = dev.sharded && d->nv_hint != 0u ? std::min(d->nv_hint, dev.nv) : dev.nv;   // (a slab launches for its capacity)
     dev.g2p_npass = (D == 3 && nv_now >= G2P_MANY_PASS_MIN_PARTICLES) ? (uint32_t)G2P_MANY_PASSES
-                    : (nv_now >= G2P_TWO_PASS_MIN_PARTICLES || (dev.dbg & 131072u)) ? 2u : 1u;
+                    : (nv_now >= G2P_TWO_PASS_MIN_PARTICLES || (dev.dbg & DBG_G2P_TWO_PASSES)) ? 2u : 1u;
     // Steady state: the buffer is in the sorted order of the previous substep, whose block ids, cell ids
     // (perm_cell) and neighbour links are still valid, so the particles are re-binned RELATIVE to their old
     // block (k_rebin: no hash lookups except for the few particles that changed block). The full k_bin runs
@@ -744,9 +1005,9 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
     dev.cdf_moving = d->moving_mask;
     const bool fused_cdf = d->cpic && dev.n_rigid == 0;  // (mesh cdfs are only complete after k_p2g_cdf)
     if (first) dev.listed_in_perm = fused_cdf ? 1u : 0u;  // (part 2 of a sharded substep consumes what its part 1 wrote)
-    const bool use_rebin = d->prev_sorted && !rehash && !(dev.dbg & 128u);
+    const bool use_rebin = d->prev_sorted && !rehash && !(dev.dbg & DBG_NO_REBIN);
     // The fused G2P of this substep also bins its output for the next one (g2p_body.inc, Dev::bin_next; slabs too), unless
-    // that substep rebuilds the table anyway (dbg bit 20 brings launch 1 of the sort, k_rebin, back: same results, tested).
+    // that substep rebuilds the table anyway (DBG_REBIN_LAUNCH brings launch 1 of the sort, k_rebin, back: same results, tested).
     // `prebinned`: the previous substep's G2P did so for this one.
     const bool binned = use_rebin && d->prebinned;
     if (first && d->prebinned && !binned) {
@@ -761,7 +1022,7 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
     // instruction cache, cost a third of the launch — and launch 1 of the sort, k_rebin, stays)
     // (a slab: its fused G2P bins the residents — the guests it drops leave their block's total —, k_g2p_arrivals the particles that
     // arrive; both parts of a sharded substep see the same value)
-    dev.bin_next = (!d->plastic && !(dev.dbg & (128u | 1048576u)) && (d->rehash_period == 0u || (d->substeps + 1) % d->rehash_period != 0)) ? 1u : 0u;
+    dev.bin_next = (!d->plastic && !(dev.dbg & (DBG_NO_REBIN | DBG_REBIN_LAUNCH)) && (d->rehash_period == 0u || (d->substeps + 1) % d->rehash_period != 0)) ? 1u : 0u;
     // the fused G2P drops the guests only inside the sharded step (kernels_shard.h); wgs_step on a slab advances what it holds
     dev.skip_guests = (d->in_sharded_step && dev.sharded) ? 1u : 0u;
     if (dev.sharded && d->needs_compact && first) {
@@ -817,13 +1078,8 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
                 const int have_old = use_rebin ? 1 : 0;
                 // (summ: every block within reach of a collider is evaluated substep after substep — each evaluates its own nodes and
                 // tells its neighbours, kernels_sort.h block_cdf_summ; with colliders at rest: the instantiation without)
-                const bool summ = (dev.cdf_moving != 0u || dev.cdf_gen == 0u) && !(dev.dbg & 2048u);
-                if (fused_cdf && dev.sharded && summ) hipLaunchKernelGGL((k_regroup<D, true, true, true>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
-                else if (fused_cdf && dev.sharded) hipLaunchKernelGGL((k_regroup<D, true, true>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
-                else if (fused_cdf && summ) hipLaunchKernelGGL((k_regroup<D, true, false, true>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
-                else if (fused_cdf) hipLaunchKernelGGL((k_regroup<D, true, false>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
-                else if (dev.sharded) hipLaunchKernelGGL((k_regroup<D, false, true>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
-                else hipLaunchKernelGGL((k_regroup<D, false, false>), g, dim3(SORT_THREADS), 0, s, dev, side, epoch, nscan, have_old);
+                const bool summ = (dev.cdf_moving != 0u || dev.cdf_gen == 0u) && !(dev.dbg & DBG_NO_CDF_SUMM);
+                launch_regroup<D>(dev, s, g, side, epoch, nscan, have_old, fused_cdf, summ);
             }
         } else {
             HIP_TRY(hipMemsetAsync(dev.counters + CTR_NBLOCKS, 0, sizeof(uint32_t), s));
@@ -839,204 +1095,26 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
         mark(3);
     }
     if (part != 2 && p2g_sel != 1) {
-        const uint32_t layer_sel = p2g_sel == 2 ? 1u : p2g_sel == 3 ? 2u : 0u;   // (kernels_transfer.h: boundary layers / the others)
-        if (n > 0) {
-            // ---- "p2g"
-            // Workgroups per body: about one per two entries of the block list (as the host last saw it), between 8 and
-            // 32 per CU. A workgroup strides over the list, and the dispatcher balances better than a fixed stride does:
-            // blocks differ in cost, and with 5 per CU — one resident round and a quarter — the quarter started when the
-            // first workgroups retired (C5, 16 M particles: P2G 472 -> 346 us; C2: 35.6 -> 31.8 us). Same results for
-            // any grid: a block's slab is the work of one workgroup.
-            const uint32_t p2g_wgs = std::min((uint32_t)grid_for(d, 32), std::max((uint32_t)grid_for(d, 8), (d->seen_nblocks / 2u + 255u) & ~255u));
-            const dim3 p2g_grid(p2g_wgs), p2g_block(P2GCfg<D>::NW * 64);
-            // Large one-way collider simulations ALWAYS run the paired launch, with the CPIC body cut to 168 VGPRs: the
-            // plain body then keeps its occupancy, so the pair costs nothing while the list is empty, and the choice
-            // does not follow the host's syncs (the two budgets differ in the last bit here and there).
-            const bool big_one_way = !d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES && !(dev.dbg & 32768u);
-            // Single-domain simulations: the grid update rides in the (last) P2G launch as workgroups of its own
-            // behind the P2G workgroups (kernels_transfer.h gu_waves; GU = 2), one wave per active block as the host last saw
-            // them; a P2G launch before it hands its slabs over the same way (GU = 1). Same results as the launch of its own
-            // (dbg bit 18 brings that back): the same sums in the same order.
-            const bool fuse_gu = part == 0 && !dev.sharded && !(dev.dbg & 262144u);
-            // Inside wgs_sharded_step (part 1 of a slab's substep): behind the P2G workgroups ride the waves that pack the
-            // outgoing messages (no k_pack_face launch) and the grid update of the INTERIOR blocks — everything that does
-            // not wait for the exchange; the interface layers are updated after it (GU = 3).
-            const bool fuse_shard = part == 1 && d->in_sharded_step && d->link && d->link->attached && !(dev.dbg & 262144u);
-            const int gum = fuse_gu ? 2 : fuse_shard ? 3 : 0;   // what rides in the LAST P2G launch of this substep
-            const uint32_t NW = (uint32_t)P2GCfg<D>::NW;
-            // (8, 16, 32 or 64 workgroups per CU at most: the same times at C2 / C3 / C5)
-            const uint32_t gu_wgs = (gum == 0 || p2g_sel == 2) ? 0u : std::min((uint32_t)grid_for(d, 8), std::max((uint32_t)grid_for(d, 1), ((d->seen_nblocks + NW - 1u) / NW + 7u) & ~7u));
-            // pack waves: one per interface block as the host last saw the grid (a face holds a fraction of the active
-            // blocks), plus a few for the guests
-            uint32_t npack = 0u, npack_blk = 0u;
-            if (fuse_shard && (d->link->has_lower || d->link->has_upper) && p2g_sel != 3) {   // (they ride behind the boundary layers' P2G)
-                npack_blk = std::max(64u, std::min(2048u, d->seen_nblocks ? d->seen_nblocks : 2048u));
-                const uint32_t nmig = std::max(1u, std::min(64u, (2u * d->link->mig_cap + 63u) / 64u));
-                npack = (npack_blk + nmig + NW - 1u) / NW;
-            }
-            d->gu_fused = fuse_gu;
-            d->shard_fused = fuse_shard;
-            const uint32_t ride = npack + gu_wgs;   // workgroups behind the P2G workgroups
-            // Large TWO-WAY simulations never pair: the kernel would take the two-way CPIC body's 225 registers and the plain
-            // body — nearly every block — would run at two thirds of its occupancy (C4, 8 M particles: P2G 416 -> 347 us
-            // with the two launches). Bit-identical either way (the same body text under -ffp-contract=on).
-            const bool big_two_way = d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES;
-            // Prologue waves (kernels_transfer.h pcdf_waves): the particle cdf of the listed blocks by one wave per visit-list entry in front
-            // of the paired launch, while the lists are short enough for the idle part of the chip to take them at once (as of the
-            // host's last look: the waves stride over whatever the lists hold now). Single-domain data only: a slab's pack waves read
-            // the guests' quads inside the launch. WGS_DEBUG bit 2 (value 4) = never.
-            uint32_t npro = 0u;
-            if (d->cpic && !dev.sharded && d->last_nvisit != UINT32_MAX && d->last_nvisit != 0u && d->last_nvisit <= PCDF_WAVES_MAX_VISITS && !(dev.dbg & 4u))
-                npro = 8u * ((std::min(d->last_nvisit + 8u, dev.visit_cap) + NW - 1u) / NW);
-            if (d->cpic && !dev.sharded && (dev.dbg & 8u)) npro = 8u;   // (tests: waves sized for a list the host never saw grow — the launch itself then decides, device_math.h pcdf_waves_on)
-            dev.pcdf_waves = 0u;
-#define WGS_P2G_PAIR(TW, WPE)                                                                                                          \
-    do {                                                                                                                               \
-        dev.pcdf_waves = npro;                                                                                                                 \
-        const dim3 pg(npro + 2u * p2g_wgs + ride);                                                                                     \
-        if (gum == 2) hipLaunchKernelGGL((k_p2g_pair<D, TW, WPE, 2>), pg, p2g_block, 0, s, dev, side, epoch, p2g_wgs, npack, npack_blk, layer_sel, npro);      \
-        else if (gum == 3) hipLaunchKernelGGL((k_p2g_pair<D, TW, WPE, 3>), pg, p2g_block, 0, s, dev, side, epoch, p2g_wgs, npack, npack_blk, layer_sel, npro); \
-        else hipLaunchKernelGGL((k_p2g_pair<D, TW, WPE, 0>), pg, p2g_block, 0, s, dev, side, epoch, p2g_wgs, npack, npack_blk, layer_sel, npro);               \
-        dev.pcdf_waves = 0u;                                                                                                           \
-    } while (0)
-#define WGS_P2G_LAST(CP, TW, PC, FILTER)                                                                                                        \
-    do {                                                                                                                                        \
-        const uint32_t np_ = (PC) ? npro : 0u;                                                                                                  \
-        dev.pcdf_waves = np_;                                                                                                                    \
-        const dim3 lg(np_ + p2g_wgs + ride);                                                                                                    \
-        if (gum == 2) hipLaunchKernelGGL((k_p2g<D, CP, TW, PC, 2>), lg, p2g_block, 0, s, dev, side, FILTER, epoch, p2g_wgs, npack, npack_blk, layer_sel, np_);        \
-        else if (gum == 3) hipLaunchKernelGGL((k_p2g<D, CP, TW, PC, 3>), lg, p2g_block, 0, s, dev, side, FILTER, epoch, p2g_wgs, npack, npack_blk, layer_sel, np_);   \
-        else hipLaunchKernelGGL((k_p2g<D, CP, TW, PC, 0>), lg, p2g_block, 0, s, dev, side, FILTER, epoch, p2g_wgs, npack, npack_blk, layer_sel, np_);                 \
-        dev.pcdf_waves = 0u;                                                                                                                    \
-    } while (0)
-            // (small two-way scenes pair whatever the list length: they fill less than one round of workgroups, so the plain body's lost
-            // occupancy costs nothing and a launch goes — the reference's sand2, 490 k particles, 2D: 76-79 -> 67-68 us per substep;
-            // the one-way 262 k cube: P2G 20.4 + a boundary -> 18.3 us, not taken: its fused G2P then ran 27 us every other run against 21-22)
-            const bool small_two_way = d->two_way && n < P2G_SMALL_BUDGET_MIN_PARTICLES;
-            if (d->cpic && !big_two_way && (big_one_way || small_two_way || (d->last_ncpic != UINT32_MAX && d->last_ncpic >= P2G_PAIR_MIN_BLOCKS)) && !(dev.dbg & 8192u)) {
-                // many blocks near colliders (as of the last wgs_sync): both bodies in one launch (k_p2g_pair)
-                if (d->two_way) WGS_P2G_PAIR(true, 1);
-                else if (big_one_way) WGS_P2G_PAIR(false, 3);
-                else WGS_P2G_PAIR(false, 1);
-            } else if (d->cpic && big_two_way && gum == 2 && !(dev.dbg & 67108864u)) {
-                // Large two-way simulations on a single domain: the near-collider launch FIRST, the plain launch behind it with the grid
-                // update riding in IT. The grid-update waves take the registers of the launch they ride in: behind the two-way body (209
-                // registers, two waves per SIMD) the update of every block of the scene ran at two thirds of the occupancy it has behind
-                // the plain body (160), and started only when the last near-collider workgroup — a 30 us chain each — had a slot. Same
-                // sums in the same order (WGS_DEBUG bit 26 = the plain launch first, as before: tested bit-identical).
-                {
-                    dev.pcdf_waves = npro;
-                    const dim3 lg(npro + p2g_wgs);
-                    hipLaunchKernelGGL((k_p2g<D, true, true, true, 1>), lg, p2g_block, 0, s, dev, side, 2, epoch, p2g_wgs, 0u, 0u, layer_sel, npro);
-                    dev.pcdf_waves = 0u;
-                }
-                hipLaunchKernelGGL((k_p2g<D, false, false, false, 2, true>), dim3(p2g_wgs + ride), p2g_block, 0, s, dev, side, 1, epoch, p2g_wgs, npack, npack_blk, layer_sel, 0u);
-            } else if (d->cpic) {
-                // (the first of the two launches hands its slabs over like the last one when anything rides in that one)
-                if (gum != 0) hipLaunchKernelGGL((k_p2g<D, false, false, false, 1>), p2g_grid, p2g_block, 0, s, dev, side, 1, epoch, p2g_wgs, 0u, 0u, layer_sel, 0u);
-                else hipLaunchKernelGGL((k_p2g<D, false>), p2g_grid, p2g_block, 0, s, dev, side, 1, epoch, p2g_wgs, 0u, 0u, layer_sel, 0u);
-                // near-collider list: particle cdf in the prologue (the node cdfs are complete: k_setup_scatter<CDF>, or
-                // k_cdf after k_p2g_cdf with mesh colliders), then the CPIC transfer
-                if (d->two_way) WGS_P2G_LAST(true, true, true, 2);
-                else WGS_P2G_LAST(true, false, true, 2);
-            } else {
-                WGS_P2G_LAST(false, false, false, 0);
-            }
-#undef WGS_P2G_PAIR
-#undef WGS_P2G_LAST
-        }
+        if (n > 0) launch_p2g<D>(dev, s, side, epoch, plan_p2g(d, part, p2g_sel));   // ---- "p2g"
         mark(4);
     }
     if (part != 1) {
-        if (n > 0 && !(part == 0 && d->gu_fused)) {
-            // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
-            if (part == 0 && d->two_way)
-                hipLaunchKernelGGL((k_grid_update<D, 0, true>), dim3(grid_for(d, WGS_GU_WG_PER_CU)), dim3(256), 0, s, dev, epoch, 0u);
-            else if (part == 0) hipLaunchKernelGGL((k_grid_update<D, 0>), dim3(grid_for(d, WGS_GU_WG_PER_CU)), dim3(256), 0, s, dev, epoch, 0u);
-            else if (d->two_way) hipLaunchKernelGGL((k_grid_update<D, 3, true>), dim3(grid_for(d, WGS_GU_WG_PER_CU)), dim3(256), 0, s, dev, epoch, d->shard_fused ? 1u : 0u);
-            else hipLaunchKernelGGL((k_grid_update<D, 3>), dim3(grid_for(d, WGS_GU_WG_PER_CU)), dim3(256), 0, s, dev, epoch, d->shard_fused ? 1u : 0u);
-        }
+        // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
+        if (n > 0 && !(part == 0 && d->gu_fused))
+            launch_grid_update<D>(dev, s, dim3(grid_for(d, WGS_GU_WG_PER_CU)), epoch, part != 0, d->two_way, d->shard_fused ? 1u : 0u);
         mark(5);
+        // ---- "g2p" + "particles_update", fused (mark 6: between the two launches of a collider simulation's G2P)
+        const G2pLaunch g2p = plan_g2p(d);
+        if (dev.nv > 0) launch_g2p<D>(dev, s, side, epoch, d->plastic, g2p, mark);
+        if (!(dev.nv > 0 && g2p.shape == G2pShape::two_launches)) mark(6);
         // sharded step: the particles that arrived with this substep's messages are advanced too (kernels_arrivals.h), by a
         // launch of their own behind the fused G2P. (As extra workgroups INSIDE that launch — first or last in its grid — they
         // made it 7-10 us longer at a 1 M slab for the 5 us launch they saved: measured twice in round 3, not kept.)
-        const bool arrivals = part == 2 && d->in_sharded_step && d->link && d->link->attached;
-        const uint32_t arr_most = arrivals ? ((d->link->has_lower ? 1u : 0u) + (d->link->has_upper ? 1u : 0u)) * d->link->mig_cap : 0u;
-        if (dev.nv > 0) {
-            // ---- "g2p" + "particles_update", fused
-            // one single-wave workgroup per `npass` chunks of 64 sorted particles; multiple of 8: XCD-aware mapping
-            const uint32_t npass = dev.g2p_npass;
-            const int g = (int)(((dev.nv + G2P_THREADS * npass - 1) / (G2P_THREADS * npass) + 7) / 8) * 8;
-#ifndef WGS_PLASTIC_WPE_DENSE
-#define WGS_PLASTIC_WPE_DENSE 2
-#endif
-#ifndef WGS_PLASTIC_WPE
-#define WGS_PLASTIC_WPE G2P_WAVES_PER_EU
-#endif
-            // (the decomposition is a template parameter of the fused G2P: kernels_transfer.h; a slab always takes the paired /
-            // single-body launch shapes, the two-launch debug shape exists for single-domain data only)
-#define WGS_LAUNCH_G2P(MODEL, PL, CM, NP, SH)                                                                          \
-    hipLaunchKernelGGL((k_g2p_update<D, MODEL, PL, CM, NP, SH, !(PL)>), (CM) == 2 ? dim3(8 * (grid_for(d, 1) * 3 / 2)) : dim3(g), \
-                       dim3(G2P_THREADS), 0, s, dev, side, epoch)
-#define WGS_LAUNCH_G2P_PAIR(MODEL, PL, WPE, NP, SH)                                                                        \
-    hipLaunchKernelGGL((k_g2p_pair<D, MODEL, PL, WPE, NP, SH, !(PL)>), dim3((uint32_t)g + 8u * nlist), dim3(G2P_THREADS), 0, s, \
-                       dev, side, epoch, (uint32_t)g, nlist)
-#define WGS_LAUNCH_G2P_NP(MODEL, PL, NP)    \
-    do {                                    \
-        if (d->cpic && (shard || !(dev.dbg & 4096u))) {                                                    \
-            /* both bodies in one launch (k_g2p_pair) */                                                          \
-            /* list waves (8 x nlist; the waves of an XCD stride over the runs of its visit list): 2 x the runs of the */ \
-            /* longest list as the host last saw it */                                                             \
-            /* (unknown: a wave and a half per SIMD) */                                                           \
-            const uint32_t full = (uint32_t)grid_for(d, 1) * 3u / 2u;                                             \
-            const uint32_t nlist = d->last_nvisit == UINT32_MAX ? full : std::min(full, std::max(8u, 2u * ((d->last_nvisit + std::min<uint32_t>(NP, WGS_G2P_LIST_PASSES) - 1u) / std::min<uint32_t>(NP, WGS_G2P_LIST_PASSES)))); \
-            /* plastic scenes with a large share of listed blocks: the spill-free variant (kernels_transfer.h) */  \
-            const bool dense = PL && d->last_ncpic != UINT32_MAX && d->last_ncpic * 2u >= std::max(1u, d->last_nblocks) && !(dev.dbg & 16384u); \
-            if (dense && shard) WGS_LAUNCH_G2P_PAIR(MODEL, PL, (PL) ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU, NP, true);      \
-            else if (dense) WGS_LAUNCH_G2P_PAIR(MODEL, PL, (PL) ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU, NP, false);         \
-            else if (shard) WGS_LAUNCH_G2P_PAIR(MODEL, PL, (PL) ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, NP, true);                 \
-            else WGS_LAUNCH_G2P_PAIR(MODEL, PL, (PL) ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, NP, false);                           \
-            mark(6);                                                                                              \
-        } else if (d->cpic) {               \
-            WGS_LAUNCH_G2P(MODEL, PL, 1, NP, false);   \
-            mark(6);                        \
-            WGS_LAUNCH_G2P(MODEL, PL, 2, 1, false);    \
-        } else if (shard) {                 \
-            WGS_LAUNCH_G2P(MODEL, PL, 0, NP, true);    \
-        } else {                            \
-            WGS_LAUNCH_G2P(MODEL, PL, 0, NP, false);   \
-        }                                   \
-    } while (0)
-#define WGS_LAUNCH_G2P_MP(MODEL, PL)                    \
-    do {                                                \
-        if (npass == (uint32_t)G2P_MANY_PASSES) WGS_LAUNCH_G2P_NP(MODEL, PL, G2P_MANY_PASSES); \
-        else if (npass == 2u) WGS_LAUNCH_G2P_NP(MODEL, PL, 2); \
-        else WGS_LAUNCH_G2P_NP(MODEL, PL, 1);           \
-    } while (0)
-            const bool shard = dev.sharded != 0u;
-            const int sel = (dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (d->plastic ? 1 : 0);
-            switch (sel) {
-                case 0: WGS_LAUNCH_G2P_MP(0, false); break;
-                case 1: WGS_LAUNCH_G2P_MP(0, true); break;
-                case 2: WGS_LAUNCH_G2P_MP(1, false); break;
-                default: WGS_LAUNCH_G2P_MP(1, true); break;
-            }
-#undef WGS_LAUNCH_G2P_MP
-#undef WGS_LAUNCH_G2P_NP
-#undef WGS_LAUNCH_G2P_PAIR
-#undef WGS_LAUNCH_G2P
-        }
-        if (!(d->cpic && dev.nv > 0)) mark(6);  // (collider simulations: recorded between the two G2P launches)
         // (the arrivals' body also does the bookkeeping of the migration round, so it runs even when nobody can arrive)
+        const bool arrivals = part == 2 && d->in_sharded_step && d->link && d->link->attached;
         if (arrivals) {
-            const dim3 ag(std::max(1u, std::min((arr_most + ARR_PER_WG - 1u) / ARR_PER_WG, 1024u)));
-            const int asel = (dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (d->plastic ? 1 : 0);
-            switch (asel) {
-                case 0: hipLaunchKernelGGL((k_g2p_arrivals<D, 0, false>), ag, dim3(256), 0, s, dev, side, epoch); break;
-                case 1: hipLaunchKernelGGL((k_g2p_arrivals<D, 0, true>), ag, dim3(256), 0, s, dev, side, epoch); break;
-                case 2: hipLaunchKernelGGL((k_g2p_arrivals<D, 1, false>), ag, dim3(256), 0, s, dev, side, epoch); break;
-                default: hipLaunchKernelGGL((k_g2p_arrivals<D, 1, true>), ag, dim3(256), 0, s, dev, side, epoch); break;
-            }
+            const uint32_t arr_most = ((d->link->has_lower ? 1u : 0u) + (d->link->has_upper ? 1u : 0u)) * d->link->mig_cap;
+            launch_arrivals<D>(dev, s, dim3(std::max(1u, std::min((arr_most + ARR_PER_WG - 1u) / ARR_PER_WG, 1024u))), side, epoch, d->plastic);
         }
         mark(7);
         // ---- "integrate_bodies" (rigid_impulses.wgsl:95-136) + the world mass properties of the next substep
@@ -1049,7 +1127,7 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
             // Single-domain simulations without mesh colliders: left to the first launch of the next substep (or to the end of
             // this wgs_step call, flush_bodies) — a 16-thread launch of its own costs a dependent launch, ~5 us, per substep.
             // (not when this substep's G2P binned for the next one: that substep has no launch in front of the node cdfs of its sort)
-            if (part == 0 && !dev.sharded && dev.n_rigid == 0 && n > 0 && !(dev.dbg & 524288u) && !dev.bin_next) d->bodies_pending = true;
+            if (part == 0 && !dev.sharded && dev.n_rigid == 0 && n > 0 && !(dev.dbg & DBG_BODIES_OWN_LAUNCH) && !dev.bin_next) d->bodies_pending = true;
             else hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, s, dev);
         }
         mark(8);
@@ -1158,25 +1236,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
         dev.h_pow2 = (frexpf(cell_width, &e) == 0.5f) ? 1u : 0u;
     }
     dev.model = WGS_MODEL_COROTATED;
-    // Developer switches (read once, here; 0 in production): A/B of launch shapes, SAME results — 128 = full k_bin on
-    // every substep (no k_rebin), 1024 = no eviction of long-inactive blocks from the table (it is rebuilt when the ids run out instead),
-    // 2048 = launch 2 of the sort never shares node-cdf summaries between neighbouring blocks (every wave evaluates its whole tile),
-    // 2 = ... shares them but never waits for one (a neighbour's word that is not there at the first look is evaluated locally),
-    // 4 = the particle cdf of the listed blocks always inside their CPIC workgroups of P2G (no prologue waves), 8 = prologue waves sized for an
-    // empty list whatever the host saw (the launch then finds the lists too long for them and leaves the work to the workgroups),
-    // 4096 = the two G2P bodies as two launches, 8192 = the two P2G bodies always as two launches, 16384 = never the
-    // spill-free variant of the plastic G2P pair, 32768 = never the small register budget of the one-way P2G pair,
-    // 65536 = never the uniform-material mode (the per-particle constants always travel with the particle), 131072 = the
-    // fused G2P always with two chunks per wave (the large-scene launch shape), 262144 = the grid update as a launch of its
-    // own also where it could ride in the P2G launch, 524288 = integrate_bodies as a launch of its own at the tail of every substep,
-    // 1048576 = launch 1 of the sort (k_rebin) every substep instead of the binning inside the fused G2P, 4194304 = P2G of a
-    // lockstep slab split into its boundary layers and the rest (the shape wgs_sharded_step uses when it forks), 8388608 =
-    // wgs_sharded_step forks the exchange onto a second stream beside the interior's P2G (measured slower here: capi_sharded.inc),
-    // 16777216 = launch 2 of the sort orders the cells of a dirty block by insertion instead of by ranks (kernels_sort.h),
-    // 33554432 = P2G gathers every block through the sort permutation (no direct runs for unchanged blocks: layout.h CELL_DIRECT),
-    // 67108864 = large two-way simulations run the plain P2G launch in front of the near-collider one (round 5's order).
-    // The ablations that change the RESULTS (64 = G2P moves bytes only, 256 = P2G without its accumulation loop,
-    // 512 = P2G without its particle loads) exist only in builds with -DWGS_ABLATE; the shipped library ignores them.
+    // developer switches (layout.h DebugSwitch), read once, here; 0 in production
     dev.dbg = getenv("WGS_DEBUG") ? (uint32_t)strtoul(getenv("WGS_DEBUG"), nullptr, 0) : 0u;
     if (getenv("WGS_REHASH_PERIOD")) d->rehash_period = std::max(1u, (uint32_t)strtoul(getenv("WGS_REHASH_PERIOD"), nullptr, 0));  // same results
 #ifndef WGS_ABLATE
@@ -1280,7 +1340,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
     d->plastic = plastic || force_plastic != 0;
     // uniform plasticity parameters (bitwise; single-domain data, like the automatic uniform-material mode; layout.h Dev::uni_dp):
     // 1 = one set of h0..h3, 2 = all six and max_stretch — the per-particle state is then packed into DP1 before the upload
-    if (d->plastic && n > 0 && !sharded && !(dev.dbg & 65536u)) {
+    if (d->plastic && n > 0 && !sharded && !(dev.dbg & DBG_NO_UNIFORM)) {
         bool u4 = true, u6 = true;
         for (uint32_t i = 1; i < n && u4; i++) {
             u4 = memcmp(&s_dp[(size_t)i * 6], &s_dp[0], 4 * sizeof(float)) == 0;
@@ -1300,7 +1360,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
     }
     // one material for all particles (bitwise)? -> uniform-material mode (layout.h). Sharded data: the caller says so
     // (wgs_set_uniform_material), a rank cannot know the other ranks' particles.
-    bool uniform = D == 3 && n > 0 && !sharded && !(dev.dbg & 65536u);
+    bool uniform = D == 3 && n > 0 && !sharded && !(dev.dbg & DBG_NO_UNIFORM);
     for (uint32_t i = 1; i < n && uniform; i++)
         uniform = memcmp(&particles[i].dynamics.mass, &particles[0].dynamics.mass, 4) == 0 &&
                   memcmp(&particles[i].dynamics.init_volume, &particles[0].dynamics.init_volume, 4) == 0 &&
@@ -1412,12 +1472,6 @@ wgs_status wgs_shard_export(wgs_data *d, void *device_buf, uint32_t capacity_rec
 void wgs_data_destroy(wgs_data *d) {
     if (!d) return;
     if (d->stream) hipStreamSynchronize(d->stream);
-    if (d->stream2) {
-        hipStreamSynchronize(d->stream2);
-        hipStreamDestroy(d->stream2);
-        if (d->ev_sorted) hipEventDestroy(d->ev_sorted);
-        if (d->ev_exchanged) hipEventDestroy(d->ev_exchanged);
-    }
     if (d->events.created)
         for (int s = 0; s < Events::MAX_SUBSTEPS; s++)
             for (int m = 0; m < Events::MARKS; m++) hipEventDestroy(d->events.ev[s][m]);

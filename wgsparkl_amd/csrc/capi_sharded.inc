@@ -106,34 +106,22 @@ wgs_status allreduce_impulses(wgs_data *d) {
     return WGS_OK;
 }
 
-wgs_status rccl_exchange(wgs_data *d, hipStream_t s);
-
-// The exchange off the critical path (SURVEY 5: "boundary blocks first"; measured, not the default: see wgs_sharded_step): after
-// the sort the substep forks. The data's second stream runs P2G of the two block layers at each cut — the only slabs the outgoing messages are gathered
-// from —, the pack waves behind it, and the one grouped send / receive per neighbour; the data's own stream runs P2G of every
-// other block with the interior's grid update behind it meanwhile, and waits for the messages only in front of the interface
-// layers' grid update. Same kernels, same sums in the same order as the unsplit form: bit-identical (tested on lockstep slabs,
-// WGS_DEBUG = 4194304 splits there too).
-wgs_status shard_phase_begin_overlapped(wgs_data *d, bool exchange) {
+// The split form of phase A (DBG_SHARD_SPLIT_LAYERS): the sort, then P2G of the two block layers at each cut —
+// the only slabs the outgoing messages are gathered from — with the pack waves behind it, then P2G of every other block with
+// the interior's grid update behind it. Same kernels, same sums in the same order as the unsplit form: bit-identical (tested).
+wgs_status shard_phase_begin_split(wgs_data *d) {
     d->in_sharded_step = true;
     wgs_status st = enqueue_substep<false>(d, 0, 1, 1);                    // the sort
-    if (st == WGS_OK && d->stream2) {
-        if (hipEventRecord(d->ev_sorted, d->stream) != hipSuccess || hipStreamWaitEvent(d->stream2, d->ev_sorted, 0) != hipSuccess)
-            st = fail(WGS_ERR_HIP, "hipEventRecord / hipStreamWaitEvent (sharded step fork)");
-    }
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 2);            // boundary layers + pack waves (second stream)
-    if (st == WGS_OK && exchange) st = rccl_exchange(d, d->stream2 ? d->stream2 : d->stream);
-    if (st == WGS_OK && d->stream2 && hipEventRecord(d->ev_exchanged, d->stream2) != hipSuccess) st = fail(WGS_ERR_HIP, "hipEventRecord (sharded step join)");
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 3);            // everything else + the interior's grid update (own stream)
-    if (st == WGS_OK && d->stream2 && hipStreamWaitEvent(d->stream, d->ev_exchanged, 0) != hipSuccess) st = fail(WGS_ERR_HIP, "hipStreamWaitEvent (sharded step join)");
+    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 2);            // boundary layers + pack waves
+    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 3);            // everything else + the interior's grid update
     d->in_sharded_step = false;
     return st;
 }
 
 // phase A: sort .. P2G, then the interface node sums and the guests packed into the outgoing messages
 wgs_status shard_phase_begin(wgs_pipeline *p, wgs_data *d) {
-    if ((d->dev.dbg & 4194304u) && d->link && (d->link->has_lower || d->link->has_upper) && !(d->dev.dbg & 262144u))
-        return shard_phase_begin_overlapped(d, false);   // (the split form on one stream, the caller moves the messages: a test shape)
+    if ((d->dev.dbg & DBG_SHARD_SPLIT_LAYERS) && d->link && (d->link->has_lower || d->link->has_upper) && !(d->dev.dbg & DBG_GU_OWN_LAUNCH))
+        return shard_phase_begin_split(d);
     d->in_sharded_step = true;
     wgs_status st = enqueue_substep<false>(d, 0, 1);
     d->in_sharded_step = false;
@@ -141,11 +129,8 @@ wgs_status shard_phase_begin(wgs_pipeline *p, wgs_data *d) {
     ShardLink &L = *d->link;
     if (!L.has_lower && !L.has_upper) return WGS_OK;
     if (d->shard_fused) return WGS_OK;   // the pack waves rode in the P2G launch (capi.hip)
-    // one wave per interface block (as the host last saw the grid: a face holds a fraction of the active blocks), plus a
-    // few workgroups for the guests
-    const uint32_t nblk = std::max(64u, std::min(2048u, d->seen_nblocks ? d->seen_nblocks : 2048u));
-    const uint32_t nmig = std::max(1u, std::min(64u, (2u * L.mig_cap + 63u) / 64u));
-    hipLaunchKernelGGL(k_pack_face<D>, dim3(nblk + nmig), dim3(64), 0, d->stream, d->dev, d->side, (uint32_t)(d->substeps + 1), nblk);
+    const PackWaves pw = pack_waves(d);   // (workgroups of one wave)
+    hipLaunchKernelGGL(k_pack_face<D>, dim3(pw.blocks + pw.guests), dim3(64), 0, d->stream, d->dev, d->side, (uint32_t)(d->substeps + 1), pw.blocks);
     HIP_TRY(hipGetLastError());
     return WGS_OK;
 }
@@ -161,7 +146,8 @@ wgs_status shard_phase_end(wgs_pipeline *p, wgs_data *d) {
 
 // one grouped send + receive per neighbour on the data's stream (the two neighbours are distinct peers: each message
 // rides its own xGMI link; a rank that is its own neighbour — the one-GPU proxy — matches its sends in order)
-wgs_status rccl_exchange(wgs_data *d, hipStream_t s) {
+wgs_status rccl_exchange(wgs_data *d) {
+    const hipStream_t s = d->stream;
     ShardLink &L = *d->link;
     Rccl *r = rccl();
     if (!L.has_lower && !L.has_upper) return WGS_OK;
@@ -281,36 +267,16 @@ wgs_status wgs_sharded_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_su
     // body impulses are reduced over ALL ranks (also those without particles near the body) before integrate_bodies
     d->reduce_impulses = (d->two_way && L.comm && L.comm->world > 1) ? 1 : 0;
     if ((st = maintain_grid(d)) != WGS_OK) return st;
-    // The exchange beside the interior's P2G (shard_phase_begin_overlapped) is OFF unless WGS_DEBUG bit 23 asks for it: on this
-    // stack (ROCm 7.0 / 7.2, MI355X) every cross-stream dependency costs 15-20 us, more than the 14-16 us RCCL kernel it hides —
-    // one rank as its own two neighbours, 1 M slab: 139-145 us serial, 168-175 us forked (and 520 us when the second stream is
-    // created with a raised priority: every kernel of BOTH queues then takes several times its time). Same results either way.
-    const bool overlap = neighbours && (d->dev.dbg & 8388608u) && !(d->dev.dbg & 262144u);
-    if (overlap && !d->stream2) {
-        // (created into locals and committed together: a failure half way must not leave a stream without its events)
-        hipStream_t s2 = nullptr;
-        hipEvent_t e1 = nullptr, e2 = nullptr;
-        hipError_t fe = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-        if (fe == hipSuccess) fe = hipEventCreateWithFlags(&e1, hipEventDisableTiming | hipEventDisableSystemFence);   // (device-side ordering only: no cache write-back to the host per record)
-        if (fe == hipSuccess) fe = hipEventCreateWithFlags(&e2, hipEventDisableTiming | hipEventDisableSystemFence);
-        if (fe != hipSuccess) {
-            if (e2) hipEventDestroy(e2);
-            if (e1) hipEventDestroy(e1);
-            if (s2) hipStreamDestroy(s2);
-            return fail(WGS_ERR_HIP, std::string("wgs_sharded_step: second stream / events: ") + hipGetErrorString(fe));
-        }
-        d->stream2 = s2;
-        d->ev_sorted = e1;
-        d->ev_exchanged = e2;
-    }
+    // The exchange is not overlapped with the interior's P2G. Forking it onto a second stream (the boundary layers' P2G, the pack
+    // waves and the send / receive there, the rest of P2G on the data's stream) was measured slower on ROCm 7.0 / 7.2, MI355X:
+    // every cross-stream dependency cost 15-20 us, more than the 14-16 us RCCL kernel it hid — one rank as its own two
+    // neighbours, 1 M slab: 139-145 us serial, 168-175 us forked (520 us with the second stream at a raised priority: every
+    // kernel of BOTH queues then took several times its time). The fork was removed; the split of P2G it used remains
+    // (shard_phase_begin_split).
     for (uint32_t i = 0; i < num_substeps; i++) {
         if (i > 0 && i % 64u == 0u && ((st = watch_counters(d)) != WGS_OK || (st = maintain_grid(d)) != WGS_OK)) return st;
-        if (neighbours && overlap) {
-            if ((st = shard_phase_begin_overlapped(d, true)) != WGS_OK) return st;
-        } else {
-            if ((st = shard_phase_begin(pipeline, d)) != WGS_OK) return st;
-            if (neighbours && (st = rccl_exchange(d, d->stream)) != WGS_OK) return st;
-        }
+        if ((st = shard_phase_begin(pipeline, d)) != WGS_OK) return st;
+        if (neighbours && (st = rccl_exchange(d)) != WGS_OK) return st;
         if ((st = shard_phase_end(pipeline, d)) != WGS_OK) return st;
     }
     return watch_counters(d);

@@ -225,7 +225,7 @@
         }
 
 #ifdef WGS_ABLATE
-        if (d.dbg & 64u) {  // ablation: memory traffic of the kernel without tile staging / maths
+        if (d.dbg & DBG_ABLATE_G2P_BYTES_ONLY) {  // ablation: memory traffic of the kernel without tile staging / maths
             if (valid) {
                 if constexpr (D == 3) {
                     stq(out, npad, P::XM, j, make_float4(x[0], x[1], x[2], mass));

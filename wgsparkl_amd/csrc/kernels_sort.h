@@ -677,7 +677,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             pc_flag = any ? CELL_LISTED : 0u;
         } else if (own_cached) {
             // (nothing to do: its nodes are what they were, it holds no particle)
-        } else if (CDF WGS_ABLATE_AND(!(d.dbg & (1u << 21)))) {
+        } else if (CDF WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_NO_BLOCK_CDF))) {
             constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE;
             uint32_t mine = 0u;
             const uint32_t near = reach_mask(0xffffu);  // bit i: collider i can reach a node of this tile
@@ -742,7 +742,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             publish_summ(cdf_summ & 0xffu);   // (its nodes are what they were)
         } else if (own_cached) {
             publish_summ(cdf_summ & 0xffu);   // (nothing else to do: its nodes are what they were, it holds no particle)
-        } else if (CDF WGS_ABLATE_AND(!(d.dbg & (1u << 21)))) {
+        } else if (CDF WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_NO_BLOCK_CDF))) {
             constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE;
             constexpr int ROUNDS = (TILE + 63) / 64;
             const uint32_t near = reach_mask(0xffffu);  // bit i: collider i can reach a node of this tile
@@ -780,7 +780,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
                                 const bool have = nb != NONE && (w >> 8) == (epoch & SUMM_TAG);
                                 any = __ballot(have && ((w >> lane) & 1u) != 0u) != 0ull;
                                 parts = (uint32_t)__ballot(nb != NONE && !have);
-                                if (any || parts == 0u || (d.dbg & 2u) || wall_clock64() - t_start > 400ull) break;   // (100 MHz: 4 us; WGS_DEBUG bit 1: no wait at all — tests)
+                                if (any || parts == 0u || (d.dbg & DBG_CDF_SUMM_NO_WAIT) || wall_clock64() - t_start > 400ull) break;   // (100 MHz: 4 us; the switch: no wait at all — tests)
                                 __builtin_amdgcn_s_sleep(8);
                             }
                             if (any) parts = 0u;
@@ -982,7 +982,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
                 pv = v;
             }
         }
-        const bool quick = ordered && !(d.dbg & 16777216u);   // (WGS_DEBUG bit 24: the insertion sort below for every cell — same order, tested)
+        const bool quick = ordered && !(d.dbg & DBG_CELL_INSERTION_SORT);   // (the switch: the insertion sort below for every cell — same order, tested)
         // (batches of NEWC newcomers: the members merged so far are the sorted prefix of the next batch)
         for (uint32_t base = par_nst; quick && base < total; base += (uint32_t)NEWC) {
             const uint32_t par_nst = base, n_new = min((uint32_t)NEWC, total - base);   // (this batch: `par_nst` sorted members, `n_new` newcomers)
@@ -1209,8 +1209,8 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     d.cell_cursor[idx] = bstart + lstart + total;
     // (the same, where P2G finds it without the block id — or, for a run that is the block's previous run member for member, where the
     // particles ARE: [cs_old, ce_old) of the buffer, which P2G then reads without the gather through perm: layout.h CELL_DIRECT.
-    // WGS_DEBUG bit 25: never — same particles in the same order either way, tested)
-    const bool direct = fast_clean && !(d.dbg & 33554432u);
+    // DBG_NO_DIRECT_RUNS: never — same particles in the same order either way, tested)
+    const bool direct = fast_clean && !(d.dbg & DBG_NO_DIRECT_RUNS);
     d.act_cells[(size_t)aidx * NPB + lane] = direct ? make_uint2(cs_old, ce_old) : make_uint2(bstart + lstart, bstart + lstart + total);
     if (head != 0u) d.cell_head[idx] = 0u;
     if (lane == 0 && narr != 0u) d.blk_narr[id] = 0u;

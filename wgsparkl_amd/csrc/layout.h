@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #ifndef WGS_DIM
 #define WGS_DIM 3
 #endif
@@ -191,7 +193,7 @@ struct Dev {
     uint32_t cap;        // block capacity
     // per physical block id (ids persist while the block stays in the hash map)
     uint32_t *block_key;   // cap: packed virtual id (NONE: the id is on the free list — the block was evicted)
-    uint32_t *block_slot;  // cap: the table slot that holds the block's key (what an eviction marks); null: no eviction on this data (WGS_DEBUG bit 10)
+    uint32_t *block_slot;  // cap: the table slot that holds the block's key (what an eviction marks); null: no eviction on this data (DBG_NO_EVICTION)
     uint32_t *free_ids;    // cap: ids of evicted blocks, a stack of counters[CTR_NFREE] entries (pushed by launch 2 of the sort, popped by insertions)
     uint32_t *block_stamp; // cap: epoch of the last substep in which the block was active
     uint32_t *links_epoch; // cap: epoch at which nbr_plus / nbr_minus of the block were last written
@@ -290,9 +292,56 @@ struct Dev {
     uint32_t uni_dp;
     float uni_dpv[6], uni_max_stretch;
     int model;           // WGS_MODEL_*
-    uint32_t dbg;        // launch-shape A/B switches (env WGS_DEBUG; same results, see capi.hip), 0 in production. The
-                         // result-changing ablations only exist in builds with -DWGS_ABLATE (never the shipped library)
+    uint32_t dbg;        // developer switches DBG_* below (env WGS_DEBUG, read once at creation), 0 in production
 };
+
+// WGS_DEBUG: developer switches, one bit each. A launch-shape switch brings back an alternative launch shape that must give
+// the SAME results; the test named beside it uses it as the reference (tests/test_gpu_*.py). The bit values are stable.
+enum DebugSwitch : uint32_t {
+    DBG_CDF_SUMM_NO_WAIT = 1u << 1,         // sort launch 2 shares node-cdf summaries but never waits for one (bit_identity: node_cdf_summaries)
+    DBG_NO_PCDF_WAVES = 1u << 2,            // particle cdf of listed blocks always in their CPIC workgroups (bit_identity: prologue_waves)
+    DBG_PCDF_WAVES_UNSIZED = 1u << 3,       // prologue waves sized for an empty list, the launch decides (bit_identity: prologue_waves)
+    DBG_ABLATE_G2P_BYTES_ONLY = 1u << 6,    // ablation only (-DWGS_ABLATE): G2P moves its bytes without tile staging or maths
+    DBG_NO_REBIN = 1u << 7,                 // full k_bin every substep, no k_rebin (bit_identity: steady_state_rebinning)
+    DBG_ABLATE_P2G_NO_ACCUM = 1u << 8,      // ablation only (-DWGS_ABLATE): P2G without its accumulation loop
+    DBG_ABLATE_P2G_NO_LOADS = 1u << 9,      // ablation only (-DWGS_ABLATE): P2G without its particle loads
+    DBG_NO_EVICTION = 1u << 10,             // no eviction of long-inactive blocks, the table is rebuilt instead (bit_identity: evicts_blocks)
+    DBG_NO_CDF_SUMM = 1u << 11,             // sort launch 2 evaluates every block's whole tile (bit_identity: node_cdf_summaries)
+    DBG_G2P_TWO_LAUNCHES = 1u << 12,        // the two G2P bodies as two launches (parity: long_near_collider_list_paths)
+    DBG_P2G_TWO_LAUNCHES = 1u << 13,        // the two P2G bodies always as two launches (parity: long_near_collider_list_paths; bit_identity)
+    DBG_NO_G2P_DENSE = 1u << 14,            // never the spill-free plastic G2P pair (bit_identity: plastic_pair_register_budgets)
+    DBG_NO_P2G_SMALL_BUDGET = 1u << 15,     // never the small register budget of the one-way P2G pair (bit_identity: large_one_way_scenes)
+    DBG_NO_UNIFORM = 1u << 16,              // never the uniform-material modes (bit_identity: uniform_*; constitutive)
+    DBG_G2P_TWO_PASSES = 1u << 17,          // fused G2P always with two chunks per wave (bit_identity: g2p_launch_shapes; parity; constitutive)
+    DBG_GU_OWN_LAUNCH = 1u << 18,           // grid update as a launch of its own, k_pack_face on slabs (bit_identity: grid_update_inside; sharded)
+    DBG_BODIES_OWN_LAUNCH = 1u << 19,       // integrate_bodies as a launch of its own every substep (bit_identity: grid_update_inside)
+    DBG_REBIN_LAUNCH = 1u << 20,            // k_rebin every substep, no binning inside the fused G2P (bit_identity: binning_inside; sharded)
+    DBG_ABLATE_NO_BLOCK_CDF = 1u << 21,     // ablation only (-DWGS_ABLATE): sort launch 2 skips the node cdfs of a block's tile
+    DBG_SHARD_SPLIT_LAYERS = 1u << 22,      // P2G of a lockstep slab split into boundary layers and the rest (sharded: pack_and_interior)
+    DBG_CELL_INSERTION_SORT = 1u << 24,     // sort launch 2 orders a dirty block's cells by insertion, not ranks (bit_identity: binning_inside)
+    DBG_NO_DIRECT_RUNS = 1u << 25,          // P2G gathers every block through the permutation (bit_identity: direct_runs)
+    DBG_PLAIN_P2G_FIRST = 1u << 26,         // large two-way scenes: plain P2G launch before the near-collider one (bit_identity: near_collider_launch_first)
+};
+
+// the OR of `bits`, or 0 if one of them is not a single bit or repeats one before it
+constexpr uint32_t or_of_distinct_bits(std::initializer_list<uint32_t> bits) {
+    uint32_t all = 0u;
+    for (const uint32_t b : bits) {
+        if (b == 0u || (b & (b - 1u)) != 0u || (all & b) != 0u) return 0u;
+        all |= b;
+    }
+    return all;
+}
+// the switches the shipped library honours; the others change results and exist only in builds with -DWGS_ABLATE
+constexpr uint32_t WGS_LAUNCH_SHAPE_SWITCHES = or_of_distinct_bits({
+    DBG_CDF_SUMM_NO_WAIT, DBG_NO_PCDF_WAVES, DBG_PCDF_WAVES_UNSIZED, DBG_NO_REBIN, DBG_NO_EVICTION, DBG_NO_CDF_SUMM,
+    DBG_G2P_TWO_LAUNCHES, DBG_P2G_TWO_LAUNCHES, DBG_NO_G2P_DENSE, DBG_NO_P2G_SMALL_BUDGET, DBG_NO_UNIFORM, DBG_G2P_TWO_PASSES,
+    DBG_GU_OWN_LAUNCH, DBG_BODIES_OWN_LAUNCH, DBG_REBIN_LAUNCH, DBG_SHARD_SPLIT_LAYERS, DBG_CELL_INSERTION_SORT,
+    DBG_NO_DIRECT_RUNS, DBG_PLAIN_P2G_FIRST});
+constexpr uint32_t WGS_ABLATION_SWITCHES = or_of_distinct_bits({
+    DBG_ABLATE_G2P_BYTES_ONLY, DBG_ABLATE_P2G_NO_ACCUM, DBG_ABLATE_P2G_NO_LOADS, DBG_ABLATE_NO_BLOCK_CDF});
+static_assert(WGS_LAUNCH_SHAPE_SWITCHES != 0u && WGS_ABLATION_SWITCHES != 0u && (WGS_LAUNCH_SHAPE_SWITCHES & WGS_ABLATION_SWITCHES) == 0u,
+              "WGS_DEBUG switches must be distinct single bits");
 
 // Sharded runs keep TWO sets of the three particle counters (CTR_N, CTR_NV, CTR_NPREV; the second set CTR_SET slots
 // further): the kernels of substep n read set n & 1 (Dev::ctr_set), and the bookkeeping of the migration round — done by

@@ -204,7 +204,7 @@
                 if (sl < SLOTS) {
                     const int c = sl / P2G_J;
                     const uint32_t rank = r0 + (uint32_t)(sl % P2G_J);
-                    if (rank < s_cn[c] WGS_ABLATE_AND(!(d.dbg & 512u))) {
+                    if (rank < s_cn[c] WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_P2G_NO_LOADS))) {
                         const uint32_t src = direct ? s_cs[c] + rank : d.perm[s_cs[c] + rank];
                         pre_ok[k] = true;
                         if constexpr (D == 3) {
@@ -257,7 +257,7 @@
             __syncthreads();
             if (r0 == 0) { P2G_PROF(3) }
             if (r0 + P2G_J < maxc) fetch_round(r0 + P2G_J);  // in flight during the accumulation below
-            const uint32_t jn = (cn > r0 WGS_ABLATE_AND(!(d.dbg & 256u))) ? min((uint32_t)P2G_J, cn - r0) : 0u;
+            const uint32_t jn = (cn > r0 WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_P2G_NO_ACCUM))) ? min((uint32_t)P2G_J, cn - r0) : 0u;
             for (uint32_t j = 0; j < jn; j++) {
                 const int sl = j * ROW + cell;
                 float x[D], mv[D], c[D * D], mass;
