@@ -190,8 +190,9 @@ const char *wgs_build_info(void);
 /* Version of this header's structs and entry points as the LIBRARY was built (WGS_ABI_VERSION as the caller was): the structs carry no
  * size field — wgs_get_stats writes sizeof(wgs_stats) of ITS header —, so a binding checks wgs_abi_version() == WGS_ABI_VERSION once,
  * after loading the library, and refuses to go on otherwise (include/wgsparkl_hip.hpp and wgsparkl_amd/_ffi.py do). History: 5 =
- * wgs_stats grew by block_ids .. table_refreshes (24 bytes); 6 = this function. New counters will come behind a call of their own. */
-#define WGS_ABI_VERSION 6
+ * wgs_stats grew by block_ids .. table_refreshes (24 bytes); 6 = this function. New counters will come behind a call of their own.
+ * 7 = wgs_read_diagnostics / wgs_enqueue_diagnostics and their structs (nothing that existed changed). */
+#define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
 /* MpmPipeline::new(&Device) -> Result<Self, ComposerError>  (src/pipeline.rs:176-193).
@@ -396,6 +397,99 @@ wgs_status wgs_sharded_step(wgs_pipeline *pipeline, wgs_data *data, uint32_t num
  * comm == NULL), device-to-device copies as the transport: decomposition tests on a single GPU. For the duration of
  * the call the group's work is ordered on slab 0's stream; afterwards every slab's own stream waits for it. */
 wgs_status wgs_sharded_step_lockstep(wgs_pipeline *pipeline, wgs_data **slabs, uint32_t num_slabs, uint32_t num_substeps);
+
+/* ---------------------------------------------------------------------------------------------
+ * Device-side diagnostics. NEW: the reference has no counterpart (its host can only map `positions`,
+ * src/solver/particle3d.rs:197-201; nothing in src/pipeline.rs:195-281 reduces anything). Conserved sums, bounds and a state digest of
+ * the state after the last enqueued substep, reduced on the device: no particle crosses PCIe. Per-particle values are the canonical ones
+ * wgs_read_particles returns (the uniform-material / uniform-plasticity layouts are undone first). Everything is ORDER-INDEPENDENT by
+ * construction — storage order, launch shapes, the side of the ping-pong, rebuilds, evictions and restarts do not change one bit of the
+ * result — because nothing on the way is a floating-point addition: sums are 64-bit INTEGER sums of fixed-point terms, bounds are integer
+ * maxima / minima of ordered bit patterns, the digest is a sum modulo 2^64.
+ *
+ * what = OR of WGS_DIAG_*:
+ *   PARTICLES  counts, bounds, and every particle sum but WGS_SUM_ELASTIC (a pure streaming pass, twice);
+ *   ENERGY     adds WGS_SUM_ELASTIC (a symmetric eigenvalue problem per particle, in fp64); implies PARTICLES;
+ *   GRID       the three grid sums, over the nodes of the blocks active in the last substep, as wgs_read_grid reports them
+ *              (velocity after the grid update, mass; x_i = cell * h); all zero before the first substep;
+ *   DIGEST     digest[2] (and the counts).
+ * Fields that were not asked for are zero; `what` echoes the bits that were computed, `model` the constitutive model.
+ *
+ * Particles. Slots whose particle now lives on a neighbouring rank (sharded data) are skipped. A particle with a non-finite position,
+ * velocity, affine matrix, deformation gradient, mass, init_volume, lambda or mu is counted in num_nonfinite and left out of every sum
+ * and bound (it is still in num_particles and in the digest).
+ *
+ * Terms (fp64, from the fp32 state; a product of two fp32 values is exact there). m = mass, x = position, v = velocity, F = def_grad,
+ * A = `affine` AS STORED, V0 = init_volume, h = cell width, g = gravity, D = h^2/4 (inv_d = 4/h^2, src/grid/kernel.wgsl). NOTE on A: the
+ * particle update stores A = m * grad v - tau * V0 * inv_d * dt (src/solver/particle_update.wgsl:129-132), and P2G transfers
+ * w * (A * (x_i - x) + m v) (src/solver/p2g.wgsl:176-236): A already carries the mass, and the velocity gradient it stands for is C = A / m.
+ *   WGS_SUM_MASS              m
+ *   WGS_SUM_MOMENTUM + k      m * v_k
+ *   WGS_SUM_ANGULAR + k       m * (x cross v)_k + D * axial(A - A^T)_k   — about the origin; what P2G puts on the grid, exactly: sum_i w_i
+ *                             (x_i - x)(x_i - x)^T = D * I for the quadratic kernel. axial(A - A^T) = (A_zy - A_yz, A_xz - A_zx, A_yx - A_xy);
+ *                             tau is symmetric, so this is m * D * axial(C - C^T) of the velocity gradient. 2D: the z component only, in [+0].
+ *   WGS_SUM_MASS_MOMENT + k   m * x_k
+ *   WGS_SUM_KINETIC           m * |v|^2 / 2
+ *   WGS_SUM_KINETIC_AFFINE    D * |A|_F^2 / (2 m)  = m * D * |C|_F^2 / 2 with C = A / m (0 where m == 0)
+ *   WGS_SUM_GRAVITY_POTENTIAL -m * (g . x)
+ *   WGS_SUM_ELASTIC           V0 * Psi(F), Psi = the energy whose derivative is the Kirchhoff stress the step applies, tau = (dPsi/dF) F^T,
+ *                             under the model of wgs_set_constitutive_model, with the particle's own lambda, mu (F of a Drucker-Prager
+ *                             particle is its elastic part):
+ *                               corotated   (src/models/linear_elasticity.wgsl:28-41)      Psi = mu * sum_i (s_i - 1)^2 + lambda / 2 * (J - 1)^2,
+ *                               neo-Hookean (src/models/neo_hookean_elasticity.wgsl:14-25) Psi = mu / 2 * (tr F^T F - d) - mu * ln J + lambda / 2 * ln^2 J,
+ *                                           J = max(det F, 1e-10) as there.
+ *                             s_i = signed singular values (proper rotations, the sign of det F on the smallest). Evaluated through
+ *                             G = F - I and E = G + G^T + G^T G = F^T F - I: s_i - 1 = e_i / (s_i + 1) for the eigenvalues e_i of E (fp64
+ *                             cyclic Jacobi; the fp32 SVD of the step would lose (s_i - 1)^2 near the rest state), det F - 1 from the invariants of G.
+ *   WGS_SUM_GRID_MASS         m_i
+ *   WGS_SUM_GRID_MOMENTUM + k m_i * v_i,k
+ *   WGS_SUM_GRID_ANGULAR + k  m_i * (x_i cross v_i)_k,  x_i = cell * h  (2D: [+0])
+ *
+ * Reproducible accumulation. value == ldexp(fixed, exponent): `fixed` is the sum over particles (nodes) of rint(term * 2^-exponent) as a
+ * signed 64-bit integer (the reference's own device for its impulses, src/solver/p2g.wgsl:142-155, fixed point x 1e5 — with a scale that is
+ * chosen, not assumed). The components of a vector sum share one exponent:
+ *     exponent = b + nbits(N) - 62,   clamped to [-1000, 1000]
+ *   b        = the binary exponent of the largest |term| of the sum (all components) as a first pass finds it, in fp64: 2^(b-1) <= max < 2^b
+ *              (frexp); b = -200 when every term is zero;
+ *   N        = num_particles for the particle sums, 64 * active blocks for the grid sums; nbits(N) = bits of N, N < 2^nbits(N) (nbits(0) = 0).
+ * It is the smallest exponent for which N * 2^b stays below 2^62 * 2^exponent, so `fixed` cannot overflow, and the rounding error of a
+ * sum is at most N * 2^(exponent - 1). `fixed` sums of EQUAL exponent, counts and digests of the ranks of a sharded run add exactly;
+ * combining the ranks is the caller's task.
+ *
+ * Bounds (exact maxima / minima over the finite particles; where a value is computed it is computed in fp64 and rounded to fp32 once):
+ * aabb of x; max_speed = max |v|_2; max_affine_norm = max |A|_F; min / max det F; max_wave_speed = max sqrt((lambda + 2 mu) * V0 / m)
+ * (m > 0); cfl = (max |v|_inf * dt) / h in fp32. No finite particle: aabb_min = min_det_f = +inf, aabb_max = max_det_f = -inf, the rest 0.
+ *
+ * Digest. digest[0] = sum of H(p), digest[1] = sum of mix(H(p) + 0xd1b54a32d192ed03) over every particle held, modulo 2^64, with
+ *     mix(z): z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  return z ^ (z >> 31)     (splitmix64)
+ *     H = mix(id + 0x9e3779b97f4a7c15);  for every PAIR of words (w0, w1):  H = mix(H + 0x9e3779b97f4a7c15 + (w0 | w1 << 32))
+ * id = the particle's persistent id (the caller's index; the global id on sharded data); the words are the bit patterns of position,
+ * velocity, def_grad, affine (matrices column-major), the plastic state (3) and the phase (2) — the fields of wgs_read_particles in
+ * that order: 29 words in 3D, 17 in 2D, the last pair completed with a zero word. The cdf is left out (it is stamped by epoch). Data
+ * whose step carries no plastic state hashes (1, 1, 0) like wgs_read_particles reports it, and the caller's input phase — except on
+ * SHARDED data of that kind, which does not hold the phase per slot: the two phase words are zero there (create the slabs with
+ * force_plastic to compare them with a single domain).
+ *
+ * wgs_read_diagnostics blocks (the struct comes back through pinned memory); wgs_enqueue_diagnostics is stream-ordered, returns at
+ * once and leaves the struct at `device_out` (DEVICE memory), for a controller that lives on the device or a later copy. Neither
+ * writes simulation state: a step that never calls them launches exactly what it launched before. */
+enum { WGS_DIAG_PARTICLES = 1, WGS_DIAG_ENERGY = 2, WGS_DIAG_GRID = 4, WGS_DIAG_DIGEST = 8 };
+enum { /* indices into wgs_diagnostics.sum[]; vector sums take three slots in both dimensions */
+    WGS_SUM_MASS = 0, WGS_SUM_MOMENTUM = 1, WGS_SUM_ANGULAR = 4, WGS_SUM_MASS_MOMENT = 7,
+    WGS_SUM_KINETIC = 10, WGS_SUM_KINETIC_AFFINE = 11, WGS_SUM_ELASTIC = 12, WGS_SUM_GRAVITY_POTENTIAL = 13,
+    WGS_SUM_GRID_MASS = 14, WGS_SUM_GRID_MOMENTUM = 15, WGS_SUM_GRID_ANGULAR = 18, WGS_NUM_SUMS = 21
+};
+typedef struct { int64_t fixed; int32_t exponent; uint32_t reserved; double value; } wgs_fixed_sum;
+typedef struct {
+    uint64_t num_particles, num_nonfinite;
+    wgs_fixed_sum sum[WGS_NUM_SUMS];
+    float aabb_min[3], aabb_max[3];           /* 2D: [2] = 0 */
+    float max_speed, max_affine_norm, min_det_f, max_det_f, max_wave_speed, cfl;
+    uint64_t digest[2];
+    uint32_t what, model;
+} wgs_diagnostics;
+wgs_status wgs_read_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *out);
+wgs_status wgs_enqueue_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *device_out);
 
 #ifdef __cplusplus
 }

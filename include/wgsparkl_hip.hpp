@@ -161,6 +161,13 @@ class MpmData {
         check(wgs_get_stats(h_, &s));
         return s;
     }
+    // reproducible sums, bounds and the state digest of the state after the last enqueued substep, reduced on the device (no
+    // reference counterpart); `what` = OR of WGS_DIAG_*. Blocking.
+    wgs_diagnostics diagnostics(uint32_t what = WGS_DIAG_PARTICLES) {
+        wgs_diagnostics r{};
+        check(wgs_read_diagnostics(h_, what, &r));
+        return r;
+    }
     size_t num_particles() const { return n_; }
     wgs_data *handle() const { return h_; }
 

@@ -150,6 +150,53 @@ pub struct wgs_device_ptrs {
     pub hip_stream: *mut c_void,
 }
 
+/// Device-side diagnostics (`wgs_read_diagnostics`): `what` bits and the indices into `wgs_diagnostics::sum`.
+pub const WGS_DIAG_PARTICLES: u32 = 1;
+pub const WGS_DIAG_ENERGY: u32 = 2;
+pub const WGS_DIAG_GRID: u32 = 4;
+pub const WGS_DIAG_DIGEST: u32 = 8;
+pub const WGS_SUM_MASS: usize = 0;
+pub const WGS_SUM_MOMENTUM: usize = 1;
+pub const WGS_SUM_ANGULAR: usize = 4;
+pub const WGS_SUM_MASS_MOMENT: usize = 7;
+pub const WGS_SUM_KINETIC: usize = 10;
+pub const WGS_SUM_KINETIC_AFFINE: usize = 11;
+pub const WGS_SUM_ELASTIC: usize = 12;
+pub const WGS_SUM_GRAVITY_POTENTIAL: usize = 13;
+pub const WGS_SUM_GRID_MASS: usize = 14;
+pub const WGS_SUM_GRID_MOMENTUM: usize = 15;
+pub const WGS_SUM_GRID_ANGULAR: usize = 18;
+pub const WGS_NUM_SUMS: usize = 21;
+
+/// `value == ldexp(fixed, exponent)`; `fixed` sums of equal exponent add exactly.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_fixed_sum {
+    pub fixed: i64,
+    pub exponent: i32,
+    pub reserved: u32,
+    pub value: f64,
+}
+
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_diagnostics {
+    pub num_particles: u64,
+    pub num_nonfinite: u64,
+    pub sum: [wgs_fixed_sum; WGS_NUM_SUMS],
+    pub aabb_min: [f32; 3],
+    pub aabb_max: [f32; 3],
+    pub max_speed: f32,
+    pub max_affine_norm: f32,
+    pub min_det_f: f32,
+    pub max_det_f: f32,
+    pub max_wave_speed: f32,
+    pub cfl: f32,
+    pub digest: [u64; 2],
+    pub what: u32,
+    pub model: u32,
+}
+
 #[repr(C)]
 pub struct wgs_comm {
     _private: [u8; 0],
@@ -158,7 +205,7 @@ pub const WGS_COMM_ID_BYTES: usize = 128;
 pub const WGS_COMM_SELF_NEIGHBOURS: i32 = 1;
 
 /// include/wgsparkl_hip.h WGS_ABI_VERSION as this file mirrors it
-pub const ABI_VERSION: u32 = 6;
+pub const ABI_VERSION: u32 = 7;
 
 extern "C" {
     pub fn wgs_last_error() -> *const c_char;
@@ -202,6 +249,9 @@ extern "C" {
     pub fn wgs_abi_version() -> u32;
     pub fn wgs_set_grid_growth(d: *mut wgs_data, enabled: i32) -> wgs_status;
     pub fn wgs_set_uniform_material(d: *mut wgs_data, mass: f32, init_volume: f32, lambda: f32, mu: f32) -> wgs_status;
+    /// reproducible sums, bounds and state digest, reduced on the device; blocking / stream-ordered into DEVICE memory
+    pub fn wgs_read_diagnostics(d: *mut wgs_data, what: u32, out: *mut wgs_diagnostics) -> wgs_status;
+    pub fn wgs_enqueue_diagnostics(d: *mut wgs_data, what: u32, device_out: *mut wgs_diagnostics) -> wgs_status;
     /// test hook: the device scan on caller data (prefix_sum.rs:183-229 vectors)
     pub fn wgs_debug_scan(p: *mut wgs_pipeline, values: *const u32, n: u32, out: *mut u32, total: *mut u32) -> wgs_status;
 

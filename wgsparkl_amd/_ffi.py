@@ -12,7 +12,7 @@ import subprocess
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 
 WGS_OK = 0
-ABI_VERSION = 6   # include/wgsparkl_hip.h WGS_ABI_VERSION
+ABI_VERSION = 7   # include/wgsparkl_hip.h WGS_ABI_VERSION
 WGS_NUM_PASSES = 10
 PASS_NAMES = ("update rigid particles", "grid sort", "grid_update_cdf", "p2g_cdf", "g2p_cdf", "p2g",
               "grid_update", "g2p", "particles_update", "integrate_bodies")  # src/pipeline.rs:201-271
@@ -27,6 +27,8 @@ EXPORTS = (
     # one call per frame on sharded data (RCCL inside the library) + build identification
     "wgs_comm_get_unique_id", "wgs_comm_create", "wgs_comm_destroy", "wgs_shard_attach", "wgs_sharded_step",
     "wgs_sharded_step_lockstep", "wgs_build_info", "wgs_abi_version", "wgs_debug_scan", "wgs_set_grid_growth", "wgs_set_uniform_material",
+    # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
+    "wgs_read_diagnostics", "wgs_enqueue_diagnostics",
 )
 
 
@@ -115,6 +117,26 @@ class DevicePtrs(C.Structure):
                 ("dim", C.c_uint32), ("reserved", C.c_uint32), ("hip_stream", C.c_void_p)]
 
 
+# wgs_diagnostics (include/wgsparkl_hip.h "Device-side diagnostics"): the same struct in both dimensions
+DIAG_PARTICLES, DIAG_ENERGY, DIAG_GRID, DIAG_DIGEST = 1, 2, 4, 8
+DIAG_ALL = DIAG_PARTICLES | DIAG_ENERGY | DIAG_GRID | DIAG_DIGEST
+SUM_INDEX = dict(mass=0, momentum=1, angular=4, mass_moment=7, kinetic=10, kinetic_affine=11, elastic=12, gravity_potential=13,
+                 grid_mass=14, grid_momentum=15, grid_angular=18)   # WGS_SUM_*
+NUM_SUMS = 21
+
+
+class FixedSum(C.Structure):
+    """wgs_fixed_sum: value == ldexp(fixed, exponent)."""
+    _fields_ = [("fixed", C.c_int64), ("exponent", C.c_int32), ("reserved", C.c_uint32), ("value", C.c_double)]
+
+
+class Diagnostics(C.Structure):
+    _fields_ = [("num_particles", C.c_uint64), ("num_nonfinite", C.c_uint64), ("sum", FixedSum * NUM_SUMS),
+                ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("max_speed", C.c_float), ("max_affine_norm", C.c_float),
+                ("min_det_f", C.c_float), ("max_det_f", C.c_float), ("max_wave_speed", C.c_float), ("cfl", C.c_float),
+                ("digest", C.c_uint64 * 2), ("what", C.c_uint32), ("model", C.c_uint32)]
+
+
 _LIBS = {}
 
 
@@ -182,6 +204,8 @@ def load(dim: int):
         raise RuntimeError(f"{path}: ABI version {lib.wgs_abi_version()}, this binding mirrors {ABI_VERSION} — rebuild the library (csrc/build.sh)")
     lib.wgs_set_grid_growth.argtypes = [vp, C.c_int32]
     lib.wgs_set_uniform_material.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+    lib.wgs_read_diagnostics.argtypes = [vp, C.c_uint32, C.POINTER(Diagnostics)]
+    lib.wgs_enqueue_diagnostics.argtypes = [vp, C.c_uint32, vp]
     lib.wgs_debug_scan.argtypes = [vp, u32p, C.c_uint32, u32p, u32p]
     lib.wgs_comm_get_unique_id.argtypes = [C.c_char_p]
     lib.wgs_comm_create.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]

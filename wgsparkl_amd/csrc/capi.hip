@@ -151,6 +151,8 @@ struct wgs_data {
                                         // integrate_bodies, 2 = the caller sums them and integrates (lockstep group)
     int32_t **lockstep_imp_ptrs = nullptr;
     uint32_t lockstep_imp_n = 0;
+    // diagnostics (kernels_diag.h): accumulators and the result on the device (allocated by the first call, freed with `allocs`), pinned host copy
+    void *diag_acc = nullptr, *diag_out = nullptr, *diag_host = nullptr;
 };
 
 namespace {
@@ -1478,6 +1480,7 @@ void wgs_data_destroy(wgs_data *d) {
     for (void *p : d->allocs) hipFree(p);
     if (d->stream && d->owns_stream) hipStreamDestroy(d->stream);
     if (d->watch) hipHostFree(d->watch);
+    if (d->diag_host) hipHostFree(d->diag_host);
     if (d->watch_event) hipEventDestroy(d->watch_event);
     delete d->link;
     delete d;
@@ -2038,3 +2041,4 @@ wgs_status wgs_get_stats(wgs_data *d, wgs_stats *out) {
 }  // extern "C"
 
 #include "capi_sharded.inc"
+#include "kernels_diag.h"

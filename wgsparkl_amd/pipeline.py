@@ -16,7 +16,8 @@ The reference records ~25 dispatches into a `KernelInvocationQueue` once
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
@@ -25,6 +26,71 @@ from .models import MODEL_COROTATED
 from .solver import Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
+
+
+@dataclass
+class FixedSum:
+    """One reproducible sum: `value == ldexp(fixed, exponent)`; `fixed` sums of equal exponent add exactly (ranks of a sharded run)."""
+    fixed: np.ndarray       # int64, one entry per component
+    exponent: int
+    value: np.ndarray       # float64
+
+    def __float__(self):
+        return float(self.value[0])
+
+
+@dataclass
+class Diagnostics:
+    """`wgs_diagnostics` as numpy: what the simulation says about itself without a read-back (include/wgsparkl_hip.h "Device-side
+    diagnostics"). `sums[name]` for name in _ffi.SUM_INDEX; vector sums have `dim` components (angular: 1 in 2D)."""
+    dim: int
+    num_particles: int
+    num_nonfinite: int
+    sums: Dict[str, FixedSum]
+    aabb_min: np.ndarray
+    aabb_max: np.ndarray
+    max_speed: float
+    max_affine_norm: float
+    min_det_f: float
+    max_det_f: float
+    max_wave_speed: float
+    cfl: float
+    digest: tuple
+    what: int
+    model: int
+    raw: bytes              # the struct itself: two runs ended in the same state iff these bytes are equal
+
+    def value(self, name: str) -> np.ndarray:
+        return self.sums[name].value
+
+    def suggest_dt(self, dt: float, cfl_target: float = 0.5, cell_width: Optional[float] = None) -> float:
+        """The time step that would put the fastest signal of the current state at `cfl_target` cells per step: material velocity
+        (`cfl` was measured with the `dt` passed here) and, when `cell_width` is given, the elastic wave on top of it. Arithmetic on
+        the result only; `dt` is returned unchanged when nothing moves."""
+        per_dt = self.cfl / dt if dt > 0 else 0.0                    # max |v|_inf / h
+        if cell_width:
+            per_dt += self.max_wave_speed / float(cell_width)
+        return float(cfl_target / per_dt) if per_dt > 0 else float(dt)
+
+
+def diagnostics_from_struct(r, dim: int) -> Diagnostics:
+    ncomp = dict(momentum=dim, mass_moment=dim, grid_momentum=dim, angular=1 if dim == 2 else 3, grid_angular=1 if dim == 2 else 3)
+    sums = {}
+    for name, i in _ffi.SUM_INDEX.items():
+        k = ncomp.get(name, 1)
+        sums[name] = FixedSum(np.array([r.sum[i + c].fixed for c in range(k)], np.int64), int(r.sum[i].exponent),
+                              np.array([r.sum[i + c].value for c in range(k)], np.float64))
+    return Diagnostics(dim=dim, num_particles=int(r.num_particles), num_nonfinite=int(r.num_nonfinite), sums=sums,
+                       aabb_min=np.array(list(r.aabb_min)[:dim], F32), aabb_max=np.array(list(r.aabb_max)[:dim], F32),
+                       max_speed=float(r.max_speed), max_affine_norm=float(r.max_affine_norm), min_det_f=float(r.min_det_f),
+                       max_det_f=float(r.max_det_f), max_wave_speed=float(r.max_wave_speed), cfl=float(r.cfl),
+                       digest=(int(r.digest[0]), int(r.digest[1])), what=int(r.what), model=int(r.model), raw=bytes(r))
+
+
+def read_diagnostics(lib, handle, dim: int, what: int) -> Diagnostics:
+    r = _ffi.Diagnostics()
+    _ffi.check(lib, lib.wgs_read_diagnostics(handle, int(what), C.byref(r)))
+    return diagnostics_from_struct(r, dim)
 
 
 class KernelInvocationQueue:
@@ -272,6 +338,16 @@ class MpmData:
     # -- device -> host
     def sync(self):
         _ffi.check(self.lib, self.lib.wgs_sync(self._h))
+
+    def diagnostics(self, what: int = _ffi.DIAG_PARTICLES) -> Diagnostics:
+        """`wgs_read_diagnostics`: reproducible sums, bounds and the state digest of the state after the last enqueued substep,
+        reduced on the device (blocking; nothing but the small struct crosses PCIe). `what` = OR of _ffi.DIAG_*."""
+        return read_diagnostics(self.lib, self._h, self.dim, what)
+
+    def enqueue_diagnostics(self, device_ptr: int, what: int = _ffi.DIAG_PARTICLES):
+        """`wgs_enqueue_diagnostics`: the same, stream-ordered; the struct (`ctypes.sizeof(_ffi.Diagnostics)` bytes) is left at the
+        DEVICE address `device_ptr`. Returns at once."""
+        _ffi.check(self.lib, self.lib.wgs_enqueue_diagnostics(self._h, int(what), C.c_void_p(int(device_ptr))))
 
     def read_positions(self) -> np.ndarray:
         out = np.zeros((self.n, self.dim), F32)

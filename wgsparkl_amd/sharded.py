@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _ffi
 from .models import MODEL_COROTATED
-from .pipeline import MpmPipeline, _fill_collider, _pack_particles
+from .pipeline import MpmPipeline, _fill_collider, _pack_particles, read_diagnostics
 from .solver import ParticleSet, SimulationParams
 
 INT_MIN, INT_MAX = -(2 ** 31), 2 ** 31 - 1
@@ -183,6 +183,11 @@ class NativeShard:
 
     def num_particles(self) -> int:
         return self.stats()["num_particles"]
+
+    def diagnostics(self, what: int = _ffi.DIAG_PARTICLES):
+        """`wgs_read_diagnostics` over the slots this rank holds. Counts, digests and `fixed` sums of equal exponent of the ranks add
+        exactly; combining them is the caller's task."""
+        return read_diagnostics(self.lib, self._h, self.dim, what)
 
     def read_body_poses(self):
         """Like MpmData.read_body_poses: every rank integrates the same bodies, any rank can be asked."""
