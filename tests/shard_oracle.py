@@ -1,4 +1,4 @@
-"""CPU checker of the multi-GPU substep protocol (wgsparkl_amd/csrc/kernels_shard.h, capi_sharded.inc) — the SAME
+"""CPU checker of the multi-GPU substep protocol (wgsparkl_amd/csrc/kernels_shard.h, host_sharded.inc) — the SAME
 protocol restated on top of the C oracle's passes, so that the decomposition can be exercised under
 torch.distributed (gloo) without a GPU, in fp64, against the single-domain oracle run:
 

@@ -245,7 +245,7 @@ def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
         pipe.step(data, 4)
         data.sync()
         st = data.stats()
-        assert st["num_near_collider_blocks"] * 2 >= st["num_active_blocks"]     # the switch condition of capi.hip
+        assert st["num_near_collider_blocks"] * 2 >= st["num_active_blocks"]     # the switch condition of host_substep.inc plan_g2p
         pipe.step(data, 8)
         data.sync()
         return data.read_particles()

@@ -858,7 +858,7 @@ def test_oracle_parity_of_the_reference_sand3_scene_across_host_looks(hip_libs, 
 def test_one_call_of_two_thousand_substeps_keeps_its_table_in_order(hip_libs):
     """Upkeep INSIDE a call: the host takes its decisions (growth, rebuild, refresh of the table) between wgs_step calls; a caller that
     queues 2 000 substeps of a body flying across the grid in ONE call gives it no such moment. The call itself looks at its pinned
-    counters every 64 substeps it has queued (capi.hip wgs_step: watch_counters + maintain_grid): the run ends without overflow, the table was refreshed on the way, and
+    counters every 64 substeps it has queued (capi_lifecycle.inc wgs_step: watch_counters + maintain_grid of host_grid.inc): the run ends without overflow, the table was refreshed on the way, and
     the result is the bits of the same 2 000 substeps queued a hundred at a time."""
     sc = _flying_cube(40.0, 1.0 / 300.0, 512)
     ps = sc["particles"]

@@ -1,4 +1,4 @@
-"""-m gpu: one scene cut into x-slabs (kernels_shard.h, capi_sharded.inc) on one GPU — lockstep groups with device copies as the transport, one
+"""-m gpu: one scene cut into x-slabs (kernels_shard.h, host_sharded.inc, capi_sharded.inc) on one GPU — lockstep groups with device copies as the transport, one
 rank over a real RCCL communicator as its own neighbours — against the single-domain run of the same scene."""
 import numpy as np
 import pytest

@@ -1,173 +1,11 @@
-// capi_sharded.inc — the multi-GPU substep behind the C ABI (included at the end of capi.hip).
-//
-// NEW DESIGN: the reference is single-GPU (one wgpu::Device, src/pipeline.rs:176-193). A caller that replays the
-// reference contract — one call per frame, src_testbed/step.rs:122-128 — gets the x-slab decomposition of
-// kernels_shard.h through ONE entry point: wgs_sharded_step(pipeline, data, n_substeps) enqueues, per substep,
-//   sort .. P2G | pack (interface node sums + guests) | ONE ncclSend/Recv group | grid update (adds the neighbours' sums)
-//   + fused G2P + the arrivals' G2P (+ all-reduce of the body impulses + integrate_bodies)
-// on the data's stream, with no host synchronisation anywhere. RCCL is bound at run time (dlopen of librccl.so.1: the
-// copy the process already loaded — PyTorch-ROCm ships one — or the system's), so the library itself has no link-time
-// dependency on it and single-GPU users never load it.
-// wgs_sharded_step_lockstep runs the SAME per-phase code for several slabs that live in one process on one device,
-// with device-to-device copies as the transport: what the single-GPU parity tests (and a multi-slab run on one GPU) use.
-#include <mutex>
-#include <dlfcn.h>
-
-namespace {
-
-struct NcclUid { char internal[128]; };   // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128)
-enum { NCCL_INT32 = 2, NCCL_FLOAT32 = 7, NCCL_SUM = 0 };
-
-struct Rccl {
-    void *handle = nullptr;
-    int (*GetUniqueId)(NcclUid *) = nullptr;
-    int (*CommInitRank)(void **, int, NcclUid, int) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*Send)(const void *, size_t, int, int, void *, hipStream_t) = nullptr;
-    int (*Recv)(void *, size_t, int, int, void *, hipStream_t) = nullptr;
-    int (*AllReduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-    std::string error;
-};
-
-Rccl *rccl() {
-    static Rccl r;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-        for (const char *n : names) {
-            r.handle = dlopen(n, RTLD_NOW | RTLD_NOLOAD);   // the copy this process already uses, if any
-            if (r.handle) break;
-        }
-        for (const char *n : names) {
-            if (r.handle) break;
-            r.handle = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        }
-        if (!r.handle) {
-            const char *why = dlerror();
-            r.error = std::string("librccl.so.1 not found: ") + (why ? why : "");
-            return;
-        }
-#define RCCL_SYM(field, name)                                                  \
-    r.field = reinterpret_cast<decltype(r.field)>(dlsym(r.handle, name));      \
-    if (!r.field) r.error = std::string("librccl: missing symbol ") + name;
-        RCCL_SYM(GetUniqueId, "ncclGetUniqueId")
-        RCCL_SYM(CommInitRank, "ncclCommInitRank")
-        RCCL_SYM(CommDestroy, "ncclCommDestroy")
-        RCCL_SYM(GroupStart, "ncclGroupStart")
-        RCCL_SYM(GroupEnd, "ncclGroupEnd")
-        RCCL_SYM(Send, "ncclSend")
-        RCCL_SYM(Recv, "ncclRecv")
-        RCCL_SYM(AllReduce, "ncclAllReduce")
-        RCCL_SYM(GetErrorString, "ncclGetErrorString")
-#undef RCCL_SYM
-    });
-    return &r;
-}
-
-#define RCCL_TRY(expr)                                                                                              \
-    do {                                                                                                            \
-        int _rc = (expr);                                                                                           \
-        if (_rc != 0)                                                                                               \
-            return fail(WGS_ERR_HIP, std::string(#expr) + ": " + (rccl()->GetErrorString ? rccl()->GetErrorString(_rc) : "RCCL error")); \
-    } while (0)
-
-}  // namespace
-
-namespace {
-
-// Sum of the fixed-point body impulses of all slabs of a lockstep group (the ncclAllReduce of the RCCL transport):
-// integers, so any order gives the same bits.
-__global__ void k_impulses_allreduce_local(int32_t **imp, int n) {
-    const int t = threadIdx.x;  // 128 = 16 bodies x 8
-    int32_t s = 0;
-    for (int i = 0; i < n; i++) s += imp[i][t];
-    __syncthreads();
-    for (int i = 0; i < n; i++) imp[i][t] = s;
-}
-
-wgs_status shard_check(wgs_pipeline *pipeline, wgs_data *d) {
-    if (!pipeline || !d) return fail(WGS_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!d->dev.sharded) return fail(WGS_ERR_INVALID_ARGUMENT, "not a sharded wgs_data");
-    if (!d->link || !d->link->attached) return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_shard_attach has not been called on this wgs_data");
-    return WGS_OK;
-}
-
-}  // namespace
-
-namespace {
-// sharded two-way coupling: every rank holds the impulses of its own particles; all ranks need the sum
-wgs_status allreduce_impulses(wgs_data *d) {
-    if (!d->link || !d->link->comm) return WGS_OK;
-    Rccl *r = rccl();
-    RCCL_TRY(r->AllReduce(d->dev.impulses, d->dev.impulses, (size_t)WGS_MAX_COLLIDERS * 8, NCCL_INT32, NCCL_SUM, d->link->comm->comm, d->stream));
-    return WGS_OK;
-}
-
-// The split form of phase A (DBG_SHARD_SPLIT_LAYERS): the sort, then P2G of the two block layers at each cut —
-// the only slabs the outgoing messages are gathered from — with the pack waves behind it, then P2G of every other block with
-// the interior's grid update behind it. Same kernels, same sums in the same order as the unsplit form: bit-identical (tested).
-wgs_status shard_phase_begin_split(wgs_data *d) {
-    d->in_sharded_step = true;
-    wgs_status st = enqueue_substep<false>(d, 0, 1, 1);                    // the sort
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 2);            // boundary layers + pack waves
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 3);            // everything else + the interior's grid update
-    d->in_sharded_step = false;
-    return st;
-}
-
-// phase A: sort .. P2G, then the interface node sums and the guests packed into the outgoing messages
-wgs_status shard_phase_begin(wgs_pipeline *p, wgs_data *d) {
-    if ((d->dev.dbg & DBG_SHARD_SPLIT_LAYERS) && d->link && (d->link->has_lower || d->link->has_upper) && !(d->dev.dbg & DBG_GU_OWN_LAUNCH))
-        return shard_phase_begin_split(d);
-    d->in_sharded_step = true;
-    wgs_status st = enqueue_substep<false>(d, 0, 1);
-    d->in_sharded_step = false;
-    if (st != WGS_OK) return st;
-    ShardLink &L = *d->link;
-    if (!L.has_lower && !L.has_upper) return WGS_OK;
-    if (d->shard_fused) return WGS_OK;   // the pack waves rode in the P2G launch (capi.hip)
-    const PackWaves pw = pack_waves(d);   // (workgroups of one wave)
-    hipLaunchKernelGGL(k_pack_face<D>, dim3(pw.blocks + pw.guests), dim3(64), 0, d->stream, d->dev, d->side, (uint32_t)(d->substeps + 1), pw.blocks);
-    HIP_TRY(hipGetLastError());
-    return WGS_OK;
-}
-
-// phase B: grid update (which adds the neighbours' partial sums from the inbound messages) + fused G2P + the arrivals' G2P
-// (bodies deferred when the caller reduces the impulses itself)
-wgs_status shard_phase_end(wgs_pipeline *p, wgs_data *d) {
-    d->in_sharded_step = true;
-    const wgs_status st = enqueue_substep<false>(d, 0, 2);
-    d->in_sharded_step = false;
-    return st;
-}
-
-// one grouped send + receive per neighbour on the data's stream (the two neighbours are distinct peers: each message
-// rides its own xGMI link; a rank that is its own neighbour — the one-GPU proxy — matches its sends in order)
-wgs_status rccl_exchange(wgs_data *d) {
-    const hipStream_t s = d->stream;
-    ShardLink &L = *d->link;
-    Rccl *r = rccl();
-    if (!L.has_lower && !L.has_upper) return WGS_OK;
-    RCCL_TRY(r->GroupStart());
-    int rc = 0;
-    const int peers[2] = {L.comm->lower, L.comm->upper};
-    for (int f = 0; f < 2 && rc == 0; f++) {
-        if (!(f == 0 ? L.has_lower : L.has_upper)) continue;
-        rc = r->Send(L.msg_out[f], L.msg_floats, NCCL_FLOAT32, peers[f], L.comm->comm, s);
-        if (rc == 0) rc = r->Recv(L.msg_in[f], L.msg_floats, NCCL_FLOAT32, peers[f], L.comm->comm, s);
-    }
-    const int rc_end = r->GroupEnd();  // (always closed: a communicator left in group mode would swallow every later call)
-    if (rc != 0 || rc_end != 0)
-        return fail(WGS_ERR_HIP, std::string("ncclSend / ncclRecv: ") + (r->GetErrorString ? r->GetErrorString(rc != 0 ? rc : rc_end) : "RCCL error"));
-    return WGS_OK;
-}
-
-}  // namespace
+// capi_sharded.inc — entry points of the multi-GPU decomposition: communicators, wgs_shard_attach, wgs_sharded_step and its
+// one-process twin wgs_sharded_step_lockstep (what they enqueue: host_sharded.inc; wgs_shard_export is a reader: capi_io.inc).
 
 extern "C" {
+
+uint32_t wgs_shard_halo_record_bytes(void) { return (uint32_t)(HaloCfg<D>::REC_F4 * sizeof(float4)); }
+uint32_t wgs_shard_particle_record_bytes(void) { return (uint32_t)(particle_record_floats<D>() * sizeof(float)); }
+uint32_t wgs_shard_buffer_header_bytes(void) { return 16u; }
 
 wgs_status wgs_comm_get_unique_id(uint8_t id[WGS_COMM_ID_BYTES]) {
     if (!id) return fail(WGS_ERR_INVALID_ARGUMENT, "id is NULL");
@@ -214,7 +52,7 @@ void wgs_comm_destroy(wgs_comm *comm) {   // (every wgs_data attached to it must
 
 wgs_status wgs_shard_attach(wgs_data *d, wgs_comm *comm, int32_t has_lower, int32_t has_upper, uint32_t halo_capacity_records,
                             uint32_t migrant_capacity) {
-    if (!d) return fail(WGS_ERR_INVALID_ARGUMENT, "data is NULL");
+    WGS_TRY(enter(d, true, "data is NULL"));
     if (!d->dev.sharded) return fail(WGS_ERR_INVALID_ARGUMENT, "not a sharded wgs_data");
     if (d->link && d->link->attached) return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_shard_attach: already attached");
     if (d->substeps != 0) return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_shard_attach: call before the first step");
@@ -229,7 +67,6 @@ wgs_status wgs_shard_attach(wgs_data *d, wgs_comm *comm, int32_t has_lower, int3
         return fail(WGS_ERR_INVALID_ARGUMENT, "a slab with two neighbours must be at least 3 blocks wide");
     if ((has_lower && d->dev.shard_lo == INT32_MIN) || (has_upper && d->dev.shard_hi == INT32_MAX))
         return fail(WGS_ERR_INVALID_ARGUMENT, "a slab with a neighbour needs a finite block range on that side");
-    HIP_TRY(hipSetDevice(d->pipeline->device));
     if (!d->link) d->link = new ShardLink();
     ShardLink &L = *d->link;
     L.comm = comm;
@@ -238,11 +75,10 @@ wgs_status wgs_shard_attach(wgs_data *d, wgs_comm *comm, int32_t has_lower, int3
     L.halo_cap = halo_capacity_records;
     L.mig_cap = migrant_capacity;
     L.msg_floats = msg_floats<D>(L.halo_cap, L.mig_cap);
-    wgs_status st;
     for (int f = 0; f < 2; f++) {
         if (!(f == 0 ? L.has_lower : L.has_upper)) continue;
-        if ((st = dev_alloc(d, &L.msg_out[f], L.msg_floats)) != WGS_OK) return st;
-        if ((st = dev_alloc(d, &L.msg_in[f], L.msg_floats)) != WGS_OK) return st;
+        WGS_TRY(dev_alloc(d, &L.msg_out[f], L.msg_floats));
+        WGS_TRY(dev_alloc(d, &L.msg_in[f], L.msg_floats));
     }
     Dev &dev = d->dev;
     dev.shard_has_lo = L.has_lower ? 1u : 0u;
@@ -258,12 +94,11 @@ wgs_status wgs_shard_attach(wgs_data *d, wgs_comm *comm, int32_t has_lower, int3
 }
 
 wgs_status wgs_sharded_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_substeps) {
-    wgs_status st = shard_check(pipeline, d);
-    if (st != WGS_OK) return st;
+    WGS_TRY(shard_check(pipeline, d));
+    wgs_status st = WGS_OK;
     ShardLink &L = *d->link;
     const bool neighbours = L.has_lower || L.has_upper;
     if (neighbours && !L.comm) return fail(WGS_ERR_INVALID_ARGUMENT, "slab has neighbours but no communicator: use wgs_sharded_step_lockstep");
-    HIP_TRY(hipSetDevice(pipeline->device));
     // body impulses are reduced over ALL ranks (also those without particles near the body) before integrate_bodies
     d->reduce_impulses = (d->two_way && L.comm && L.comm->world > 1) ? 1 : 0;
     if ((st = maintain_grid(d)) != WGS_OK) return st;
@@ -285,8 +120,7 @@ wgs_status wgs_sharded_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_su
 wgs_status wgs_sharded_step_lockstep(wgs_pipeline *pipeline, wgs_data **slabs, uint32_t num_slabs, uint32_t num_substeps) {
     if (!pipeline || !slabs || num_slabs == 0) return fail(WGS_ERR_INVALID_ARGUMENT, "NULL argument");
     for (uint32_t r = 0; r < num_slabs; r++) {
-        wgs_status st = shard_check(pipeline, slabs[r]);
-        if (st != WGS_OK) return st;
+        WGS_TRY(shard_check(pipeline, slabs[r]));
         ShardLink &L = *slabs[r]->link;
         if (L.comm) return fail(WGS_ERR_INVALID_ARGUMENT, "lockstep slabs must be attached without a communicator");
         if (L.has_lower != (r > 0) || L.has_upper != (r + 1 < num_slabs))
@@ -341,7 +175,7 @@ wgs_status wgs_sharded_step_lockstep(wgs_pipeline *pipeline, wgs_data **slabs, u
         for (uint32_t r = 0; r < num_slabs; r++) host[r] = slabs[r]->dev.impulses;
         wgs_data *d0 = slabs[0];
         if (!d0->lockstep_imp_ptrs || d0->lockstep_imp_n != num_slabs) {
-            if (d0->lockstep_imp_ptrs) release_alloc(d0, d0->lockstep_imp_ptrs);
+            d0->mem.release(d0->lockstep_imp_ptrs);
             d0->lockstep_imp_ptrs = nullptr;
             LOCKSTEP_TRY(dev_alloc(d0, &d0->lockstep_imp_ptrs, num_slabs));
             d0->lockstep_imp_n = num_slabs;

@@ -1,0 +1,477 @@
+// host_substep.inc — one substep on the data's stream: the tunables of the launch shapes, the launch ladders (which
+// instantiation a decided shape means), the launch plans (which shape a substep takes: plan_p2g, plan_g2p) and
+// enqueue_substep, which strings them together. Everything that decides WHAT is launched lives here; entry points only
+// call enqueue_substep / enqueue_bodies.
+
+namespace {
+
+wgs_status allreduce_impulses(wgs_data *d);  // host_sharded.inc
+
+#ifndef WGS_PCDF_WAVES_MAX_VISITS
+#define WGS_PCDF_WAVES_MAX_VISITS 256
+#endif
+constexpr uint32_t PCDF_WAVES_MAX_VISITS = WGS_PCDF_WAVES_MAX_VISITS;   // per XCD list: above, the prologue waves would be a round of work in front of the launch, not a use of idle CUs
+constexpr uint32_t P2G_SMALL_BUDGET_MIN_PARTICLES = 600000;  // one-way CPIC P2G body at 168 VGPRs from this size on
+#ifndef WGS_REGROUP_ROUNDS
+#define WGS_REGROUP_ROUNDS 4u
+#endif
+#ifndef WGS_GU_WG_PER_CU
+#define WGS_GU_WG_PER_CU 8
+#endif
+#ifndef WGS_PLASTIC_WPE_DENSE
+#define WGS_PLASTIC_WPE_DENSE 2
+#endif
+#ifndef WGS_PLASTIC_WPE
+#define WGS_PLASTIC_WPE G2P_WAVES_PER_EU
+#endif
+constexpr uint32_t P2G_PAIR_MIN_BLOCKS = 8;  // near-collider blocks from which P2G runs both bodies in one launch
+
+// ---- launch ladders of enqueue_substep: each takes the shape enqueue_substep decided and lists exactly the instantiations
+// that exist. (Templates on the dimension: they are instantiated where enqueue_substep reaches them, which keeps the kernels
+// in the code object in the order of their first use — placement alone moves a kernel by a few percent, DESIGN 9.7.)
+
+// pack waves of a slab with neighbours: one per interface block as the host last saw the grid (a face holds a fraction of the
+// active blocks), plus a few for the guests
+struct PackWaves {
+    uint32_t blocks, guests;
+};
+PackWaves pack_waves(const wgs_data *d) {
+    return {std::max(64u, std::min(2048u, d->seen.nblocks ? d->seen.nblocks : 2048u)), std::max(1u, std::min(64u, (2u * d->link->mig_cap + 63u) / 64u))};
+}
+
+// launch 2 of the sort (kernels_sort.h): CDF = the node cdfs and block classes ride in it; SUMM = blocks share node-cdf summaries
+template <int DIM> void launch_regroup(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, uint32_t nscan, int have_old, bool cdf, bool summ) {
+    const dim3 b(SORT_THREADS);
+    if (cdf && dev.sharded && summ) hipLaunchKernelGGL((k_regroup<DIM, true, true, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf && dev.sharded) hipLaunchKernelGGL((k_regroup<DIM, true, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf && summ) hipLaunchKernelGGL((k_regroup<DIM, true, false, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (cdf) hipLaunchKernelGGL((k_regroup<DIM, true, false>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else if (dev.sharded) hipLaunchKernelGGL((k_regroup<DIM, false, true>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+    else hipLaunchKernelGGL((k_regroup<DIM, false, false>), g, b, 0, s, dev, side, epoch, nscan, have_old);
+}
+
+enum class P2gShape {
+    plain,       // no collider: the plain body
+    separate,    // the plain body, then the CPIC body (particle cdf in its prologue) in a launch of its own
+    cpic_first,  // the CPIC body first, then the plain body with the grid update riding in it
+    pair,        // both bodies in one launch (k_p2g_pair)
+};
+struct P2gLaunch {
+    P2gShape shape;
+    bool two_way;       // the two-way CPIC body
+    bool small_budget;  // pair, one-way: the CPIC body cut to 168 VGPRs
+    int gu;             // what rides in the last launch (kernels_transfer.h GU): 0 nothing, 2 the grid update, 3 a slab's pack waves + interior update
+    uint32_t wgs;       // workgroups per body
+    uint32_t ride;      // workgroups behind the P2G workgroups of the last launch: npack + the grid update's
+    uint32_t npack, npack_blk, layer_sel;
+    uint32_t npro;      // prologue workgroups (kernels_transfer.h pcdf_waves)
+};
+
+template <int DIM, bool TW, int WPE> void launch_p2g_pair(Dev &dev, hipStream_t s, int side, uint32_t epoch, const P2gLaunch &p) {
+    const dim3 g(p.npro + 2u * p.wgs + p.ride), b(P2GCfg<DIM>::NW * 64);
+    dev.pcdf_waves = p.npro;
+    if (p.gu == 2) hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 2>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    else if (p.gu == 3) hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 3>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    else hipLaunchKernelGGL((k_p2g_pair<DIM, TW, WPE, 0>), g, b, 0, s, dev, side, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, p.npro);
+    dev.pcdf_waves = 0u;
+}
+
+// the last P2G launch of the substep, with what rides behind its workgroups
+template <int DIM, bool CP, bool TW, bool PC> void launch_p2g_last(Dev &dev, hipStream_t s, int side, int filter, uint32_t epoch, const P2gLaunch &p) {
+    const uint32_t npro = PC ? p.npro : 0u;
+    const dim3 g(npro + p.wgs + p.ride), b(P2GCfg<DIM>::NW * 64);
+    dev.pcdf_waves = npro;
+    if (p.gu == 2) hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 2>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    else if (p.gu == 3) hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 3>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    else hipLaunchKernelGGL((k_p2g<DIM, CP, TW, PC, 0>), g, b, 0, s, dev, side, filter, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, npro);
+    dev.pcdf_waves = 0u;
+}
+
+template <int DIM> void launch_p2g(Dev &dev, hipStream_t s, int side, uint32_t epoch, const P2gLaunch &p) {
+    const dim3 g(p.wgs), b(P2GCfg<DIM>::NW * 64);
+    switch (p.shape) {
+        case P2gShape::pair:
+            if (p.two_way) launch_p2g_pair<DIM, true, 1>(dev, s, side, epoch, p);
+            else if (p.small_budget) launch_p2g_pair<DIM, false, 3>(dev, s, side, epoch, p);
+            else launch_p2g_pair<DIM, false, 1>(dev, s, side, epoch, p);
+            break;
+        case P2gShape::cpic_first:
+            dev.pcdf_waves = p.npro;
+            hipLaunchKernelGGL((k_p2g<DIM, true, true, true, 1>), dim3(p.npro + p.wgs), b, 0, s, dev, side, 2, epoch, p.wgs, 0u, 0u, p.layer_sel, p.npro);
+            dev.pcdf_waves = 0u;
+            hipLaunchKernelGGL((k_p2g<DIM, false, false, false, 2, true>), dim3(p.wgs + p.ride), b, 0, s, dev, side, 1, epoch, p.wgs, p.npack, p.npack_blk, p.layer_sel, 0u);
+            break;
+        case P2gShape::separate:
+            // (the first of the two launches hands its slabs over like the last one when anything rides in that one)
+            if (p.gu != 0) hipLaunchKernelGGL((k_p2g<DIM, false, false, false, 1>), g, b, 0, s, dev, side, 1, epoch, p.wgs, 0u, 0u, p.layer_sel, 0u);
+            else hipLaunchKernelGGL((k_p2g<DIM, false>), g, b, 0, s, dev, side, 1, epoch, p.wgs, 0u, 0u, p.layer_sel, 0u);
+            // near-collider list: particle cdf in the prologue (the node cdfs are complete: k_setup_scatter<CDF>, or
+            // k_cdf after k_p2g_cdf with mesh colliders), then the CPIC transfer
+            if (p.two_way) launch_p2g_last<DIM, true, true, true>(dev, s, side, 2, epoch, p);
+            else launch_p2g_last<DIM, true, false, true>(dev, s, side, 2, epoch, p);
+            break;
+        case P2gShape::plain:
+            launch_p2g_last<DIM, false, false, false>(dev, s, side, 0, epoch, p);
+            break;
+    }
+}
+
+// PHASE 0: every block of single-domain data; 3: a slab's blocks after the exchange (iface_only: the interior's rode in P2G)
+template <int DIM> void launch_grid_update(const Dev &dev, hipStream_t s, dim3 g, uint32_t epoch, bool slab, bool two_way, uint32_t iface_only) {
+    if (!slab && two_way) hipLaunchKernelGGL((k_grid_update<DIM, 0, true>), g, dim3(256), 0, s, dev, epoch, 0u);
+    else if (!slab) hipLaunchKernelGGL((k_grid_update<DIM, 0>), g, dim3(256), 0, s, dev, epoch, 0u);
+    else if (two_way) hipLaunchKernelGGL((k_grid_update<DIM, 3, true>), g, dim3(256), 0, s, dev, epoch, iface_only);
+    else hipLaunchKernelGGL((k_grid_update<DIM, 3>), g, dim3(256), 0, s, dev, epoch, iface_only);
+}
+
+enum class G2pShape {
+    single,        // no collider: one launch
+    two_launches,  // the plain body, then the CPIC body in a launch of its own
+    pair,          // both bodies in one launch (k_g2p_pair)
+    pair_dense,    // ... in the spill-free plastic variant
+};
+struct G2pLaunch {
+    G2pShape shape;
+    bool shard;
+    uint32_t g;      // main-body waves: one per `npass` chunks of 64 sorted particles, a multiple of 8 (XCD-aware mapping)
+    uint32_t nlist;  // list waves per XCD of the CPIC body (8 x nlist in all)
+};
+
+// (the decomposition is a template parameter of the fused G2P: kernels_transfer.h; BIN: not the plastic variants)
+template <int DIM, int MODEL, bool PL, int NP, class Mark>
+void launch_g2p_shape(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
+    constexpr int WPE = PL ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, WPE_DENSE = PL ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU;
+    const dim3 g(p.g), pg(p.g + 8u * p.nlist), t(G2P_THREADS);
+    switch (p.shape) {
+        case G2pShape::pair_dense:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            break;
+        case G2pShape::pair:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            break;
+        case G2pShape::two_launches:
+            hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 1, NP, false, !PL>), g, t, 0, s, dev, side, epoch);
+            mark(6);
+            hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 2, 1, false, !PL>), dim3(8u * p.nlist), t, 0, s, dev, side, epoch);
+            break;
+        case G2pShape::single:
+            if (p.shard) hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, true, !PL>), g, t, 0, s, dev, side, epoch);
+            else hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, false, !PL>), g, t, 0, s, dev, side, epoch);
+            break;
+    }
+}
+
+template <int DIM, int MODEL, bool PL, class Mark>
+void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
+    if (dev.g2p_npass == (uint32_t)G2P_MANY_PASSES) launch_g2p_shape<DIM, MODEL, PL, G2P_MANY_PASSES>(dev, s, side, epoch, p, mark);
+    else if (dev.g2p_npass == 2u) launch_g2p_shape<DIM, MODEL, PL, 2>(dev, s, side, epoch, p, mark);
+    else launch_g2p_shape<DIM, MODEL, PL, 1>(dev, s, side, epoch, p, mark);
+}
+
+// the fused G2P; `mark(6)` between the two launches of that shape
+template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
+    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+        case 0: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
+        case 1: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
+        case 2: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
+        default: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
+    }
+}
+
+template <int DIM> void launch_arrivals(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, bool plastic) {
+    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case 1: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case 2: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        default: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+    }
+}
+
+// The shape of this substep's P2G (`part`, `p2g_sel`: enqueue_substep). Sets what the grid update that follows needs to know.
+P2gLaunch plan_p2g(wgs_data *d, int part, int p2g_sel) {
+    const Dev &dev = d->dev;
+    const uint32_t n = dev.n;
+    const uint32_t NW = (uint32_t)P2GCfg<D>::NW;
+    P2gLaunch p{};
+    p.two_way = d->two_way;
+    p.layer_sel = p2g_sel == 2 ? 1u : p2g_sel == 3 ? 2u : 0u;   // (kernels_transfer.h: boundary layers / the others)
+    // Workgroups per body: about one per two entries of the block list (as the host last saw it), between 8 and
+    // 32 per CU. A workgroup strides over the list, and the dispatcher balances better than a fixed stride does:
+    // blocks differ in cost, and with 5 per CU — one resident round and a quarter — the quarter started when the
+    // first workgroups retired (C5, 16 M particles: P2G 472 -> 346 us; C2: 35.6 -> 31.8 us). Same results for
+    // any grid: a block's slab is the work of one workgroup.
+    p.wgs = std::min((uint32_t)grid_for(d, 32), std::max((uint32_t)grid_for(d, 8), (d->seen.nblocks / 2u + 255u) & ~255u));
+    // Single-domain simulations: the grid update rides in the (last) P2G launch as workgroups of its own
+    // behind the P2G workgroups (kernels_transfer.h gu_waves; GU = 2), one wave per active block as the host last saw
+    // them; a P2G launch before it hands its slabs over the same way (GU = 1). Same results as the launch of its own
+    // (DBG_GU_OWN_LAUNCH): the same sums in the same order.
+    const bool fuse_gu = part == 0 && !dev.sharded && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    // Inside wgs_sharded_step (part 1 of a slab's substep): behind the P2G workgroups ride the waves that pack the
+    // outgoing messages (no k_pack_face launch) and the grid update of the INTERIOR blocks — everything that does
+    // not wait for the exchange; the interface layers are updated after it (GU = 3).
+    const bool fuse_shard = part == 1 && d->sub.in_sharded_step && d->link && d->link->attached && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    p.gu = fuse_gu ? 2 : fuse_shard ? 3 : 0;
+    d->sub.gu_fused = fuse_gu;
+    d->sub.shard_fused = fuse_shard;
+    // (8, 16, 32 or 64 workgroups per CU at most: the same times at C2 / C3 / C5)
+    const uint32_t gu_wgs = (p.gu == 0 || p2g_sel == 2) ? 0u : std::min((uint32_t)grid_for(d, 8), std::max((uint32_t)grid_for(d, 1), ((d->seen.nblocks + NW - 1u) / NW + 7u) & ~7u));
+    if (fuse_shard && (d->link->has_lower || d->link->has_upper) && p2g_sel != 3) {   // (they ride behind the boundary layers' P2G)
+        const PackWaves pw = pack_waves(d);
+        p.npack_blk = pw.blocks;
+        p.npack = (pw.blocks + pw.guests + NW - 1u) / NW;
+    }
+    p.ride = p.npack + gu_wgs;
+    // Prologue waves (kernels_transfer.h pcdf_waves): the particle cdf of the listed blocks by one wave per visit-list entry in front
+    // of the paired launch, while the lists are short enough for the idle part of the chip to take them at once (as of the
+    // host's last look: the waves stride over whatever the lists hold now). Single-domain data only: a slab's pack waves read
+    // the guests' quads inside the launch.
+    if (d->cpic && !dev.sharded && d->seen.nvisit != UINT32_MAX && d->seen.nvisit != 0u && d->seen.nvisit <= PCDF_WAVES_MAX_VISITS && !(dev.dbg & DBG_NO_PCDF_WAVES))
+        p.npro = 8u * ((std::min(d->seen.nvisit + 8u, dev.visit_cap) + NW - 1u) / NW);
+    if (d->cpic && !dev.sharded && (dev.dbg & DBG_PCDF_WAVES_UNSIZED)) p.npro = 8u;   // (the launch itself then decides, device_math.h pcdf_waves_on)
+    if (!d->cpic) {
+        p.shape = P2gShape::plain;
+        return p;
+    }
+    // Large one-way collider simulations ALWAYS run the paired launch, with the CPIC body cut to 168 VGPRs: the
+    // plain body then keeps its occupancy, so the pair costs nothing while the list is empty, and the choice
+    // does not follow the host's syncs (the two budgets differ in the last bit here and there).
+    p.small_budget = !d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES && !(dev.dbg & DBG_NO_P2G_SMALL_BUDGET);
+    // Large TWO-WAY simulations never pair: the kernel would take the two-way CPIC body's 225 registers and the plain
+    // body — nearly every block — would run at two thirds of its occupancy (C4, 8 M particles: P2G 416 -> 347 us
+    // with the two launches). Bit-identical either way (the same body text under -ffp-contract=on).
+    const bool big_two_way = d->two_way && n >= P2G_SMALL_BUDGET_MIN_PARTICLES;
+    // (small two-way scenes pair whatever the list length: they fill less than one round of workgroups, so the plain body's lost
+    // occupancy costs nothing and a launch goes — the reference's sand2, 490 k particles, 2D: 76-79 -> 67-68 us per substep;
+    // the one-way 262 k cube: P2G 20.4 + a boundary -> 18.3 us, not taken: its fused G2P then ran 27 us every other run against 21-22)
+    const bool small_two_way = d->two_way && n < P2G_SMALL_BUDGET_MIN_PARTICLES;
+    // many blocks near colliders (as of the last wgs_sync): both bodies in one launch
+    const bool many_listed = d->seen.ncpic != UINT32_MAX && d->seen.ncpic >= P2G_PAIR_MIN_BLOCKS;
+    if (!big_two_way && (p.small_budget || small_two_way || many_listed) && !(dev.dbg & DBG_P2G_TWO_LAUNCHES))
+        p.shape = P2gShape::pair;
+    // Large two-way simulations on a single domain: the near-collider launch FIRST, the plain launch behind it with the grid
+    // update riding in IT. The grid-update waves take the registers of the launch they ride in: behind the two-way body (209
+    // registers, two waves per SIMD) the update of every block of the scene ran at two thirds of the occupancy it has behind
+    // the plain body (160), and started only when the last near-collider workgroup — a 30 us chain each — had a slot. Same
+    // sums in the same order (DBG_PLAIN_P2G_FIRST = the plain launch first, as before: tested bit-identical).
+    else if (big_two_way && p.gu == 2 && !(dev.dbg & DBG_PLAIN_P2G_FIRST))
+        p.shape = P2gShape::cpic_first;
+    else
+        p.shape = P2gShape::separate;
+    return p;
+}
+
+// The shape of this substep's fused G2P (dev.g2p_npass set).
+G2pLaunch plan_g2p(const wgs_data *d) {
+    const Dev &dev = d->dev;
+    const uint32_t npass = dev.g2p_npass;
+    // the list walk of the CPIC body: a wave and a half per SIMD unless the host saw the visit lists
+    const uint32_t full = (uint32_t)grid_for(d, 1) * 3u / 2u;
+    G2pLaunch p{G2pShape::single, dev.sharded != 0u, ((dev.nv + G2P_THREADS * npass - 1) / (G2P_THREADS * npass) + 7) / 8 * 8, full};
+    // (a slab always takes the paired / single-body launch shapes, the two-launch debug shape exists for single-domain data only)
+    if (d->cpic && (p.shard || !(dev.dbg & DBG_G2P_TWO_LAUNCHES))) {
+        // both bodies in one launch; list waves (8 x nlist; the waves of an XCD stride over the runs of its visit list): 2 x the
+        // runs of the longest list as the host last saw it
+        const uint32_t per_run = std::min<uint32_t>(npass, WGS_G2P_LIST_PASSES);
+        if (d->seen.nvisit != UINT32_MAX) p.nlist = std::min(full, std::max(8u, 2u * ((d->seen.nvisit + per_run - 1u) / per_run)));
+        // plastic scenes with a large share of listed blocks: the spill-free variant (kernels_transfer.h)
+        const bool dense = d->plastic && d->seen.ncpic != UINT32_MAX && d->seen.ncpic * 2u >= std::max(1u, d->seen.sync_nblocks) && !(dev.dbg & DBG_NO_G2P_DENSE);
+        p.shape = dense ? G2pShape::pair_dense : G2pShape::pair;
+    } else if (d->cpic) {
+        p.shape = G2pShape::two_launches;
+    }
+    return p;
+}
+
+// One substep = pipeline.rs:201-280 (MPM passes), enqueued on the data's stream.
+// part 0 = the whole substep (single GPU, or a slab stepped without its neighbours); the sharded step splits it around
+// its one neighbour exchange: part 1 = sort .. P2G, part 2 = grid update + fused G2P (+ the arrivals' G2P) + bodies.
+// `p2g_sel` splits part 1 further (DBG_SHARD_SPLIT_LAYERS on lockstep slabs): 0 = all of it; 1 = the sort only; 2 = P2G of the
+// boundary layers with the pack waves behind it; 3 = P2G of all other blocks with the interior's grid update.
+template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part, int p2g_sel = 0) {
+    Dev &dev = d->dev;
+    hipStream_t s = d->stream;
+    const bool first = part != 2 && p2g_sel <= 1;   // the first call of this substep
+    const int side = d->side;
+    const uint32_t n = dev.n;
+    const int pgrid = (int)((n + SORT_THREADS - 1) / SORT_THREADS);
+    static const bool trace = getenv("WGS_TRACE") != nullptr;   // developer aid: drain the stream at every pass boundary and say so
+    auto mark = [&](int m) {
+        if (TS) hipEventRecord(d->timing.events.ev[ts_slot][m], s);
+        if (trace) {
+            const hipError_t te = hipStreamSynchronize(s);
+            fprintf(stderr, "[wgs trace] substep %llu part %d mark %d: %s\n", (unsigned long long)d->substeps, part, m, hipGetErrorString(te));
+        }
+    };
+    const uint32_t epoch = (uint32_t)(d->substeps + 1);
+    d->sub.gu_fused = false;
+    if (first) d->sub.shard_fused = false;   // (part 2 of a sharded substep consumes what its part 1 decided)
+    dev.ctr_set = (uint32_t)(d->substeps & 1u);  // sharded runs: the set of particle counters this substep reads (layout.h)
+    // chunks of 64 sorted particles per wave of the fused G2P (kernels_transfer.h); the sort files the visit list by it
+    // (2D: the body keeps no state of the chunk after the next one — at most two chunks per wave)
+    const uint32_t nv_now = dev.sharded && d->seen.nv_hint != 0u ? std::min(d->seen.nv_hint, dev.nv) : dev.nv;   // (a slab launches for its capacity)
+    dev.g2p_npass = (D == 3 && nv_now >= G2P_MANY_PASS_MIN_PARTICLES) ? (uint32_t)G2P_MANY_PASSES
+                    : (nv_now >= G2P_TWO_PASS_MIN_PARTICLES || (dev.dbg & DBG_G2P_TWO_PASSES)) ? 2u : 1u;
+    // Steady state: the buffer is in the sorted order of the previous substep, whose block ids, cell ids
+    // (perm_cell) and neighbour links are still valid, so the particles are re-binned RELATIVE to their old
+    // block (k_rebin: no hash lookups except for the few particles that changed block). The full k_bin runs
+    // on the first substep, on table-rebuild substeps and in sharded runs (particles arrive from neighbours).
+    const bool rehash = d->substeps == 0 || (d->rehash_period != 0u && d->substeps % d->rehash_period == 0) || (d->seen.force_rehash && first);
+    if (rehash && first) {
+        d->stats.table_rebuilds++;
+        d->seen.force_rehash = false;
+        d->cdf_generation++;   // block ids are handed out anew
+    }
+    // node cdfs / block classes are reused from one substep to the next while no collider can move
+    dev.cdf_gen = d->cpic ? d->cdf_generation : 0u;
+    dev.cdf_moving = d->moving_mask;
+    const bool fused_cdf = d->cpic && dev.n_rigid == 0;  // (mesh cdfs are only complete after k_p2g_cdf)
+    if (first) dev.listed_in_perm = fused_cdf ? 1u : 0u;  // (part 2 of a sharded substep consumes what its part 1 wrote)
+    const bool use_rebin = d->sub.prev_sorted && !rehash && !(dev.dbg & DBG_NO_REBIN);
+    // The fused G2P of this substep also bins its output for the next one (g2p_body.inc, Dev::bin_next; slabs too), unless
+    // that substep rebuilds the table anyway (DBG_REBIN_LAUNCH brings launch 1 of the sort, k_rebin, back: same results, tested).
+    // `prebinned`: the previous substep's G2P did so for this one.
+    const bool binned = use_rebin && d->sub.prebinned;
+    if (first && d->sub.prebinned && !binned) {
+        // (a table rebuild nobody could foresee — ids three quarters handed out, seen by the host in between: what the G2P
+        // accumulated for the old ids is dropped; the stamps it left mean nothing once the ids are handed out anew)
+        HIP_TRY(hipMemsetAsync(dev.block_acc, 0, sizeof(uint32_t) * (size_t)dev.cap, s));
+        HIP_TRY(hipMemsetAsync(dev.cell_head, 0, sizeof(uint32_t) * (size_t)dev.cap * NPB, s));
+        HIP_TRY(hipMemsetAsync(dev.blk_narr, 0, sizeof(uint32_t) * (size_t)dev.cap, s));
+    }
+    if (first) d->sub.prebinned = false;
+    // (not the plastic variants: their fused G2P is compiled without the binning — kernels_transfer.h: the code alone, beyond the
+    // instruction cache, cost a third of the launch — and launch 1 of the sort, k_rebin, stays)
+    // (a slab: its fused G2P bins the residents — the guests it drops leave their block's total —, k_g2p_arrivals the particles that
+    // arrive; both parts of a sharded substep see the same value)
+    dev.bin_next = (!d->plastic && !(dev.dbg & (DBG_NO_REBIN | DBG_REBIN_LAUNCH)) && (d->rehash_period == 0u || (d->substeps + 1) % d->rehash_period != 0)) ? 1u : 0u;
+    // the fused G2P drops the guests only inside the sharded step (kernels_shard.h); wgs_step on a slab advances what it holds
+    dev.skip_guests = (d->sub.in_sharded_step && dev.sharded) ? 1u : 0u;
+    if (dev.sharded && d->sub.needs_compact && first) {
+        hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, s, dev);
+        d->sub.needs_compact = false;
+    }
+    if (first) {
+        if (TS) {  // two adjacent marks: their distance is what every interval below pays for its closing mark
+            mark(9);
+            mark(10);
+        }
+        mark(0);
+        // ---- "grid sort" (grid.rs:30-207)
+        if (d->seen.force_refresh && !rehash && dev.free_ids != nullptr) {
+            // the marks of evicted blocks crowd the table (the host's last look): clear it and insert the live blocks again under
+            // their own ids — no particle is touched, the steady-state sort goes on (kernels_sort.h k_table_refresh)
+            HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
+            HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
+            hipLaunchKernelGGL(k_table_refresh, dim3(std::max(1u, std::min((dev.cap + 255u) / 256u, (uint32_t)grid_for(d, 4)))), dim3(256), 0, s, dev);
+            d->stats.table_refreshes++;
+        }
+        if (first) d->seen.force_refresh = false;
+        if (rehash) {  // reset_hmap, amortised (device_math.h)
+            HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
+            HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
+            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NPHYS, 0, sizeof(uint32_t), s));
+            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NFREE, 0, 3 * sizeof(uint32_t), s));   // (free list, insertion count, marks: layout.h)
+        }
+        // ---- "update rigid particles" (rigid_particle_update.wgsl): samples and vertices of the mesh colliders
+        if (dev.n_rigid > 0)
+            hipLaunchKernelGGL(k_rigid_transform<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev);
+        if (n > 0) {
+            // (sharded runs: k_rebin also bins the particles that arrived in the last substep, behind the residents)
+            // (a pending integrate_bodies of the previous substep rides in workgroup 0 of this launch)
+            const uint32_t do_bodies = d->sub.bodies_pending ? 1u : 0u;
+            d->sub.bodies_pending = false;
+            if (binned) {   // launch 1 ran inside the previous substep's fused G2P
+                if (do_bodies) hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, s, dev);
+            } else if (use_rebin) hipLaunchKernelGGL(k_rebin<D>, dim3((pgrid + REBIN_K - 1) / REBIN_K), dim3(SORT_THREADS), 0, s, dev, side, epoch, do_bodies);
+            else hipLaunchKernelGGL(k_bin<D>, dim3(pgrid), dim3(SORT_THREADS), 0, s, dev, side, epoch, do_bodies);
+            if (dev.n_rigid > 0) {  // blocks a mesh sample reaches must exist (sort.wgsl:38-86)
+                hipLaunchKernelGGL(k_rigid_mark<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev, epoch);
+                hipLaunchKernelGGL(k_rigid_touch<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev, epoch);
+            }
+            // launch 2: chunked scan (active list, first_particle) + per-block setup and regrouping in canonical order.
+            // Collider simulations without mesh colliders: node cdf + block classes ride in this launch, the particle
+            // cdf in the CPIC P2G launch (no CDF launch at all)
+            {
+                const uint32_t nscan = (dev.cap + SCAN_CHUNK - 1) / SCAN_CHUNK;
+                // one resident round: 4 workgroups per CU (127 VGPRs, 36 KB of LDS), the scan workgroups among them
+                const uint32_t nreg = std::max(1u, std::min((dev.cap + 3u) / 4u, WGS_REGROUP_ROUNDS * ((uint32_t)grid_for(d, 4) - std::min(nscan, (uint32_t)grid_for(d, 2)))));
+                const dim3 g(nscan + nreg);
+                const int have_old = use_rebin ? 1 : 0;
+                // (summ: every block within reach of a collider is evaluated substep after substep — each evaluates its own nodes and
+                // tells its neighbours, kernels_sort.h block_cdf_summ; with colliders at rest: the instantiation without)
+                const bool summ = (dev.cdf_moving != 0u || dev.cdf_gen == 0u) && !(dev.dbg & DBG_NO_CDF_SUMM);
+                launch_regroup<D>(dev, s, g, side, epoch, nscan, have_old, fused_cdf, summ);
+            }
+        } else {
+            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NBLOCKS, 0, sizeof(uint32_t), s));
+        }
+        mark(1);
+        // ---- "grid_update_cdf" + "g2p_cdf" (collide.wgsl, grid_update_cdf.wgsl, g2p_cdf.wgsl): one launch
+        // (kernels_cdf.h); the reference's two pass names share its time in wgs_read_timings
+        if (dev.n_rigid > 0 && n > 0)  // "p2g_cdf": mesh primitives -> node cdf accumulators
+            hipLaunchKernelGGL(k_p2g_cdf<D>, dim3(std::min((dev.n_rigid * 32u + 255u) / 256u, (uint32_t)grid_for(d, 32))), dim3(256), 0, s, dev, epoch);
+        if (d->cpic && n > 0 && !fused_cdf)
+            hipLaunchKernelGGL(k_cdf<D>, dim3(grid_for(d, 16)), dim3(CDF_THREADS), 0, s, dev, side, epoch);
+        mark(2);
+        mark(3);
+    }
+    if (part != 2 && p2g_sel != 1) {
+        if (n > 0) launch_p2g<D>(dev, s, side, epoch, plan_p2g(d, part, p2g_sel));   // ---- "p2g"
+        mark(4);
+    }
+    if (part != 1) {
+        // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
+        if (n > 0 && !(part == 0 && d->sub.gu_fused))
+            launch_grid_update<D>(dev, s, dim3(grid_for(d, WGS_GU_WG_PER_CU)), epoch, part != 0, d->two_way, d->sub.shard_fused ? 1u : 0u);
+        mark(5);
+        // ---- "g2p" + "particles_update", fused (mark 6: between the two launches of a collider simulation's G2P)
+        const G2pLaunch g2p = plan_g2p(d);
+        if (dev.nv > 0) launch_g2p<D>(dev, s, side, epoch, d->plastic, g2p, mark);
+        if (!(dev.nv > 0 && g2p.shape == G2pShape::two_launches)) mark(6);
+        // sharded step: the particles that arrived with this substep's messages are advanced too (kernels_arrivals.h), by a
+        // launch of their own behind the fused G2P. (As extra workgroups INSIDE that launch — first or last in its grid — they
+        // made it 7-10 us longer at a 1 M slab for the 5 us launch they saved: measured twice in round 3, not kept.)
+        // (the arrivals' body also does the bookkeeping of the migration round, so it runs even when nobody can arrive)
+        const bool arrivals = part == 2 && d->sub.in_sharded_step && d->link && d->link->attached;
+        if (arrivals) {
+            const uint32_t arr_most = ((d->link->has_lower ? 1u : 0u) + (d->link->has_upper ? 1u : 0u)) * d->link->mig_cap;
+            launch_arrivals<D>(dev, s, dim3(std::max(1u, std::min((arr_most + ARR_PER_WG - 1u) / ARR_PER_WG, 1024u))), side, epoch, d->plastic);
+        }
+        mark(7);
+        // ---- "integrate_bodies" (rigid_impulses.wgsl:95-136) + the world mass properties of the next substep
+        // (pipeline.rs:204-205). Skipped while no body has a velocity or a mass: it would be the identity.
+        if (d->bodies_move && dev.n_colliders > 0 && !(part == 2 && d->reduce_impulses == 2)) {
+            if (part == 2 && d->reduce_impulses == 1) {
+                wgs_status rst = allreduce_impulses(d);
+                if (rst != WGS_OK) return rst;
+            }
+            // Single-domain simulations without mesh colliders: left to the first launch of the next substep (or to the end of
+            // this wgs_step call, flush_bodies) — a 16-thread launch of its own costs a dependent launch, ~5 us, per substep.
+            // (not when this substep's G2P binned for the next one: that substep has no launch in front of the node cdfs of its sort)
+            if (part == 0 && !dev.sharded && dev.n_rigid == 0 && n > 0 && !(dev.dbg & DBG_BODIES_OWN_LAUNCH) && !dev.bin_next) d->sub.bodies_pending = true;
+            else hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, s, dev);
+        }
+        mark(8);
+        d->side ^= 1;
+        d->substeps++;
+        d->sub.prev_sorted = true;
+        d->sub.prebinned = dev.bin_next != 0u && dev.nv > 0;
+        dev.n = dev.nv;  // the buffer just written holds the valid particles only, in sorted order
+        // sharded: the counters of the new buffer (CTR_N / CTR_NPREV / CTR_NV) are set by k_g2p_arrivals; a slab stepped
+        // without its neighbours (wgs_step) sets them at the head of its next substep (k_shard_compacted)
+        if (dev.sharded && !arrivals) d->sub.needs_compact = true;
+    }
+    HIP_TRY(hipGetLastError());
+    return WGS_OK;
+}
+
+// integrate_bodies of a lockstep group (the group summed the impulses of its slabs after every slab's grid update)
+wgs_status enqueue_bodies(wgs_data *d) {
+    if (d->bodies_move && d->dev.n_colliders > 0) hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, d->stream, d->dev);
+    HIP_TRY(hipGetLastError());
+    return WGS_OK;
+}
+
+}  // namespace

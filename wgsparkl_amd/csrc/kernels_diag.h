@@ -1,8 +1,9 @@
 // kernels_diag.h — device-side diagnostics (include/wgsparkl_hip.h "Device-side diagnostics"): reproducible sums, bounds and a
 // state digest, reduced on the device. NEW: the reference reduces nothing on the device.
 //
-// Included by capi.hip AFTER every other kernel header and after the existing entry points (it uses capi.hip's unpack_slot +
-// fix_uniform, and the kernels of the step keep their place in the code object: DESIGN.md 9.7), followed by its two entry points.
+// Included by capi.hip AFTER every other kernel header and after the entry points of the step (it uses unpack_slot + fix_uniform
+// of kernels_readback.h, and the kernels of the step keep their place in the code object: DESIGN.md 9.7). Ends in diag_enqueue,
+// the launch sequence of one diagnostics call; its two entry points are in capi_debug.inc.
 //
 // Shape: a streaming pass over the particle quads of the current buffer (16-byte-per-lane loads, one SGPR base: layout.h ldq),
 // grid-stride, 256 threads; each lane keeps its partial results in registers, a wave combines them by a __shfl_xor ladder, the four
@@ -464,19 +465,13 @@ wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     if (what == 0u || (what & ~(uint32_t)(WGS_DIAG_PARTICLES | WGS_DIAG_ENERGY | WGS_DIAG_GRID | WGS_DIAG_DIGEST)))
         return fail(WGS_ERR_INVALID_ARGUMENT, "what: an OR of WGS_DIAG_*");
     if (what & WGS_DIAG_ENERGY) what |= WGS_DIAG_PARTICLES;
-    HIP_TRY(hipSetDevice(d->pipeline->device));
-    if (!d->diag_acc) {
-        DiagAcc *acc = nullptr;
-        const wgs_status st = dev_alloc(d, &acc, 1);
-        if (st != WGS_OK) return st;
-        d->diag_acc = acc;
-    }
-    DiagAcc *acc = static_cast<DiagAcc *>(d->diag_acc);
+    if (!d->diag_acc) WGS_TRY(dev_alloc(d, &d->diag_acc, 1));
+    DiagAcc *acc = d->diag_acc;
     if (d->dev.sharded) {   // (the particle counters of a slab live on the device, in the set of the substep's parity: wgs_shard_export)
         d->dev.ctr_set = (uint32_t)(d->substeps & 1u);
-        if (d->needs_compact) {
+        if (d->sub.needs_compact) {
             hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, d->stream, d->dev);
-            d->needs_compact = false;
+            d->sub.needs_compact = false;
         }
     }
     const bool part = what & WGS_DIAG_PARTICLES, energy = what & WGS_DIAG_ENERGY, digest = what & WGS_DIAG_DIGEST, grid = what & WGS_DIAG_GRID;
@@ -504,30 +499,3 @@ wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
 }
 
 }  // namespace
-
-extern "C" {
-
-wgs_status wgs_enqueue_diagnostics(wgs_data *d, uint32_t what, wgs_diagnostics *device_out) {
-    if (!d || !device_out) return fail(WGS_ERR_INVALID_ARGUMENT, "NULL argument");
-    return diag_enqueue(d, what, device_out);
-}
-
-wgs_status wgs_read_diagnostics(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
-    if (!d || !out) return fail(WGS_ERR_INVALID_ARGUMENT, "NULL argument");
-    HIP_TRY(hipSetDevice(d->pipeline->device));
-    if (!d->diag_out) {
-        wgs_diagnostics *p = nullptr;
-        const wgs_status st = dev_alloc(d, &p, 1);
-        if (st != WGS_OK) return st;
-        d->diag_out = p;
-    }
-    if (!d->diag_host) HIP_TRY(hipHostMalloc(&d->diag_host, sizeof(wgs_diagnostics), hipHostMallocDefault));
-    const wgs_status st = diag_enqueue(d, what, static_cast<wgs_diagnostics *>(d->diag_out));
-    if (st != WGS_OK) return st;
-    HIP_TRY(hipMemcpyAsync(d->diag_host, d->diag_out, sizeof(wgs_diagnostics), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    memcpy(out, d->diag_host, sizeof(wgs_diagnostics));
-    return WGS_OK;
-}
-
-}  // extern "C"
