@@ -125,7 +125,25 @@ typedef struct {
 
 /* Constitutive model (the reference picks at shader-compile time,
  * src/solver/particle_update.wgsl:7-8; default = corotated like the reference). */
-enum { WGS_MODEL_COROTATED = 0, WGS_MODEL_NEO_HOOKEAN = 1 };
+enum { WGS_MODEL_COROTATED = 0, WGS_MODEL_NEO_HOOKEAN = 1, WGS_MODEL_FLUID = 2 };
+/* WGS_MODEL_FLUID — weakly-compressible fluid: Tait pressure + Newtonian viscosity. NEW: the reference ships no fluid / equation of
+ * state. The only deformation state of a particle is its volume ratio J. Per particle and substep, with G = the velocity gradient
+ * G2P leaves in `affine` (src/solver/particle_update.wgsl:89-91), lambda, mu = the particle's wgs_elastic_coefficients REINTERPRETED
+ * (lambda = bulk modulus at rest, mu = dynamic viscosity), gamma = the Tait exponent of wgs_set_fluid_eos:
+ *     J'      = J * det(I + dt * G)                  the determinant of what F <- F + (G dt) F does to an isotropic F
+ *     Jc      = max(J', 1e-10)                       the clamp of src/models/neo_hookean_elasticity.wgsl:14-25
+ *     p       = (lambda / gamma) * (Jc^(-gamma) - 1) Tait; dp/dJ = -lambda at J = 1
+ *     tau     = -Jc * p * I + Jc * mu * (G + G^T)    Kirchhoff stress = J * Cauchy stress
+ *     affine' = G * m - tau * (V0 * inv_d * dt)      src/solver/particle_update.wgsl:129-132, unchanged
+ * Advection, the velocity clamp, the CPIC projection and the penalty impulse are those of the other models. To first order in J - 1
+ * the pressure term is the lambda ln J of the neo-Hookean model with mu = 0.
+ * def_grad of a fluid particle is NOT a deformation gradient: it is diag(J, 1[, 1]) — entry [0] holds J, the rest is the identity —,
+ * whose determinant is J exactly, so wgs_read_particles -> wgs_data_create -> wgs_set_constitutive_model(FLUID) restarts a run bit for
+ * bit and every diagnostic that takes det F works as it is. wgs_prep_vertex_buffer* draws a fluid particle with cbrt(J) I (2D: sqrt(J) I).
+ * Selecting the model is stream-ordered: it enqueues one small kernel that collapses the def_grad of every particle to
+ * diag(det F, 1[, 1]) (nothing changes where it has that form already); selecting another model afterwards needs nothing. On data
+ * whose step carries plastic state (Drucker-Prager particles, breakable phases, force_plastic) the call returns WGS_ERR_UNSUPPORTED
+ * and changes nothing. */
 
 /* The reference's 10 timestamped passes (src/pipeline.rs:201-271). The fused
  * G2P + particle update reports its time under WGS_PASS_G2P; in collider simulations
@@ -191,7 +209,9 @@ const char *wgs_build_info(void);
  * size field — wgs_get_stats writes sizeof(wgs_stats) of ITS header —, so a binding checks wgs_abi_version() == WGS_ABI_VERSION once,
  * after loading the library, and refuses to go on otherwise (include/wgsparkl_hip.hpp and wgsparkl_amd/_ffi.py do). History: 5 =
  * wgs_stats grew by block_ids .. table_refreshes (24 bytes); 6 = this function. New counters will come behind a call of their own.
- * 7 = wgs_read_diagnostics / wgs_enqueue_diagnostics and their structs (nothing that existed changed). */
+ * 7 = wgs_read_diagnostics / wgs_enqueue_diagnostics and their structs (nothing that existed changed). Still 7: WGS_MODEL_FLUID and
+ * wgs_set_fluid_eos were added without touching a struct, an enum value or a signature — a binding that must run against older
+ * libraries of version 7 detects wgs_set_fluid_eos by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -211,6 +231,10 @@ void wgs_data_destroy(wgs_data *data);
 
 /* Runtime replacement for the compile-time import at src/solver/particle_update.wgsl:7-8. */
 wgs_status wgs_set_constitutive_model(wgs_data *data, int32_t model);
+/* The Tait exponent of WGS_MODEL_FLUID (default 7), one value per wgs_data. Stream-ordered like the other setters: the substeps
+ * enqueued after the call use it. gamma must be finite and > 1, else WGS_ERR_INVALID_ARGUMENT; allowed under any model, read only
+ * by the fluid. */
+wgs_status wgs_set_fluid_eos(wgs_data *data, float gamma);
 
 /* MpmPipeline::queue_step + `for _ in 0..num_substeps { queue.encode(..) }` + submit
  * (src/pipeline.rs:195-281, src_testbed/step.rs:122-128,169): enqueues `num_substeps`
@@ -438,6 +462,8 @@ wgs_status wgs_sharded_step_lockstep(wgs_pipeline *pipeline, wgs_data **slabs, u
  *                               corotated   (src/models/linear_elasticity.wgsl:28-41)      Psi = mu * sum_i (s_i - 1)^2 + lambda / 2 * (J - 1)^2,
  *                               neo-Hookean (src/models/neo_hookean_elasticity.wgsl:14-25) Psi = mu / 2 * (tr F^T F - d) - mu * ln J + lambda / 2 * ln^2 J,
  *                                           J = max(det F, 1e-10) as there.
+ *                               fluid       (WGS_MODEL_FLUID; F = diag(J, 1[, 1]))          Psi = lambda / gamma * (Jc^(1-gamma) / (gamma - 1) + Jc - gamma / (gamma - 1)),
+ *                                           Jc = max(J, 1e-10): dPsi/dJ = -p, Psi(1) = 0. Viscous dissipation is not an energy and has no sum.
  *                             s_i = signed singular values (proper rotations, the sign of det F on the smallest). Evaluated through
  *                             G = F - I and E = G + G^T + G^T G = F^T F - I: s_i - 1 = e_i / (s_i + 1) for the eigenvalues e_i of E (fp64
  *                             cyclic Jacobi; the fp32 SVD of the step would lose (s_i - 1)^2 near the rest state), det F - 1 from the invariants of G.

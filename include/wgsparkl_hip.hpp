@@ -121,6 +121,8 @@ class MpmData {
     ~MpmData() { reset(); }
 
     void set_constitutive_model(int32_t model) { check(wgs_set_constitutive_model(h_, model)); }
+    // the Tait exponent of WGS_MODEL_FLUID (default 7; finite and > 1)
+    void set_fluid_eos(float gamma) { check(wgs_set_fluid_eos(h_, gamma)); }
     // device.poll(Maintain::Wait) (src/pipeline.rs:339); also reports device-side sticky errors (grid overflow, key range)
     void sync() { check(wgs_sync(h_)); }
     // the per-frame host -> device writes of src_testbed/step.rs:79-119 and ui.rs:91-104

@@ -218,6 +218,7 @@ extern "C" {
     ) -> wgs_status;
     pub fn wgs_data_destroy(d: *mut wgs_data);
     pub fn wgs_set_constitutive_model(d: *mut wgs_data, model: i32) -> wgs_status;
+    pub fn wgs_set_fluid_eos(d: *mut wgs_data, gamma: f32) -> wgs_status;
     pub fn wgs_step(p: *mut wgs_pipeline, d: *mut wgs_data, num_substeps: u32, timestamps: i32) -> wgs_status;
     pub fn wgs_sync(d: *mut wgs_data) -> wgs_status;
     pub fn wgs_set_sim_params(d: *mut wgs_data, params: *const wgs_sim_params) -> wgs_status;

@@ -1,4 +1,4 @@
-"""developer utility: a bench configuration with another constitutive model (0 corotated, 1 neo-Hookean), event-free wall time per substep.
+"""developer utility: a bench configuration with another constitutive model (0 corotated, 1 neo-Hookean, 2 Tait fluid: lambda read as the bulk modulus, mu as the viscosity), event-free wall time per substep.
 usage: gpu_model_time.py c3 1 [substeps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

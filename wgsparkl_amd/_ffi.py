@@ -29,6 +29,8 @@ EXPORTS = (
     "wgs_sharded_step_lockstep", "wgs_build_info", "wgs_abi_version", "wgs_debug_scan", "wgs_set_grid_growth", "wgs_set_uniform_material",
     # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
     "wgs_read_diagnostics", "wgs_enqueue_diagnostics",
+    # WGS_MODEL_FLUID: the Tait exponent (same ABI version: older libraries of version 7 lack the symbol)
+    "wgs_set_fluid_eos",
 )
 
 
@@ -168,6 +170,7 @@ def load(dim: int):
     lib.wgs_data_destroy.argtypes = [vp]
     lib.wgs_data_destroy.restype = None
     lib.wgs_set_constitutive_model.argtypes = [vp, C.c_int32]
+    lib.wgs_set_fluid_eos.argtypes = [vp, C.c_float]
     lib.wgs_step.argtypes = [vp, vp, C.c_uint32, C.c_int32]
     lib.wgs_sync.argtypes = [vp]
     lib.wgs_set_sim_params.argtypes = [vp, C.POINTER(T.SimParams)]

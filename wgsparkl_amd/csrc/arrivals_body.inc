@@ -259,12 +259,14 @@
 #pragma unroll
                 for (int k = 0; k < D; k++) vel[k] += imp * nrm[k];
             }
-            float gdt[DD], prod[DD];
+            if constexpr (MODEL != 2) {   // (the fluid keeps J alone, in F[0]: fluid_update below)
+                float gdt[DD], prod[DD];
 #pragma unroll
-            for (int k = 0; k < DD; k++) gdt[k] = grad[k] * dt;
-            mat_mul<D>(gdt, Fm, prod);
+                for (int k = 0; k < DD; k++) gdt[k] = grad[k] * dt;
+                mat_mul<D>(gdt, Fm, prod);
 #pragma unroll
-            for (int k = 0; k < DD; k++) Fm[k] += prod[k];
+                for (int k = 0; k < DD; k++) Fm[k] += prod[k];
+            }
             float tau[DD];
             Svd<D> sv;
             if constexpr (PLASTIC) {
@@ -284,7 +286,9 @@
                 stq(out, npad, P::DP1, j, make_float4(dp[4], dp[5], st[0], st[1]));
                 stq(out, npad, P::DP2, j, make_float4(st[2], phase, max_stretch, 0.f));
             }
-            if constexpr (MODEL == 1) {
+            if constexpr (MODEL == 2) {
+                Fm[0] = fluid_update<D>(lambda, mu, d.fluid_gamma, grad, dt, Fm[0], tau);
+            } else if constexpr (MODEL == 1) {
                 kirchoff_neo_hookean<D>(lambda, mu, Fm, tau);
             } else {
                 if constexpr (!PLASTIC) svd<D>(Fm, sv);

@@ -45,3 +45,4 @@ using namespace wgs;
 #include "capi_sharded.inc"      // extern "C": communicators, wgs_shard_attach, the sharded steps
 #include "kernels_diag.h"        // device-side diagnostics and their launch sequence
 #include "capi_debug.inc"        // extern "C": diagnostics, test hooks, WGS_ABLATE profile readers
+#include "kernels_fluid.h"       // WGS_MODEL_FLUID: the kernel of the model switch (last: nothing that existed changes its place)

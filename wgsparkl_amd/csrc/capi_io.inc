@@ -3,6 +3,10 @@
 // timings and stats. Every reader that needs a staging buffer takes a Scratch and ends in download(); the kernels they
 // launch are in kernels_readback.h / kernels_shard.h.
 
+namespace {
+__global__ void k_fluid_collapse(Dev d, int side);   // kernels_fluid.h (defined behind every other kernel: capi.hip on placement)
+}
+
 extern "C" {
 
 wgs_status wgs_set_uniform_material(wgs_data *d, float mass, float init_volume, float lambda, float mu) {
@@ -28,8 +32,24 @@ wgs_status wgs_set_grid_growth(wgs_data *d, int32_t enabled) {
 
 wgs_status wgs_set_constitutive_model(wgs_data *d, int32_t model) {
     if (!d) return fail(WGS_ERR_INVALID_ARGUMENT, "data is NULL");
-    if (model != WGS_MODEL_COROTATED && model != WGS_MODEL_NEO_HOOKEAN) return fail(WGS_ERR_INVALID_ARGUMENT, "unknown model");
+    if (model != WGS_MODEL_COROTATED && model != WGS_MODEL_NEO_HOOKEAN && model != WGS_MODEL_FLUID) return fail(WGS_ERR_INVALID_ARGUMENT, "unknown model");
+    if (model == WGS_MODEL_FLUID) {
+        // (only the instantiations without plastic state exist for the fluid: host_substep.inc launch_g2p)
+        if (d->plastic) return fail(WGS_ERR_UNSUPPORTED, "WGS_MODEL_FLUID: this data's step carries plastic state (Drucker-Prager particles, phases or force_plastic)");
+        // the F quads of the current buffer -> diag(det F, 1[, 1]), stream-ordered (kernels_fluid.h; the identity on values already in that
+        // form). Switching away needs nothing: diag(J, 1, 1) is a deformation gradient of that volume ratio.
+        WGS_TRY(enter(d));
+        if (d->dev.n) hipLaunchKernelGGL(k_fluid_collapse, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side);
+        HIP_TRY(hipGetLastError());
+    }
     d->dev.model = model;
+    return WGS_OK;
+}
+
+wgs_status wgs_set_fluid_eos(wgs_data *d, float gamma) {
+    if (!d) return fail(WGS_ERR_INVALID_ARGUMENT, "data is NULL");
+    if (!(gamma > 1.0f) || !std::isfinite(gamma)) return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_set_fluid_eos: gamma must be finite and > 1");
+    d->dev.fluid_gamma = gamma;   // (a kernel argument: the substeps enqueued from here on see it)
     return WGS_OK;
 }
 

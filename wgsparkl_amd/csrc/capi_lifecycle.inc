@@ -102,6 +102,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
         dev.h_pow2 = (frexpf(cell_width, &e) == 0.5f) ? 1u : 0u;
     }
     dev.model = WGS_MODEL_COROTATED;
+    dev.fluid_gamma = 7.0f;   // (wgs_set_fluid_eos)
     // developer switches (layout.h DebugSwitch), read once, here; 0 in production
     dev.dbg = getenv("WGS_DEBUG") ? (uint32_t)strtoul(getenv("WGS_DEBUG"), nullptr, 0) : 0u;
     if (getenv("WGS_REHASH_PERIOD")) d->rehash_period = std::max(1u, (uint32_t)strtoul(getenv("WGS_REHASH_PERIOD"), nullptr, 0));  // same results

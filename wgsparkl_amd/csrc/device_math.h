@@ -521,6 +521,45 @@ template <int D> __device__ inline void kirchoff_corotated(float lambda, float m
     for (int k = 0; k < D; k++) tau[k * D + k] += diag;
 }
 
+// Weakly-compressible (Tait) fluid, WGS_MODEL_FLUID. NEW: the reference ships no fluid / equation of state;
+// the formulae are those of include/wgsparkl_hip.h. The only deformation state is the volume ratio J.
+// Jc^(-gamma) - 1, the ONE place that raises J to the Tait exponent (every kernel variant calls it: the variants stay
+// bit-identical). Through expm1 of -gamma ln Jc: near the rest state the pressure is the small difference of Jc^(-gamma) and 1,
+// and the direct power would round that difference to 6e-8 absolute before the bulk modulus multiplies it.
+__device__ inline float tait_pow_minus_one(float jc, float gamma) { return expm1f(-gamma * logf(jc)); }
+
+// det(I + A) - 1 from the invariants of A (tr A + second invariant + det A): A = G dt is small, and the determinant of I + A
+// formed directly would carry the rounding of 1 + tr A
+template <int D> __device__ inline float det_one_plus_minus_one(const float *a) {
+    if constexpr (D == 2) {
+        return (a[0] + a[3]) + (a[0] * a[3] - a[2] * a[1]);
+    } else {
+        const float tr = (a[0] + a[4]) + a[8];
+        const float i2 = ((a[0] * a[4] - a[3] * a[1]) + (a[0] * a[8] - a[6] * a[2])) + (a[4] * a[8] - a[7] * a[5]);
+        return (tr + i2) + mat_det<D>(a);
+    }
+}
+
+// One particle update of the fluid: J' = J det(I + dt G), Jc = max(J', 1e-10) (the clamp of neo_hookean_elasticity.wgsl:14-25),
+// p = lambda / gamma (Jc^-gamma - 1), tau = -Jc p I + Jc mu (G + G^T). `lambda` = bulk modulus at rest, `mu` = dynamic
+// viscosity. Returns J'; `grad` is column-major like every matrix here.
+template <int D> __device__ inline float fluid_update(float lambda, float mu, float gamma, const float *grad, float dt, float j, float *tau) {
+    float gdt[D * D];
+#pragma unroll
+    for (int k = 0; k < D * D; k++) gdt[k] = grad[k] * dt;
+    const float jn = fmaf(j, det_one_plus_minus_one<D>(gdt), j);
+    const float jc = fmaxf(jn, 1.0e-10f);
+    const float p = (lambda / gamma) * tait_pow_minus_one(jc, gamma);
+    const float jmu = jc * mu, diag = -(jc * p);
+#pragma unroll
+    for (int c = 0; c < D; c++)
+#pragma unroll
+        for (int r = 0; r < D; r++) tau[c * D + r] = jmu * (grad[c * D + r] + grad[r * D + c]);
+#pragma unroll
+    for (int k = 0; k < D; k++) tau[k * D + k] += diag;
+    return jn;
+}
+
 // models/drucker_prager.wgsl:25-29
 __device__ inline float dp_alpha(const float *dp, float q) {
     float angle = dp[0] + (dp[1] * q - dp[3]) * expf(-dp[2] * q);

@@ -598,13 +598,15 @@
                         for (int k = 0; k < D; k++) vel[k] += imp * nrm[k];
                     }
                 }
-                // F <- F + (grad * dt) * F
-                float gdt[DD], prod[DD];
+                // F <- F + (grad * dt) * F   (the fluid keeps J alone, in F[0]: fluid_update below)
+                if constexpr (MODEL != 2) {
+                    float gdt[DD], prod[DD];
     #pragma unroll
-                for (int k = 0; k < DD; k++) gdt[k] = grad[k] * dt;
-                mat_mul<D>(gdt, Fm, prod);
+                    for (int k = 0; k < DD; k++) gdt[k] = grad[k] * dt;
+                    mat_mul<D>(gdt, Fm, prod);
     #pragma unroll
-                for (int k = 0; k < DD; k++) Fm[k] += prod[k];
+                    for (int k = 0; k < DD; k++) Fm[k] += prod[k];
+                }
 
                 float tau[DD];
                 Svd<D> sv;
@@ -651,7 +653,10 @@
                         stq(out, npad, P::DP2, j, make_float4(st[2], phase, max_stretch, 0.f));
                     }
                 }
-                if constexpr (MODEL == 1) {
+                if constexpr (MODEL == 2) {
+                    static_assert(MODEL != 2 || !PLASTIC, "the fluid carries no plastic state");
+                    Fm[0] = fluid_update<D>(lambda, mu, d.fluid_gamma, grad, dt, Fm[0], tau);   // def_grad = diag(J, 1[, 1]): layout.h
+                } else if constexpr (MODEL == 1) {
                     kirchoff_neo_hookean<D>(lambda, mu, Fm, tau);
                 } else {
                     if constexpr (!PLASTIC) svd<D>(Fm, sv);

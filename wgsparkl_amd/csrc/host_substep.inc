@@ -172,20 +172,24 @@ void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, c
 
 // the fused G2P; `mark(6)` between the two launches of that shape
 template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
-    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+    // (the fluid exists without plastic state only — wgs_set_constitutive_model refuses it on such data — and comes last: the
+    // instantiations of the other models keep their places in the code object)
+    switch (dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
         case 0: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
         case 1: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
         case 2: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
-        default: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
+        case 3: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
+        default: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
     }
 }
 
 template <int DIM> void launch_arrivals(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, bool plastic) {
-    switch ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0)) {
+    switch (dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
         case 0: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, false>), g, dim3(256), 0, s, dev, side, epoch); break;
         case 1: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, true>), g, dim3(256), 0, s, dev, side, epoch); break;
         case 2: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, false>), g, dim3(256), 0, s, dev, side, epoch); break;
-        default: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case 3: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+        default: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 2, false>), g, dim3(256), 0, s, dev, side, epoch); break;
     }
 }
 

@@ -106,7 +106,7 @@ __device__ inline void diag_sym_eigenvalues(double e[D][D], double *ev) {
 }
 
 // Psi(F) of the header in fp64, through G = F - I (exact for an fp32 F) and E = G + G^T + G^T G
-__device__ inline double diag_psi(int model, double lambda, double mu, const float *F) {
+__device__ inline double diag_psi(int model, double lambda, double mu, double gamma, const float *F) {
     double g[D][D], e[D][D];   // [row][column]; F is column-major
     for (int c = 0; c < D; c++)
         for (int r = 0; r < D; r++) g[r][c] = (double)F[c * D + r] - (r == c ? 1.0 : 0.0);
@@ -127,6 +127,14 @@ __device__ inline double diag_psi(int model, double lambda, double mu, const flo
                g[0][2] * (g[1][0] * g[2][1] - g[1][1] * g[2][0]);
     }
     const double jm1 = (tr + i2) + detg;
+    if (model == WGS_MODEL_FLUID) {
+        // (lambda / gamma) (Jc^(1-gamma) / (gamma-1) + Jc - gamma / (gamma-1)), as ((Jc^(1-gamma) - 1) / (gamma-1) + (Jc - 1)): both terms are
+        // O(J - 1) with opposite signs near the rest state, and each is formed from ln Jc = log1p(J - 1) without rounding 1 + (J - 1) first
+        const bool clamped = !(1.0 + jm1 >= 1.0e-10);
+        const double lnj = clamped ? log(1.0e-10) : log1p(jm1);
+        const double jcm1 = clamped ? 1.0e-10 - 1.0 : jm1;
+        return (lambda / gamma) * (expm1((1.0 - gamma) * lnj) / (gamma - 1.0) + jcm1);
+    }
     if (model == WGS_MODEL_NEO_HOOKEAN) {
         double tre = 0.0;
         for (int k = 0; k < D; k++) tre += e[k][k];
@@ -156,7 +164,7 @@ __device__ inline bool diag_finite(const Unpacked &u) {
 }
 
 // the terms of the particle sums (header), in fp64
-template <bool ENERGY> __device__ inline void diag_particle_terms(const Unpacked &u, double h2q, const double *grav, int model, double *t) {
+template <bool ENERGY> __device__ inline void diag_particle_terms(const Unpacked &u, double h2q, const double *grav, int model, double gamma, double *t) {
     const double m = u.mass;
     double x[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < D; k++) { x[k] = u.x[k]; v[k] = u.v[k]; }
@@ -183,7 +191,7 @@ template <bool ENERGY> __device__ inline void diag_particle_terms(const Unpacked
     t[WGS_SUM_KINETIC_AFFINE] = m != 0.0 ? 0.5 * h2q * aa / m : 0.0;
     t[WGS_SUM_GRAVITY_POTENTIAL] = -(m * gx);
     t[WGS_SUM_ELASTIC] = 0.0;
-    if constexpr (ENERGY) t[WGS_SUM_ELASTIC] = (double)u.vol * diag_psi(model, (double)u.lam, (double)u.mu, u.F);
+    if constexpr (ENERGY) t[WGS_SUM_ELASTIC] = (double)u.vol * diag_psi(model, (double)u.lam, (double)u.mu, gamma, u.F);
 }
 
 __device__ inline double diag_det(const float *F) {
@@ -252,7 +260,7 @@ __global__ __launch_bounds__(256) void k_diag_pass1(Dev d, int side, bool plasti
         if constexpr (PART) {
             if (!diag_finite(u)) { add[DA_NONFINITE]++; continue; }
             double t[DIAG_PARTICLE_SUMS];
-            diag_particle_terms<ENERGY>(u, h2q, grav, d.model, t);
+            diag_particle_terms<ENERGY>(u, h2q, grav, d.model, (double)d.fluid_gamma, t);
 #pragma unroll
             for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) {
                 const unsigned long long b = diag_abs_bits(t[s]);
@@ -327,7 +335,7 @@ template <bool ENERGY> __global__ __launch_bounds__(256) void k_diag_pass2(Dev d
         fix_uniform<D>(d, u);
         if (!diag_finite(u)) continue;
         double t[DIAG_PARTICLE_SUMS];
-        diag_particle_terms<ENERGY>(u, h2q, grav, d.model, t);
+        diag_particle_terms<ENERGY>(u, h2q, grav, d.model, (double)d.fluid_gamma, t);
 #pragma unroll
         for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) fixed[s] += (unsigned long long)__double2ll_rn(t[s] * scale[diag_group_of(s)]);
     }

@@ -293,6 +293,11 @@ struct Dev {
     float uni_dpv[6], uni_max_stretch;
     int model;           // WGS_MODEL_*
     uint32_t dbg;        // developer switches DBG_* below (env WGS_DEBUG, read once at creation), 0 in production
+    // WGS_MODEL_FLUID: the Tait exponent (wgs_set_fluid_eos; read by the fluid instantiations only). Under that model the F quads of a
+    // particle do not hold a deformation gradient: F = diag(J, 1[, 1]), the volume ratio in F[0] and the identity elsewhere, in every
+    // layout (mat_det of it is J exactly, so read-back, diagnostics, digest and checkpoint restore work as they are). k_fluid_collapse
+    // (kernels_readback.h) brings a buffer into that form when the model is selected.
+    float fluid_gamma;
 };
 
 // WGS_DEBUG: developer switches, one bit each. A launch-shape switch brings back an alternative launch shape that must give

@@ -16,6 +16,7 @@ F32 = np.float32
 # src/solver/particle_update.wgsl:7-8; here it is a runtime per-MpmData choice).
 MODEL_COROTATED = 0      # models/linear_elasticity.wgsl (reference default)
 MODEL_NEO_HOOKEAN = 1    # models/neo_hookean_elasticity.wgsl
+MODEL_FLUID = 2          # weakly-compressible Tait fluid + viscosity (no reference counterpart; include/wgsparkl_hip.h WGS_MODEL_FLUID)
 
 
 def lame_lambda_mu(young_modulus: float, poisson_ratio: float):
@@ -39,6 +40,26 @@ class ElasticCoefficients:
     def from_young_modulus(young_modulus: float, poisson_ratio: float) -> "ElasticCoefficients":
         lam, mu = lame_lambda_mu(young_modulus, poisson_ratio)
         return ElasticCoefficients(float(lam), float(mu))
+
+
+@dataclass(frozen=True)
+class FluidCoefficients:
+    """Material of MODEL_FLUID: the two slots of ElasticCoefficients reinterpreted — `lambda_` carries the bulk modulus at rest,
+    `mu` the dynamic viscosity (include/wgsparkl_hip.h WGS_MODEL_FLUID). Usable wherever ElasticCoefficients is."""
+    bulk_modulus: float
+    viscosity: float = 0.0
+
+    @property
+    def lambda_(self) -> float:
+        return float(self.bulk_modulus)
+
+    @property
+    def mu(self) -> float:
+        return float(self.viscosity)
+
+    def arrays(self, n: int):
+        """(lambda_, mu) as float32 arrays of n particles."""
+        return np.full(n, self.bulk_modulus, F32), np.full(n, self.viscosity, F32)
 
 
 @dataclass(frozen=True)

@@ -272,6 +272,10 @@ class MpmData:
     def set_constitutive_model(self, model: int):
         _ffi.check(self.lib, self.lib.wgs_set_constitutive_model(self._h, int(model)))
 
+    def set_fluid_eos(self, gamma: float):
+        """`wgs_set_fluid_eos`: the Tait exponent of MODEL_FLUID (default 7; finite and > 1). Stream-ordered."""
+        _ffi.check(self.lib, self.lib.wgs_set_fluid_eos(self._h, float(gamma)))
+
     def set_sim_params(self, params: SimulationParams):
         sp = self.T.SimParams()
         sp.gravity = (C.c_float * self.dim)(*params.gravity)

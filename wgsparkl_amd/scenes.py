@@ -9,8 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager,
-                     ElasticCoefficients, ParticlePhase)
+from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, DruckerPrager,
+                     ElasticCoefficients, FluidCoefficients, ParticlePhase)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -291,6 +291,34 @@ def fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, cell_wi
     return dict(particles=ps, global_ids=gid, partition=part,
                 params=SimulationParams(gravity=(0.0, -9.81, 0.0), dt=1.0 / 1200.0), colliders=colliders,
                 cell_width=h, grid_capacity=grid_capacity, model=MODEL_NEO_HOOKEAN, global_particles=nx * ny * nz)
+
+
+def tait_fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, cell_width=1.0, with_floor=True,
+                     density=1000.0, bulk_modulus=1.0e7, viscosity=0.0, gamma=7.0, grid_capacity=None):
+    """The lattice of `fluid_block` under MODEL_FLUID: Tait pressure with bulk modulus `bulk_modulus` and exponent `gamma`
+    (scene key "fluid_gamma": MpmData.set_fluid_eos), dynamic viscosity `viscosity`. Same particles, ids and slabs as
+    `fluid_block` for the same arguments; to first order in J - 1 the same pressure."""
+    sc = fluid_block(nx, ny, nz, world=world, rank=rank, jitter=jitter, cell_width=cell_width, with_floor=with_floor,
+                     density=density, bulk_modulus=bulk_modulus, grid_capacity=grid_capacity)
+    ps = sc["particles"]
+    ps.lambda_[:], ps.mu[:] = FluidCoefficients(bulk_modulus, viscosity).arrays(ps.n)
+    sc["model"] = MODEL_FLUID
+    sc["fluid_gamma"] = float(gamma)
+    return sc
+
+
+def dam_break(nx=24, ny=40, nz=16, jitter=0.05, cell_width=1.0, density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0):
+    """Small dam break for tests: a column of Tait fluid (MODEL_FLUID) standing on the floor cuboid, one face against a wall
+    cuboid, free to collapse along +x. Both colliders are within reach of the column from the first substep, so the
+    near-collider list walk and the CPIC paths of the fused G2P advance fluid particles at once."""
+    h = cell_width
+    origin = (8.3 * h, 2.2 * h, 8.0 * h)                       # floor top at y = 2 h, wall face at x = 8 h
+    pos = lattice((nx, ny, nz), origin, h, jitter)
+    ps = ParticleSet.uniform(pos, h / 4.0, density, FluidCoefficients(bulk_modulus, viscosity), phase=ParticlePhase(1.0, FLT_MAX))
+    colliders = [Collider.cuboid((1000.0 * h, 2.0 * h, 1000.0 * h), (0.0, 0.0, 0.0)),
+                 Collider.cuboid((2.0 * h, 1000.0 * h, 1000.0 * h), (6.0 * h, 0.0, 0.0))]
+    return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0), dt=1.0 / 1200.0), colliders=colliders,
+                cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma))
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):

@@ -169,6 +169,10 @@ class NativeShard:
         self.part_rec = self.lib.wgs_shard_particle_record_bytes() // 4
         self.hdr = self.lib.wgs_shard_buffer_header_bytes() // 4
 
+    def set_fluid_eos(self, gamma: float):
+        """`wgs_set_fluid_eos` (every rank passes the same value)."""
+        _ffi.check(self.lib, self.lib.wgs_set_fluid_eos(self._h, float(gamma)))
+
     def step(self, num_substeps: int):
         """`wgs_sharded_step`: whole substeps incl. the neighbour exchange, asynchronous."""
         _ffi.check(self.lib, self.lib.wgs_sharded_step(self.pipeline._h, self._h, int(num_substeps)))
