@@ -1,0 +1,319 @@
+"""-m gpu: the collider distance fields checked node by node and particle by particle against the fp64 truth of
+tests/cdf_truth.py (closed-form signed distances; its bounds are settled on the CPU by tests/test_cdf_truth.py).
+
+Every checked substep: the particles' positions and previous affinity words and the collider poses are those read before
+it (bodies integrate at the end of a substep); after it the active cells are exactly those of the positions, every node's
+affinity / sign bits and closest id are exact outside the undecided set and its distance is within its bound, nodes with
+no voter hold exactly (1e10, NONE, 0); every particle's cdf_affinity is exact when decided and its cdf_dist / cdf_normal
+are within their bounds, twice: from the kernel's own read-back node field (isolated) and from the truth's (end to end).
+Every run asserts the caps on its undecided shares."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+import cdf_truth as CT
+import transfer_truth as T
+from gpu_common import _native_slabs, check_blocks
+from helpers import debug_switches, pipeline, report_margin, run_oracle
+from wgsparkl_amd import MpmData
+from wgsparkl_amd.solver import Collider
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(name, d, h) for name in CT.SCENES for d in (2, 3) for h in CT.HS]
+
+
+def _new(sc):
+    ps = sc["particles"]
+    return MpmData.new(pipeline(ps.dim), sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+
+
+def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None):
+    """one substep of `data`, checked; `first`: the uploaded state is the state before it (else it is read back)"""
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    if first:
+        pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
+    else:
+        before = data.read_particles()
+        pos, prev = before.pos, before.cdf_affinity
+    poses = data.read_body_poses()
+    pipeline(d).step(data, 1)
+    data.sync()
+    cells, _, dist, aff, closest = data.read_grid()
+    assert np.array_equal(cells, CT.active_cells(pos, h, d)), f"{tag}: the active cells are not those of the positions"
+    nf = CT.NodeField(CT.colliders_of(colliders or sc["colliders"], d, poses), d, h, cells)
+    CT.check_nodes(f"{tag} nodes", nf, dist, aff, closest, fails)
+    got = data.read_particles()
+    iso = CT.ParticleField(pos, h, cells, dist, aff, prev)
+    CT.check_particle_cdf(f"{tag} isolated", iso, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
+    e2e = CT.from_truth_nodes(pos, h, nf, prev)
+    CT.check_particle_cdf(f"{tag} end to end", e2e, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
+    CT.assert_caps(tag, nf, e2e, part_cap)
+    return nf, e2e, got
+
+
+@pytest.mark.parametrize("name,d,h", CASES)
+def test_shapes_and_poses_one_substep(hip_libs, name, d, h):
+    i = CASES.index((name, d, h))
+    sc = CT.SCENES[name](d, h, uniform=i % 2 == 1)          # (the two layouts alternate)
+    if name == "sixteen":
+        # the library refuses a 17th coupled collider outright (the C oracle and the truth ignore it: test_cdf_truth.py);
+        # what runs here is all 16 slots in use
+        from wgsparkl_amd._ffi import WgsError
+        with pytest.raises(WgsError):
+            _new(sc)
+        sc["colliders"] = sc["colliders"][:16]
+    data = _new(sc)
+    fails = []
+    nf, pf, got = _checked_substep(f"{name} {d}D h={h}", sc, data, fails, first=True)
+    check_blocks(data, run_oracle(sc, 1, np.float32))
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_far_node_field_at_the_full_distance_for_h_02(hip_libs, d):
+    """h = 0.2 at the full distance of the far scene: the node field alone (there the particle caps cannot hold)"""
+    h = 0.2
+    sc = CT.far_nodes(d, h)
+    data = _new(sc)
+    pipeline(d).step(data, 1)
+    data.sync()
+    cells, _, dist, aff, closest = data.read_grid()
+    assert np.array_equal(cells, CT.active_cells(sc["particles"].pos, h, d))
+    nf = CT.NodeField(CT.colliders_of(sc["colliders"], d), d, h, cells)
+    fails = []
+    un, cn = CT.check_nodes(f"far nodes {d}D h={h}", nf, dist, aff, closest, fails)
+    report_margin(f"far nodes {d}D h={h}: undecided share of the nodes that carry an affinity", un / cn, CT.NODE_CAP, count=un, of=cn)
+    assert un <= CT.NODE_CAP * cn
+    assert not fails, "\n".join(fails)
+
+
+def _far_mesh(sc):
+    """the scene plus a small mesh collider more than 4 blocks from every particle"""
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    at = tuple(float(np.float32(v)) for v in ps.pos.max(0) + 7 * T.bw_of(d) * h)
+    if d == 3:
+        v = np.array([[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 1]], np.float32) * np.float32(2 * h)
+        mesh = Collider.trimesh(v, np.array([[0, 1, 2], [2, 1, 3]]), at)
+    else:
+        v = np.array([[0, 0], [1, 0.2], [2, 0]], np.float32) * np.float32(2 * h)
+        mesh = Collider.polyline(v, np.array([[0, 1], [1, 2]]), at)
+    out = dict(sc)
+    out["colliders"] = list(sc["colliders"]) + [mesh]
+    return out
+
+
+@pytest.mark.parametrize("d", [2, 3])
+@pytest.mark.parametrize("path", ["summaries", "no_summaries", "k_cdf"])
+def test_each_node_field_path_agrees_with_the_truth(hip_libs, monkeypatch, path, d):
+    """k_regroup with the node-cdf summaries shared between blocks (the default), without them (NO_CDF_SUMM), and k_cdf
+    (a mesh collider exists; it lies out of reach and contributes no bit)"""
+    h = 0.5
+    sc = CT.two_equal(d, h)
+    if path == "k_cdf":
+        sc = _far_mesh(sc)
+    if path == "no_summaries":
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_CDF_SUMM"))
+    data = _new(sc)
+    monkeypatch.delenv("WGS_DEBUG", raising=False)
+    fails = []
+    nf, pf, got = _checked_substep(f"node field path {path} {d}D", sc, data, fails, first=True)
+    if path == "k_cdf":
+        bit = np.uint32(0x10001 << (len(sc["colliders"]) - 1))
+        _, _, _, aff, _ = data.read_grid()
+        assert not (aff & bit).any() and not (got.cdf_affinity & bit).any(), "the mesh collider left a bit"
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.parametrize("d", [2, 3])
+@pytest.mark.parametrize("path", ["prologue_waves", "cpic_workgroups"])
+def test_each_particle_field_path_agrees_with_the_truth(hip_libs, monkeypatch, path, d):
+    """the particle cdf in the prologue waves of the P2G launch (the host has seen the visit list), and inside the CPIC
+    workgroups (NO_PCDF_WAVES)"""
+    h = 0.5
+    sc = CT.capsule(d, h)
+    if path == "cpic_workgroups":
+        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_PCDF_WAVES"))
+    data = _new(sc)
+    monkeypatch.delenv("WGS_DEBUG", raising=False)
+    pipeline(d).step(data, 1)
+    data.sync()
+    fails = []
+    _checked_substep(f"particle field path {path} {d}D", sc, data, fails, first=False)
+    n_near = data.stats()["num_near_collider_blocks"]
+    report_margin(f"particle field path {path} {d}D: near-collider blocks", n_near, 0)
+    assert n_near > 0, "no near-collider block: the prologue-waves path was not reached"
+    assert not fails, "\n".join(fails)
+
+
+def _blocks_in_reach(nf, col, d):
+    return set(map(tuple, np.unique(nf.cells[nf.voter[:, col]] // T.bw_of(d), axis=0).tolist()))
+
+
+def _ball_scene(d, h, ball_x=None):
+    """a fixed floor under a bed of particles 6 blocks long, and a kinematic ball above it moving along x at 0.4 h per substep
+    (centre x = ball_x, in h; default 1.5 h into the third block)"""
+    bw = T.bw_of(d)
+    rng = np.random.default_rng(40 + d)
+    floor = Collider.cuboid(CT._v(np.array([3.2 * bw, 1.0, 3.0 * bw]) * h, d), CT._v(np.array([3.0 * bw + 0.13, bw - 0.8, 1.5 * bw + 0.21]) * h, d),
+                            rotation=(0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0))
+    # (the ball stays 1.6 h clear of the bed: no node inside it receives mass, so it takes no impulse, and its velocity is
+    # not limited to 0.1 h / dt as that of a body in contact is)
+    ball = Collider.ball(float(np.float32(1.5 * h)), CT._v(np.array([2 * bw + 1.5 if ball_x is None else ball_x, 2 * bw + 6.13, 1.5 * bw + 0.27]) * h, d),
+                         linvel=(float(np.float32(0.4 * h / T.DT)), 0.0, 0.0))
+    lo, hi = np.array([1.0, bw + 0.5, bw + 0.5]) * h, np.array([6 * bw - 1.0, 2 * bw + 3.0, 2 * bw + 2.5]) * h
+    sc = CT._static(d, h, rng, [floor, ball], [(lo, hi)], 3000 if d == 3 else 1500, rim_keep=1.0)
+    return sc, floor, ball
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_kept_node_cdfs_follow_a_moving_ball_and_a_moved_floor(hip_libs, d):
+    """A fixed floor under a bed of particles 6 blocks long, a kinematic ball travelling along it at 0.4 h per substep:
+    the node cdfs of blocks out of the ball's reach are kept from the previous substep, those of the blocks that enter
+    or leave its reach must be rebuilt. Then the floor moves by 0.37 h (set_colliders): every kept field is stale."""
+    h = 0.2
+    sc, floor, ball = _ball_scene(d, h)
+    data = _new(sc)
+    fails = []
+    entered, left, reach = set(), set(), None
+    for k in range(12):
+        nf, _, _ = _checked_substep(f"moving ball {d}D substep {k}", sc, data, fails, first=k == 0)
+        now = _blocks_in_reach(nf, 1, d)
+        if reach is not None:
+            entered |= now - reach
+            left |= reach - now
+        reach = now
+    report_margin(f"moving ball {d}D: blocks that entered the ball's reach", len(entered), 2)
+    report_margin(f"moving ball {d}D: blocks that left the ball's reach", len(left), 2)
+    poses = data.read_body_poses()
+    moved = [dataclasses.replace(floor, translation=CT._v(np.asarray(floor.translation) + np.array([0.0, 0.37 * h, 0.0])[:d], d)),
+             dataclasses.replace(ball, translation=tuple(float(v) for v in poses[1]["translation"]))]
+    data.set_colliders(moved)
+    _checked_substep(f"moving ball {d}D after the floor moved", sc, data, fails, first=False, colliders=moved)
+    assert not fails, "\n".join(fails)
+    assert len(entered) >= 2 and len(left) >= 2, (len(entered), len(left))
+
+
+def _export_cdf(shard):
+    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds: the exchange
+    records carry every quad of the particle and the substep its cdf was computed in"""
+    import ctypes as C
+    import torch
+    D = shard.dim
+    buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
+    torch.cuda.current_stream(buf.device).synchronize()
+    cnt = C.c_uint32(0)
+    from wgsparkl_amd import _ffi
+    _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
+    rec = buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
+    ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
+    q = lambda k: rec[:, 4 * k:4 * k + 4]
+    if D == 3:
+        return ids, q(0)[:, :3].copy(), q(11)[:, 3].copy().view(np.uint32), q(10)[:, 3].copy(), q(10)[:, :3].copy(), stamp
+    return ids, q(0)[:, :2].copy(), q(7)[:, 3].copy().view(np.uint32), q(7)[:, 2].copy(), q(7)[:, :2].copy(), stamp
+
+
+def _export_all(shards, n, d):
+    """the particles of all slabs in the order of their global ids; a cdf whose stamp is not the newest is the default one"""
+    parts = [_export_cdf(s) for s in shards]
+    ids = np.concatenate([p[0] for p in parts]).astype(np.int64)
+    assert np.array_equal(np.sort(ids), np.arange(n)), "every particle exactly once"
+    order = np.argsort(ids)
+    pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
+    live = stamp == stamp.max()
+    return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_lockstep_slabs_of_the_moving_ball_scene(hip_libs, d):
+    """The moving-ball scene as two lockstep slabs, 4 substeps: the ball's reach starts 0.7 h short of the cut and crosses
+    it. Every particle against the truth of the whole domain; the nodes of each slab's own blocks against the truth
+    restricted to them."""
+    from wgsparkl_amd.sharded import native_lockstep
+    h = 0.2
+    bw = T.bw_of(d)
+    sc, _, _ = _ball_scene(d, h)
+    ps = sc["particles"]
+    pipe = pipeline(d)
+    shards, part = _native_slabs(sc, 2, pipe)
+    cut = part.block_range(1)[0]
+    for s in shards:
+        s.close()
+    sc, floor, ball = _ball_scene(d, h, ball_x=cut * bw - 3.7)       # (its reach ends 3 h ahead of its centre)
+    assert np.array_equal(sc["particles"].pos, ps.pos)
+    shards, part = _native_slabs(sc, 2, pipe)
+    ranges = [part.block_range(r) for r in range(2)]
+    fails = []
+    pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
+    crossed = []
+    for k in range(4):
+        poses = shards[0].read_body_poses()
+        native_lockstep(pipe, shards, 1)
+        for s in shards:
+            s.sync()
+        cols = CT.colliders_of(sc["colliders"], d, poses)
+        tag = f"slabs moving ball {d}D substep {k}"
+        whole = CT.NodeField(cols, d, h, CT.active_cells(pos, h, d))
+        e2e = CT.from_truth_nodes(pos, h, whole, prev)
+        npos, aff, dist, normal = _export_all(shards, ps.n, d)
+        CT.check_particle_cdf(f"{tag} end to end", e2e, aff, dist, normal, fails)
+        CT.assert_caps(tag, whole, e2e)
+        for r, s in enumerate(shards):
+            cells, _, ndist, naff, nclosest = MpmData.read_grid(s)
+            blk = cells[:, 0] // bw
+            own = (blk >= ranges[r][0]) & (blk < ranges[r][1])
+            assert own.any()
+            nf = CT.NodeField(cols, d, h, cells[own])
+            CT.check_nodes(f"{tag} slab {r} own nodes", nf, ndist[own], naff[own], nclosest[own], fails)
+            inside = set(map(tuple, cells[own].tolist()))
+            missing = [c for c in whole.cells[(whole.aff != 0) & (whole.cells[:, 0] // bw >= ranges[r][0]) & (whole.cells[:, 0] // bw < ranges[r][1])].tolist()
+                       if tuple(c) not in inside]
+            assert not missing, f"{tag} slab {r}: {len(missing)} collider-affine nodes of its range are not in its grid"
+        crossed.append(bool((whole.voter[:, 1] & (whole.cells[:, 0] >= cut * bw)).any()))
+        pos, prev = npos, aff
+    for s in shards:
+        s.close()
+    report_margin(f"slabs moving ball {d}D: substeps in which the ball's reach is past the cut", sum(crossed), 1)
+    assert not fails, "\n".join(fails)
+    assert not crossed[0] and crossed[-1], crossed
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_sign_persistence_under_a_thin_plate(hip_libs, d):
+    """A plate of half thickness 0.3 h is swept through a layer of particles by 0.45 h per substep: a particle keeps the sign
+    it had while it keeps the affinity, whatever its fresh vote says. The previous words are those read back."""
+    h = 0.2
+    rng = np.random.default_rng(50 + d)
+    x0 = np.array([4.13, 6.21, 6.17]) * h
+    at = lambda k: Collider.cuboid(CT._v(np.array([0.3, 3.0, 3.0]) * h, d), CT._v(x0 + np.array([0.45 * h * k, 0.0, 0.0]), d),
+                                   rotation=(0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0))
+    lo, hi = np.array([3.0, 3.5, 3.5]) * h, np.array([10.0, 9.0, 9.0]) * h
+    sc = CT._static(d, h, rng, [at(0)], [(lo, hi)], 3000 if d == 3 else 1500, rim_keep=1.0)
+    data = _new(sc)
+    fails = []
+    n_kept = 0
+    for k in range(8):
+        # the host moves the plate (a body in contact that integrates its own velocity is limited to 0.1 h per substep)
+        if k:
+            data.set_colliders([at(k)])
+        _, pf, _ = _checked_substep(f"thin plate {d}D substep {k}", sc, data, fails, first=k == 0, colliders=[at(k)])
+        n_kept += int(pf.fresh_sign_differs.sum())
+    report_margin(f"thin plate {d}D: decided particles whose sign differs from their fresh vote", n_kept, 10)
+    assert not fails, "\n".join(fails)
+    assert n_kept >= 10, n_kept
+
+
+def test_det_edge(hip_libs):
+    """3D, h = 0.1: decided particles on both sides of det = 1e-8 carry exactly the truth's affinity word (0 below)."""
+    sc = CT.det_edge()
+    data = _new(sc)
+    fails = []
+    _, pf, got = _checked_substep("det edge", sc, data, fails, first=True, part_cap=CT.DET_EDGE_CAP)
+    dec = pf.reaches & ~pf.undecided
+    below, above = int((dec & ~pf.ok).sum()), int((dec & pf.ok).sum())
+    report_margin("det edge: decided particles below / above 1e-8, undecided", below, 20, above=above, undecided=int((pf.reaches & pf.undecided).sum()))
+    assert below >= 20 and above >= 20
+    assert not fails, "\n".join(fails)
