@@ -144,6 +144,9 @@ enum { WGS_MODEL_COROTATED = 0, WGS_MODEL_NEO_HOOKEAN = 1, WGS_MODEL_FLUID = 2 }
  * diag(det F, 1[, 1]) (nothing changes where it has that form already); selecting another model afterwards needs nothing. On data
  * whose step carries plastic state (Drucker-Prager particles, breakable phases, force_plastic) the call returns WGS_ERR_UNSUPPORTED
  * and changes nothing. */
+/* Per-particle models (wgs_set_particle_models below): what wgs_diagnostics.model reports while a table is set. Never a model of its
+ * own: wgs_set_constitutive_model refuses it like any other unknown value. */
+#define WGS_MODEL_PER_PARTICLE 3
 
 /* The reference's 10 timestamped passes (src/pipeline.rs:201-271). The fused
  * G2P + particle update reports its time under WGS_PASS_G2P; in collider simulations
@@ -211,7 +214,9 @@ const char *wgs_build_info(void);
  * wgs_stats grew by block_ids .. table_refreshes (24 bytes); 6 = this function. New counters will come behind a call of their own.
  * 7 = wgs_read_diagnostics / wgs_enqueue_diagnostics and their structs (nothing that existed changed). Still 7: WGS_MODEL_FLUID and
  * wgs_set_fluid_eos were added without touching a struct, an enum value or a signature — a binding that must run against older
- * libraries of version 7 detects wgs_set_fluid_eos by symbol lookup. */
+ * libraries of version 7 detects wgs_set_fluid_eos by symbol lookup. Still 7: WGS_MODEL_PER_PARTICLE, wgs_set_particle_models and
+ * wgs_read_particle_models were added the same way (new symbols and a macro only; wgs_diagnostics.model may now read 3) — detect
+ * wgs_set_particle_models by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -235,6 +240,28 @@ wgs_status wgs_set_constitutive_model(wgs_data *data, int32_t model);
  * enqueued after the call use it. gamma must be finite and > 1, else WGS_ERR_INVALID_ARGUMENT; allowed under any model, read only
  * by the fluid. */
 wgs_status wgs_set_fluid_eos(wgs_data *data, float gamma);
+/* Per-particle constitutive model. NEW: the reference compiles ONE model into its shader (src/solver/particle_update.wgsl:7-8); here a
+ * simulation may mix them, so that an elastic body can be put into the Tait fluid and the two interact through the shared grid.
+ * `models`: num_particles bytes in the caller's order, each WGS_MODEL_COROTATED, WGS_MODEL_NEO_HOOKEAN or WGS_MODEL_FLUID. Blocking, like
+ * wgs_set_plastic_state. From the next substep on every particle is advanced under its own model (the transfers do not know the
+ * model: the stress enters through `affine` alone); the fluid particles share the data's one wgs_set_fluid_eos gamma, and lambda, mu
+ * of a particle mean what its OWN model takes them for. The label travels with the particle: wgs_read_particle_models returns it in
+ * the caller's order at any time, and wgs_read_particles + wgs_read_particle_models -> wgs_data_create + wgs_set_particle_models
+ * restarts a run bit for bit (the state digest does not hash the model).
+ * def_grad of the particles labelled WGS_MODEL_FLUID is collapsed to diag(det F, 1[, 1]) by the call, exactly as
+ * wgs_set_constitutive_model(WGS_MODEL_FLUID) does for all particles (nothing changes where it has that form already, so setting the
+ * same table twice changes no bit); the others are left as they are. A particle RE-LABELLED from the fluid to a solid keeps
+ * diag(J, 1[, 1]) as its deformation gradient: a valid F of that volume ratio, but whatever shape the fluid parcel took is forgotten.
+ * While a table is set, wgs_diagnostics.model reads WGS_MODEL_PER_PARTICLE, WGS_SUM_ELASTIC takes Psi of each particle's own model, and
+ * wgs_prep_vertex_buffer* draws the fluid particles isotropically (cbrt(J) I / sqrt(J) I) and the others with their F.
+ * models == NULL drops the table: every particle is advanced under the data's single model again (def_grad is not touched).
+ * wgs_set_constitutive_model while a table is set drops the table first, then does what it always does.
+ * Errors (nothing is changed): an entry > 2 -> WGS_ERR_INVALID_ARGUMENT; data whose step carries plastic state (the condition under
+ * which WGS_MODEL_FLUID is refused) -> WGS_ERR_UNSUPPORTED; sharded data (wgs_data_create_sharded: the migration record carries no
+ * model) -> WGS_ERR_UNSUPPORTED. */
+wgs_status wgs_set_particle_models(wgs_data *data, const uint8_t *models /* num_particles, or NULL */);
+/* The model of every particle in the caller's order (num_particles bytes). Blocking. Without a table every entry is the data's model. */
+wgs_status wgs_read_particle_models(wgs_data *data, uint8_t *out);
 
 /* MpmPipeline::queue_step + `for _ in 0..num_substeps { queue.encode(..) }` + submit
  * (src/pipeline.rs:195-281, src_testbed/step.rs:122-128,169): enqueues `num_substeps`

@@ -123,6 +123,16 @@ class MpmData {
     void set_constitutive_model(int32_t model) { check(wgs_set_constitutive_model(h_, model)); }
     // the Tait exponent of WGS_MODEL_FLUID (default 7; finite and > 1)
     void set_fluid_eos(float gamma) { check(wgs_set_fluid_eos(h_, gamma)); }
+    // per-particle constitutive model: one WGS_MODEL_* (0 / 1 / 2) per particle in the caller's order; an empty vector drops the table
+    void set_particle_models(const std::vector<uint8_t> &models) {
+        if (!models.empty() && models.size() != n_) throw Error(WGS_ERR_INVALID_ARGUMENT, "set_particle_models: one entry per particle");
+        check(wgs_set_particle_models(h_, models.empty() ? nullptr : models.data()));
+    }
+    std::vector<uint8_t> read_particle_models() {
+        std::vector<uint8_t> out(n_);
+        check(wgs_read_particle_models(h_, out.data()));
+        return out;
+    }
     // device.poll(Maintain::Wait) (src/pipeline.rs:339); also reports device-side sticky errors (grid overflow, key range)
     void sync() { check(wgs_sync(h_)); }
     // the per-frame host -> device writes of src_testbed/step.rs:79-119 and ui.rs:91-104

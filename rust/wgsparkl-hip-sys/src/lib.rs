@@ -219,6 +219,9 @@ extern "C" {
     pub fn wgs_data_destroy(d: *mut wgs_data);
     pub fn wgs_set_constitutive_model(d: *mut wgs_data, model: i32) -> wgs_status;
     pub fn wgs_set_fluid_eos(d: *mut wgs_data, gamma: f32) -> wgs_status;
+    /// per-particle constitutive model: `models` = num_particles bytes in the caller's order (0 / 1 / 2), or null to drop the table
+    pub fn wgs_set_particle_models(d: *mut wgs_data, models: *const u8) -> wgs_status;
+    pub fn wgs_read_particle_models(d: *mut wgs_data, out: *mut u8) -> wgs_status;
     pub fn wgs_step(p: *mut wgs_pipeline, d: *mut wgs_data, num_substeps: u32, timestamps: i32) -> wgs_status;
     pub fn wgs_sync(d: *mut wgs_data) -> wgs_status;
     pub fn wgs_set_sim_params(d: *mut wgs_data, params: *const wgs_sim_params) -> wgs_status;

@@ -31,6 +31,8 @@ EXPORTS = (
     "wgs_read_diagnostics", "wgs_enqueue_diagnostics",
     # WGS_MODEL_FLUID: the Tait exponent (same ABI version: older libraries of version 7 lack the symbol)
     "wgs_set_fluid_eos",
+    # per-particle constitutive model (same ABI version again: detected by symbol lookup)
+    "wgs_set_particle_models", "wgs_read_particle_models",
 )
 
 
@@ -171,6 +173,8 @@ def load(dim: int):
     lib.wgs_data_destroy.restype = None
     lib.wgs_set_constitutive_model.argtypes = [vp, C.c_int32]
     lib.wgs_set_fluid_eos.argtypes = [vp, C.c_float]
+    lib.wgs_set_particle_models.argtypes = [vp, C.POINTER(C.c_uint8)]
+    lib.wgs_read_particle_models.argtypes = [vp, C.POINTER(C.c_uint8)]
     lib.wgs_step.argtypes = [vp, vp, C.c_uint32, C.c_int32]
     lib.wgs_sync.argtypes = [vp]
     lib.wgs_set_sim_params.argtypes = [vp, C.POINTER(T.SimParams)]

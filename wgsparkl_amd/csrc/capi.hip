@@ -46,3 +46,4 @@ using namespace wgs;
 #include "kernels_diag.h"        // device-side diagnostics and their launch sequence
 #include "capi_debug.inc"        // extern "C": diagnostics, test hooks, WGS_ABLATE profile readers
 #include "kernels_fluid.h"       // WGS_MODEL_FLUID: the kernel of the model switch (last: nothing that existed changes its place)
+#include "kernels_models.h"      // per-particle models: the kernels of wgs_set_particle_models / wgs_read_particle_models (behind it, likewise)

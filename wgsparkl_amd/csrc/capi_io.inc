@@ -5,6 +5,21 @@
 
 namespace {
 __global__ void k_fluid_collapse(Dev d, int side);   // kernels_fluid.h (defined behind every other kernel: capi.hip on placement)
+__global__ void k_models_scatter(Dev d, int side, const uint8_t *by_pid);   // kernels_models.h (likewise)
+__global__ void k_models_gather(Dev d, int side, uint8_t *by_pid);
+__global__ void k_fluid_collapse_masked(Dev d, int side);
+
+// back to the data's single model: the planes are released once nothing in flight reads them
+wgs_status drop_particle_models(wgs_data *d) {
+    if (!d->dev.pmodel[0]) return WGS_OK;
+    WGS_TRY(enter(d));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    for (int s = 0; s < 2; s++) {
+        d->mem.release(d->dev.pmodel[s]);
+        d->dev.pmodel[s] = nullptr;
+    }
+    return WGS_OK;
+}
 }
 
 extern "C" {
@@ -36,6 +51,9 @@ wgs_status wgs_set_constitutive_model(wgs_data *d, int32_t model) {
     if (model == WGS_MODEL_FLUID) {
         // (only the instantiations without plastic state exist for the fluid: host_substep.inc launch_g2p)
         if (d->plastic) return fail(WGS_ERR_UNSUPPORTED, "WGS_MODEL_FLUID: this data's step carries plastic state (Drucker-Prager particles, phases or force_plastic)");
+    }
+    WGS_TRY(drop_particle_models(d));   // (one model for all particles again: wgs_set_particle_models)
+    if (model == WGS_MODEL_FLUID) {
         // the F quads of the current buffer -> diag(det F, 1[, 1]), stream-ordered (kernels_fluid.h; the identity on values already in that
         // form). Switching away needs nothing: diag(J, 1, 1) is a deformation gradient of that volume ratio.
         WGS_TRY(enter(d));
@@ -44,6 +62,51 @@ wgs_status wgs_set_constitutive_model(wgs_data *d, int32_t model) {
     }
     d->dev.model = model;
     return WGS_OK;
+}
+
+wgs_status wgs_set_particle_models(wgs_data *d, const uint8_t *models) {
+    if (!d) return fail(WGS_ERR_INVALID_ARGUMENT, "data is NULL");
+    if (d->dev.sharded) return fail(WGS_ERR_UNSUPPORTED, "wgs_set_particle_models: sharded data (the migration record carries no model): single-domain data only");
+    if (!models) return drop_particle_models(d);
+    // (only the instantiation without plastic state exists: host_substep.inc launch_g2p)
+    if (d->plastic) return fail(WGS_ERR_UNSUPPORTED, "wgs_set_particle_models: this data's step carries plastic state (Drucker-Prager particles, phases or force_plastic)");
+    const size_t n = d->dev.n;
+    for (size_t i = 0; i < n; i++)
+        if (models[i] > WGS_MODEL_FLUID)
+            return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_set_particle_models: entry " + std::to_string(i) + " is " + std::to_string((int)models[i]) + ", not a WGS_MODEL_* (0, 1, 2)");
+    WGS_TRY(enter(d));
+    Dev &dev = d->dev;
+    if (!dev.pmodel[0]) {   // one byte per slot and side, like the pid plane
+        WGS_TRY(dev_alloc(d, &dev.pmodel[0], (size_t)dev.npad));
+        if (dev_alloc(d, &dev.pmodel[1], (size_t)dev.npad) != WGS_OK) {
+            d->mem.release(dev.pmodel[0]);
+            dev.pmodel[0] = nullptr;
+            return WGS_ERR_HIP;
+        }
+    }
+    if (n) {
+        Scratch<uint8_t> tmp;
+        WGS_TRY(tmp.alloc(n));
+        HIP_TRY(hipMemcpyAsync(tmp.ptr, models, n, hipMemcpyHostToDevice, d->stream));
+        hipLaunchKernelGGL(k_models_scatter, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, dev, d->side, tmp.ptr);
+        // the fluid's particles -> diag(det F, 1[, 1]), as wgs_set_constitutive_model(WGS_MODEL_FLUID) does for all of them
+        hipLaunchKernelGGL(k_fluid_collapse_masked, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, dev, d->side);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(d->stream));
+    }
+    return WGS_OK;
+}
+
+wgs_status wgs_read_particle_models(wgs_data *d, uint8_t *out) {
+    WGS_TRY(enter(d, out != nullptr));
+    if (d->dev.sharded) return fail(WGS_ERR_UNSUPPORTED, "wgs_read_particle_models: sharded data has one model (wgs_set_constitutive_model)");
+    const size_t n = d->dev.n;
+    if (n == 0) return WGS_OK;
+    Scratch<uint8_t> tmp;
+    WGS_TRY(tmp.alloc(n));
+    hipLaunchKernelGGL(k_models_gather, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side, tmp.ptr);
+    HIP_TRY(hipGetLastError());
+    return download(d, out, tmp.ptr, n);
 }
 
 wgs_status wgs_set_fluid_eos(wgs_data *d, float gamma) {

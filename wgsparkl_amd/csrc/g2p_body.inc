@@ -2,6 +2,9 @@
 // that the two-body launch of collider simulations (k_g2p_pair) compiles the very code of the single-body kernel.
 // Expects in scope: d, side, epoch, the template parameters D / MODEL / PLASTIC / SHARD, the shared arrays s_node / s_cdf,
 // and the macros G2P_CMODE, G2P_BX, G2P_GX (index of the workgroup within this body and their number).
+// MODEL: 0 corotated, 1 neo-Hookean, 2 fluid — one model for every particle — or 3: every particle under its OWN model, a byte that
+// travels with it (Dev::pmodel; loaded beside the pid through the sort permutation, stored beside it at the sorted slot). Only the
+// particle update knows: the transfer, the binning and the CPIC paths are those of the other models, word for word.
 // SHARD: the data is one slab of a decomposition (particle counts in device counters, guests dropped, leavers listed).
 // A template parameter rather than the run-time field it mirrors: this kernel lives at the limit of its scalar
 // registers, and the single-domain instantiation should not carry a single one of them for a decomposition.
@@ -83,6 +86,7 @@
     }
     // state of the next item (requested one pass ahead) and the sort entries of the item after it
     uint32_t nx_src = 0u, nx_cid = NONE, nx_pid = 0u, nn_src = 0u, nn_cid = NONE;
+    [[maybe_unused]] uint32_t nx_pm = 0u;   // MODEL 3: the next item's model byte
     uint32_t nx_listed = 0u;  // G2P_CMODE 1: block_cpic of the next item's block (one more dependent load taken off the pass)
     float4 nx_xm = make_float4(0.f, 0.f, 0.f, 0.f), nx_f0 = nx_xm, nx_f1 = nx_xm, nx_f2 = nx_xm;
     if constexpr (npass > 1u) {
@@ -132,7 +136,13 @@
         // second waited for the first — a dependent round trip in front of every wave's state loads, ~1.2 us of a wave's ~6.5 at the headline)
         // (not the neo-Hookean four-chunk kernel — C5's: only a quarter of its passes are first passes, and with the earlier request it
         // ran 613 -> 648 us, twice, on one box beside the dependent form; the corotated four-chunk kernel — C4's — gains 8-18 us)
-        constexpr bool together = npass <= 2u || MODEL == 0;
+        // (MODEL 3 sides with the corotated kernel here and at the block id below. Both choices follow the register allocation, and the
+        // mixed kernel's is the corotated one's: its three stress branches are alternatives whose registers overlap, and the SVD
+        // branch is by far the widest, so the kernel sits at MODEL 0's register count in every shape (notes/round_11.md: 166-168
+        // VGPRs at the 168 cap in 3D, 8-20 B more scratch per lane than MODEL 0 where that one spills at all — the model byte and its
+        // prefetched copy are two more values live across the pass). What upset the neo-Hookean kernels was measured on THEIR
+        // allocation, which does not exist once the SVD is compiled in. Neither alternative was timed for MODEL 3.)
+        constexpr bool together = npass <= 2u || MODEL == 0 || MODEL == 3;
         const uint32_t src_any = second ? nx_src : (((together ? inb : valid) && (together || g2p_wanted(cid_raw, only))) ? d.perm[j] : 0u);
         // (a visit's lane whose particle belongs to another block than the listed one asks for slot 0 instead of its particle)
         const uint32_t src = (second || g2p_wanted(cid_raw, only)) ? src_any : 0u;
@@ -151,16 +161,19 @@
         // Particle state: issued before the tile staging so both latencies overlap.
         float x[D], Fm[DD], mass, vol0, lambda, mu;
         uint32_t pid;
+        [[maybe_unused]] uint32_t pm = 0u;   // MODEL 3: this particle's model
         if constexpr (D == 3) {
             float4 xm, f0, f1, f2 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (second) {
                 xm = nx_xm; f0 = nx_f0; f1 = nx_f1; f2 = nx_f2; pid = nx_pid;
+                if constexpr (MODEL == 3) pm = nx_pm;
             } else {
                 xm = ldq_stream(in, npad, P::XM, src);
                 f0 = ldq_stream(in, npad, P::F0, src);
                 f1 = ldq_stream(in, npad, P::F1, src);
                 if (!d.uniform) f2 = ldq_stream(in, npad, P::F2, src);
                 pid = ldpid<D>(in, npad, src);
+                if constexpr (MODEL == 3) pm = ldmodel(d.pmodel[side], src);
             }
             if constexpr (npass > 1u) {
                 if (pass + 1 < (int)npass) {  // the next pass's state, in flight while this one is computed
@@ -183,6 +196,7 @@
                     nx_f1 = ldq_stream(in, npad, P::F1, nx_src);
                     if (!d.uniform) nx_f2 = ldq_stream(in, npad, P::F2, nx_src);
                     nx_pid = ldpid<D>(in, npad, nx_src);
+                    if constexpr (MODEL == 3) nx_pm = ldmodel(d.pmodel[side], nx_src);
                     if constexpr (G2P_CMODE == 1) {
                         if (!d.listed_in_perm) nx_listed = nx_cid != NONE ? d.block_cpic[(nx_cid & ~CELL_LISTED) >> 6] : 0u;
                     }
@@ -206,6 +220,7 @@
             lambda = vl.z; mu = vl.w;
         }
         if constexpr (D == 2) pid = ldpid<D>(in, npad, src);
+        if constexpr (D == 2 && MODEL == 3) pm = ldmodel(d.pmodel[side], src);
 
         float pvel[D], nrm[D], sdist = 0.f;
         uint32_t paff = 0;
@@ -237,6 +252,7 @@
                     stq(out, npad, P::F2, j, make_float4(Fm[8], vol0, lambda, mu));
                 }
                 stpid<D>(out, npad, j, pid);
+                if constexpr (MODEL == 3) stmodel(d.pmodel[side ^ 1], j, pm);
             }
             G2P_DONE;
         }
@@ -248,7 +264,7 @@
             // (the block of the leader: by v_readlane — the id then lives in a scalar register and the kernels shed 4-32 B of scratch per
             // lane: C4's fused G2P 445 -> 413 us — except in the neo-Hookean elastic kernels, whose allocation the same change upsets:
             // the headline's ran 44.8 -> 46.5 us over five alternations on one box, C5's was a wash. They keep the permute.)
-            const uint32_t b = (MODEL == 0 || PLASTIC) ? lane_value(myblock, leader) : (uint32_t)__shfl(myblock, leader);
+            const uint32_t b = (MODEL == 0 || MODEL == 3 || PLASTIC) ? lane_value(myblock, leader) : (uint32_t)__shfl(myblock, leader);
             const bool mine = myblock == b;
             todo &= ~__ballot(mine);
             int bc[3] = {0, 0, 0};
@@ -599,7 +615,9 @@
                     }
                 }
                 // F <- F + (grad * dt) * F   (the fluid keeps J alone, in F[0]: fluid_update below)
-                if constexpr (MODEL != 2) {
+                // (MODEL 3: where the particle is not fluid. A per-lane branch, like the stress below: a wave that holds one kind skips the
+                // others' code, a mixed wave runs the branches it needs one after the other — the sum of the models it holds, never more)
+                if (MODEL != 2 && (MODEL != 3 || pm != 2u)) {
                     float gdt[DD], prod[DD];
     #pragma unroll
                     for (int k = 0; k < DD; k++) gdt[k] = grad[k] * dt;
@@ -653,7 +671,19 @@
                         stq(out, npad, P::DP2, j, make_float4(st[2], phase, max_stretch, 0.f));
                     }
                 }
-                if constexpr (MODEL == 2) {
+                if constexpr (MODEL == 3) {
+                    static_assert(MODEL != 3 || !PLASTIC, "per-particle models: no plastic state (wgs_set_particle_models refuses such data)");
+                    // the very functions of the three homogeneous instantiations, each on the arguments it gets there: under
+                    // -ffp-contract=on the rounding of a branch is that of its own kernel
+                    if (pm == 2u) {
+                        Fm[0] = fluid_update<D>(lambda, mu, d.fluid_gamma, grad, dt, Fm[0], tau);
+                    } else if (pm == 1u) {
+                        kirchoff_neo_hookean<D>(lambda, mu, Fm, tau);
+                    } else {
+                        svd<D>(Fm, sv);
+                        kirchoff_corotated<D>(lambda, mu, Fm, sv, tau);
+                    }
+                } else if constexpr (MODEL == 2) {
                     static_assert(MODEL != 2 || !PLASTIC, "the fluid carries no plastic state");
                     Fm[0] = fluid_update<D>(lambda, mu, d.fluid_gamma, grad, dt, Fm[0], tau);   // def_grad = diag(J, 1[, 1]): layout.h
                 } else if constexpr (MODEL == 1) {
@@ -683,6 +713,7 @@
                     stq(out, npad, P::F0, j, make_float4(Fm[0], Fm[1], Fm[2], Fm[3]));
                 }
                 stpid<D>(out, npad, j, pid);
+                if constexpr (MODEL == 3) stmodel(d.pmodel[side ^ 1], j, pm);
                 // G2P_CMODE 1 (no collider in reach): default_cdf() is implied by a stale stamp, nothing to store (layout.h)
                 if constexpr (CPIC) {
                     if constexpr (D == 3) {

@@ -141,14 +141,16 @@ struct G2pLaunch {
 template <int DIM, int MODEL, bool PL, int NP, class Mark>
 void launch_g2p_shape(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
     constexpr int WPE = PL ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, WPE_DENSE = PL ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU;
+    // (per-particle models exist on single-domain data only — wgs_set_particle_models refuses slabs —: no slab instantiation of MODEL 3)
+    constexpr bool SH = MODEL != 3;
     const dim3 g(p.g), pg(p.g + 8u * p.nlist), t(G2P_THREADS);
     switch (p.shape) {
         case G2pShape::pair_dense:
-            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, SH, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
             else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE_DENSE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
             break;
         case G2pShape::pair:
-            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, true, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
+            if (p.shard) hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, SH, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
             else hipLaunchKernelGGL((k_g2p_pair<DIM, MODEL, PL, WPE, NP, false, !PL>), pg, t, 0, s, dev, side, epoch, p.g, p.nlist);
             break;
         case G2pShape::two_launches:
@@ -157,7 +159,7 @@ void launch_g2p_shape(const Dev &dev, hipStream_t s, int side, uint32_t epoch, c
             hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 2, 1, false, !PL>), dim3(8u * p.nlist), t, 0, s, dev, side, epoch);
             break;
         case G2pShape::single:
-            if (p.shard) hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, true, !PL>), g, t, 0, s, dev, side, epoch);
+            if (p.shard) hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, SH, !PL>), g, t, 0, s, dev, side, epoch);
             else hipLaunchKernelGGL((k_g2p_update<DIM, MODEL, PL, 0, NP, false, !PL>), g, t, 0, s, dev, side, epoch);
             break;
     }
@@ -174,12 +176,14 @@ void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, c
 template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
     // (the fluid exists without plastic state only — wgs_set_constitutive_model refuses it on such data — and comes last: the
     // instantiations of the other models keep their places in the code object)
-    switch (dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
+    // (a table of per-particle models — Dev::pmodel, likewise without plastic state and on single-domain data only — behind the fluid)
+    switch (dev.pmodel[0] ? 5 : dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
         case 0: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
         case 1: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
         case 2: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
         case 3: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
-        default: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
+        case 4: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
+        default: launch_g2p_model<DIM, 3, false>(dev, s, side, epoch, p, mark); break;
     }
 }
 

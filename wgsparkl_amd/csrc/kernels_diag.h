@@ -260,7 +260,8 @@ __global__ __launch_bounds__(256) void k_diag_pass1(Dev d, int side, bool plasti
         if constexpr (PART) {
             if (!diag_finite(u)) { add[DA_NONFINITE]++; continue; }
             double t[DIAG_PARTICLE_SUMS];
-            diag_particle_terms<ENERGY>(u, h2q, grav, d.model, (double)d.fluid_gamma, t);
+            // (Psi of the particle's OWN model where the data carries a table: layout.h Dev::pmodel)
+            diag_particle_terms<ENERGY>(u, h2q, grav, d.pmodel[side] ? (int)d.pmodel[side][j] : d.model, (double)d.fluid_gamma, t);
 #pragma unroll
             for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) {
                 const unsigned long long b = diag_abs_bits(t[s]);
@@ -335,7 +336,7 @@ template <bool ENERGY> __global__ __launch_bounds__(256) void k_diag_pass2(Dev d
         fix_uniform<D>(d, u);
         if (!diag_finite(u)) continue;
         double t[DIAG_PARTICLE_SUMS];
-        diag_particle_terms<ENERGY>(u, h2q, grav, d.model, (double)d.fluid_gamma, t);
+        diag_particle_terms<ENERGY>(u, h2q, grav, d.pmodel[side] ? (int)d.pmodel[side][j] : d.model, (double)d.fluid_gamma, t);
 #pragma unroll
         for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) fixed[s] += (unsigned long long)__double2ll_rn(t[s] * scale[diag_group_of(s)]);
     }
@@ -443,7 +444,7 @@ template <int DIM> __global__ void k_diag_finish(Dev d, DiagAcc *acc, uint32_t w
     r.digest[0] = acc->add[DA_DIGEST0];   // (zero unless asked for)
     r.digest[1] = acc->add[DA_DIGEST1];
     r.what = what;
-    r.model = (uint32_t)d.model;
+    r.model = d.pmodel[0] ? (uint32_t)WGS_MODEL_PER_PARTICLE : (uint32_t)d.model;
     for (int s = 0; s < WGS_NUM_SUMS; s++) {
         const bool asked = s < WGS_SUM_GRID_MASS ? ((what & WGS_DIAG_PARTICLES) && (s != WGS_SUM_ELASTIC || (what & WGS_DIAG_ENERGY))) : (what & WGS_DIAG_GRID) != 0u;
         if (!asked) continue;

@@ -175,7 +175,8 @@ __global__ void k_prep_instances(Dev d, int side, uint32_t mode, bool cpic, uint
         float *r = inst + (size_t)pid * 24;
         // deformation: mat3x3 as three padded columns (instancing3d.rs:66-74); 2D embeds F in the xy block
         float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-        if (d.model == WGS_MODEL_FLUID) {   // F holds diag(J, 1[, 1]) (layout.h): drawn as the isotropic deformation of that volume ratio
+        // (the particle's own model where the data carries a table: layout.h Dev::pmodel)
+        if ((d.pmodel[side] ? (int)d.pmodel[side][j] : d.model) == WGS_MODEL_FLUID) {   // F holds diag(J, 1[, 1]) (layout.h): drawn as the isotropic deformation of that volume ratio
             const float s = D == 3 ? cbrtf(u.F[0]) : sqrtf(u.F[0]);
             for (int k = 0; k < DD; k++) u.F[k] = 0.f;
             for (int k = 0; k < D; k++) u.F[k * D + k] = s;

@@ -298,6 +298,12 @@ struct Dev {
     // layout (mat_det of it is J exactly, so read-back, diagnostics, digest and checkpoint restore work as they are). k_fluid_collapse
     // (kernels_readback.h) brings a buffer into that form when the model is selected.
     float fluid_gamma;
+    // Per-particle constitutive model (wgs_set_particle_models): one byte per slot — WGS_MODEL_COROTATED / NEO_HOOKEAN / FLUID —, one plane
+    // per ping-pong side like the pid plane (the fused G2P reads plane [side] through the sort permutation and writes plane [side ^ 1] at
+    // the sorted slot: ldmodel / stmodel below). Both null while the data has ONE model (`model` above), which is every instantiation
+    // but MODEL = 3 of the fused G2P (g2p_body.inc). Allocated by the first call; single-domain data without plastic state only.
+    // (At the END of the struct: what every existing kernel reads of its Dev argument keeps its offset.)
+    uint8_t *pmodel[2];
 };
 
 // WGS_DEBUG: developer switches, one bit each. A launch-shape switch brings back an alternative launch shape that must give
@@ -526,6 +532,18 @@ template <int D> __device__ inline void stpid(float *base, uint32_t npad, uint32
     uint32_t off = ((uint32_t)Pl<D>::NQ * 4u * npad + i) * 4u;
     asm volatile("" : "+v"(off));
     *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(base) + off) = pid;
+}
+
+// the model byte of a slot (Dev::pmodel): planes of their own, one scalar base + the slot index pinned like the quads' offsets
+__device__ inline uint32_t ldmodel(const uint8_t *plane, uint32_t i) {
+    uint32_t off = i;
+    asm volatile("" : "+v"(off));
+    return plane[off];
+}
+__device__ inline void stmodel(uint8_t *plane, uint32_t i, uint32_t m) {
+    uint32_t off = i;
+    asm volatile("" : "+v"(off));
+    plane[off] = (uint8_t)m;
 }
 
 }  // namespace wgs

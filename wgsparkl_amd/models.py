@@ -16,6 +16,7 @@ F32 = np.float32
 # src/solver/particle_update.wgsl:7-8; here it is a runtime per-MpmData choice).
 MODEL_COROTATED = 0      # models/linear_elasticity.wgsl (reference default)
 MODEL_NEO_HOOKEAN = 1    # models/neo_hookean_elasticity.wgsl
+MODEL_PER_PARTICLE = 3   # what the diagnostics report while a per-particle table is set (MpmData.set_particle_models); never a model to select
 MODEL_FLUID = 2          # weakly-compressible Tait fluid + viscosity (no reference counterpart; include/wgsparkl_hip.h WGS_MODEL_FLUID)
 
 

@@ -276,6 +276,23 @@ class MpmData:
         """`wgs_set_fluid_eos`: the Tait exponent of MODEL_FLUID (default 7; finite and > 1). Stream-ordered."""
         _ffi.check(self.lib, self.lib.wgs_set_fluid_eos(self._h, float(gamma)))
 
+    def set_particle_models(self, models):
+        """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —
+        fluid and solids in one simulation, coupled through the grid. `None` drops the table. Blocking."""
+        if models is None:
+            _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, None))
+            return
+        m = np.ascontiguousarray(models, np.uint8).reshape(-1)
+        if m.shape[0] != self.n:
+            raise ValueError("set_particle_models: one entry per particle")
+        _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def read_particle_models(self) -> np.ndarray:
+        """`wgs_read_particle_models`: the model of every particle in the caller's order (np.uint8); the data's model without a table."""
+        out = np.zeros(self.n, np.uint8)
+        _ffi.check(self.lib, self.lib.wgs_read_particle_models(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
     def set_sim_params(self, params: SimulationParams):
         sp = self.T.SimParams()
         sp.gravity = (C.c_float * self.dim)(*params.gravity)

@@ -321,6 +321,45 @@ def dam_break(nx=24, ny=40, nz=16, jitter=0.05, cell_width=1.0, density=1000.0, 
                 cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma))
 
 
+def block_in_fluid(dim=3, tank=(24, 16, 16), block=8, gap=0.5, drop_speed=0.0, solid_model=MODEL_NEO_HOOKEAN, jitter=0.05, cell_width=1.0,
+                   density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, solid_density=2000.0, young_modulus=2.0e5, poisson=0.3):
+    """Fluid and solid in one simulation (MpmData.set_particle_models): a tank of Tait fluid — `tank` particles at spacing h/2 standing on
+    the floor cuboid between four wall cuboids (two in 2D), like `dam_break` but closed — and an elastic block of `block`^dim particles
+    hanging `gap` cells above the middle of its surface, falling at `drop_speed`. The two interact through the grid alone. Returns the
+    scene dict with "models" (np.uint8 per particle: MODEL_FLUID for the tank, `solid_model` for the block) and "solid_model";
+    "model" (the data's single model, before the table is set) is the solid's: selecting the fluid for the whole data would collapse the
+    block's deformation gradient too. The fluid's particles come first."""
+    h = cell_width
+    tank = tuple(tank)[:dim] if dim == 3 else (tank[0], tank[1])
+    origin = (8.3 * h, 2.2 * h, 8.3 * h)[:dim]                 # floor top at y = 2 h, wall faces 0.3 h off the fluid
+    fpos = lattice(tank, origin, h, jitter)
+    top = origin[1] + tank[1] * h / 2.0
+    borigin = [origin[k] + (tank[k] - block) * h / 4.0 for k in range(dim)]
+    borigin[1] = top + gap * h
+    bpos = lattice((block,) * dim, borigin, h, jitter, seed=4321)
+    fluid = FluidCoefficients(bulk_modulus, viscosity)
+    ps = ParticleSet.uniform(np.concatenate([fpos, bpos]), h / 4.0, density, fluid, phase=ParticlePhase(1.0, FLT_MAX))
+    nf = len(fpos)
+    solid = ElasticCoefficients.from_young_modulus(young_modulus, poisson)
+    ps.lambda_[nf:], ps.mu[nf:] = F32(solid.lambda_), F32(solid.mu)
+    ps.mass[nf:] = (ps.init_volume[nf:] * F32(solid_density)).astype(F32)
+    ps.vel[nf:, 1] = F32(-drop_speed)
+    t, big = 2.0 * h, 1000.0 * h
+    x0, x1 = origin[0] - 0.3 * h, origin[0] + tank[0] * h / 2.0 + 0.3 * h
+    if dim == 3:
+        z0, z1 = origin[2] - 0.3 * h, origin[2] + tank[2] * h / 2.0 + 0.3 * h
+        colliders = [Collider.cuboid((big, t, big), (0.0, 0.0, 0.0)),
+                     Collider.cuboid((t, big, big), (x0 - t, 0.0, 0.0)), Collider.cuboid((t, big, big), (x1 + t, 0.0, 0.0)),
+                     Collider.cuboid((big, big, t), (0.0, 0.0, z0 - t)), Collider.cuboid((big, big, t), (0.0, 0.0, z1 + t))]
+    else:
+        colliders = [Collider.cuboid((big, t), (0.0, 0.0), rotation=(0.0,)),
+                     Collider.cuboid((t, big), (x0 - t, 0.0), rotation=(0.0,)), Collider.cuboid((t, big), (x1 + t, 0.0), rotation=(0.0,))]
+    models = np.full(ps.n, MODEL_FLUID, np.uint8)
+    models[nf:] = solid_model
+    return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0), colliders=colliders,
+                cell_width=h, grid_capacity=4096, model=int(solid_model), fluid_gamma=float(gamma), models=models, solid_model=int(solid_model))
+
+
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):
     """The BASELINE.json configs as (possibly sharded) scenes for bench.py: `c2` neo-Hookean cube (1 M), `c3`
     Drucker-Prager sand column standing between the floor and four walls (4 M), `c4` corotated cube + kinematic rotating
