@@ -1,13 +1,19 @@
-"""np_oracle.py — second, independent CPU restatement of the MLS-MPM substep (numpy, fp64).
+"""np_oracle.py — second, independent CPU restatement of the MLS-MPM substep (numpy; fp64, or the dtype it is given).
 
 TEST INFRASTRUCTURE ONLY (imported by tests/ only). Parity unpinned, like
 mpm_oracle.c: the reference cannot be run here, so this twin exists to catch
 TRANSCRIPTION errors — it is written from Appendix A of SURVEY.md and the WGSL
-(cited per function, paths relative to /root/reference/src), with a different
+(cited per function, paths relative to the reference's src/), with a different
 algorithmic structure than the C oracle (vectorised per-particle SCATTER with
 np.add.at instead of the per-node gather over linked lists), dense dictionary
 grid instead of the hash map, numpy's LAPACK SVD instead of the Jacobi SVD.
 tests/test_oracle_twin.py requires both to agree to fp64 round-off.
+
+NpState._substep is the ONE collider-free transfer truth (stencil, P2G, grid update, G2P, speed cap, advection): it does not
+know the constitutive model. The model is the hook NpState._constitutive: the solids' here, the fluid's and the per-particle
+table's in tests/fluid_truth.py and tests/mixed_truth.py. float64 is the truth; float32 is the error that a plain restatement
+of the same formulae makes in the step's own precision (helpers.assert_close_to_truth's `ref32`). Also here, for every truth
+module of tests/: the stencil and block enumerations and the column-major matrix views.
 
 No colliders (CPIC) here: those paths are cross-checked by invariants instead.
 """
@@ -15,7 +21,6 @@ from __future__ import annotations
 
 import numpy as np
 
-# grid/kernel.wgsl:22-50 (3D) / :7-17 (2D): the neighbourhood is {0,1,2}^D
 MODEL_COROTATED, MODEL_NEO_HOOKEAN = 0, 1
 
 
@@ -30,12 +35,38 @@ def eval_all(x: np.ndarray) -> np.ndarray:
     return np.stack([0.5 * (1.5 - x) ** 2, 0.75 - (x - 1.0) ** 2, 0.5 * (x - 0.5) ** 2], axis=-1)
 
 
-def _mat(a: np.ndarray, d: int) -> np.ndarray:
-    """column-major [n, d*d] -> [n, d(row), d(col)]"""
-    return a.reshape(-1, d, d).transpose(0, 2, 1)
+def cube(k: int, d: int) -> np.ndarray:
+    """{0..k-1}^d as [k^d, d] rows, the last axis fastest"""
+    return np.stack(np.meshgrid(*([np.arange(k)] * d), indexing="ij"), -1).reshape(-1, d)
 
 
-def _unmat(m: np.ndarray) -> np.ndarray:
+def shifts_of(d: int) -> np.ndarray:
+    """grid/kernel.wgsl:22-50 (3D) / :7-17 (2D): the neighbourhood is {0,1,2}^D"""
+    return cube(3, d)
+
+
+def bw_of(d: int) -> int:
+    return 8 if d == 2 else 4
+
+
+def block_cells(blocks: np.ndarray, d: int) -> np.ndarray:
+    """world cells of every node of the given blocks [B, d], sorted lexicographically"""
+    bw = bw_of(d)
+    cells = (blocks[:, None, :] * bw + cube(bw, d)[None, :, :]).reshape(-1, d)
+    return cells[np.lexsort(cells.T[::-1])]
+
+
+def mat(a, d: int, dtype=None) -> np.ndarray:
+    """column-major [n, d*d] -> [n, d(row), d(col)], in `dtype` (None: the array's own)"""
+    return np.asarray(a, dtype).reshape(-1, d, d).transpose(0, 2, 1)
+
+
+def mat64(a, d: int) -> np.ndarray:
+    """mat in fp64, whatever it is given"""
+    return mat(a, d, np.float64)
+
+
+def unmat(m: np.ndarray) -> np.ndarray:
     n, d, _ = m.shape
     return m.transpose(0, 2, 1).reshape(n, d * d)
 
@@ -102,52 +133,59 @@ def drucker_prager_project(dp, state, F):
 
 
 class NpState:
-    """fp64 particle state + one substep (no colliders)."""
+    """Particle state + one substep in `dtype` (no colliders). The transfers are model-blind; `_constitutive` is the model."""
 
-    def __init__(self, particles, params, cell_width, model=0):
+    def __init__(self, particles, params, cell_width, model=0, dtype=np.float64):
         self.d = particles.dim
-        f = lambda a: np.asarray(a, np.float64).copy()
+        self.dtype = np.dtype(dtype)
+        f = lambda a: np.asarray(a, np.float64).astype(self.dtype)        # (the inputs are fp32 values: exact in either dtype)
+        f64 = lambda a: np.asarray(a, np.float64).copy()
         self.pos, self.vel = f(particles.pos), f(particles.vel)
         self.F, self.C = f(particles.def_grad), f(particles.affine)
         self.mass, self.vol = f(particles.mass), f(particles.init_volume)
         self.lam, self.mu = f(particles.lambda_), f(particles.mu)
-        self.dp, self.dp_state, self.phase = f(particles.dp), f(particles.dp_state), f(particles.phase)
-        self.g = np.asarray(list(params.gravity), np.float64)
+        self.dp, self.dp_state, self.phase = f64(particles.dp), f64(particles.dp_state), f64(particles.phase)   # plasticity: fp64 only
+        self.g = f(list(params.gravity))
         self.dt = float(params.dt)
         self.h = float(cell_width)
+        self.dt_t, self.h_t = self.dtype.type(self.dt), self.dtype.type(self.h)
         self.model = int(model)
         self.grid = {}
+        self.cells0 = self.last_grad = None
 
     def step(self, n=1):
         for _ in range(n):
             self._substep()
 
     def _substep(self):
-        d, h, dt = self.d, self.h, self.dt
+        d, T = self.d, self.dtype
+        t = T.type
+        h, dt = self.h_t, self.dt_t
         n = self.pos.shape[0]
-        cell = assoc_cell(self.pos.astype(np.float32), h)               # [n, d] associated cell (bit-exact rule)
-        ref = cell * h - self.pos                                         # dir_to_associated_grid_node
-        w = eval_all(-ref / h)                                            # [n, d, 3]
-        shifts = np.stack(np.meshgrid(*([np.arange(3)] * d), indexing="ij"), -1).reshape(-1, d)  # [3^d, d]
+        cell = assoc_cell(self.pos.astype(np.float32), self.h)            # [n, d] associated cell (the bit-exact rule, on the fp32 position)
+        self.cells0 = cell
+        ref = cell.astype(T) * h - self.pos                               # dir_to_associated_grid_node
+        w = eval_all(-ref / h).astype(T)                                  # [n, d, 3]
+        shifts = shifts_of(d)                                             # [3^d, d]
         # weights and offsets of the 3^d nodes of every particle
-        wn = np.ones((n, len(shifts)))
+        wn = np.ones((n, len(shifts)), T)
         for k in range(d):
             wn *= w[:, k, shifts[:, k]]
-        dpt = ref[:, None, :] + shifts[None, :, :] * h                    # node - particle  [n, S, d]
+        dpt = ref[:, None, :] + shifts[None, :, :].astype(T) * h          # node - particle  [n, S, d]
         node = cell[:, None, :] + shifts[None, :, :]                      # [n, S, d] world node coordinates
         # ---- P2G (p2g.wgsl:176-236): node += w * (C' dpt + m v, m)
-        Cm = _mat(self.C, d)
+        Cm = mat(self.C, d)
         mom = np.einsum("nrc,nsc->nsr", Cm, dpt) + (self.mass[:, None] * self.vel)[:, None, :]
         lo = node.reshape(-1, d).min(0)
         ext = node.reshape(-1, d).max(0) - lo + 1
         flat = np.ravel_multi_index(tuple((node - lo).reshape(-1, d).T), tuple(ext)).reshape(n, -1)
-        gm = np.zeros((int(np.prod(ext)), d))
-        gmass = np.zeros(int(np.prod(ext)))
+        gm = np.zeros((int(np.prod(ext)), d), T)
+        gmass = np.zeros(int(np.prod(ext)), T)
         np.add.at(gm, flat.reshape(-1), (mom * wn[:, :, None]).reshape(-1, d))
         np.add.at(gmass, flat.reshape(-1), (self.mass[:, None] * wn).reshape(-1))
         # ---- grid update (grid_update.wgsl:55-64)
         with np.errstate(divide="ignore", invalid="ignore"):
-            inv = np.where(gmass > 0, 1.0 / gmass, 0.0)
+            inv = np.where(gmass > 0, t(1.0) / gmass, t(0.0)).astype(T)
         gv = (gm + gmass[:, None] * self.g[None, :] * dt) * inv[:, None]
         gv = np.clip(gv, -h / dt, h / dt)
         # keep the grid for comparisons (only nodes of active blocks matter; compared by coordinate)
@@ -155,15 +193,26 @@ class NpState:
         # ---- G2P (g2p.wgsl:150-218)
         nv = gv[flat]                                                     # [n, S, d]
         vel = np.einsum("ns,nsr->nr", wn, nv)
-        invd = 4.0 / (h * h)
-        grad = invd * np.einsum("ns,nsr,nsc->nrc", wn, nv, dpt)          # [n, r, c]
+        invd = t(4.0) / (h * h)
+        grad = invd * np.einsum("ns,nsr,nsc->nrc", wn, nv, dpt)           # G [n, r, c]
         # ---- particle update (particle_update.wgsl:66-132), no colliders
         speed = np.linalg.norm(vel, axis=1)
         too_fast = speed > h / dt
         vel[too_fast] = vel[too_fast] / speed[too_fast, None] * h / dt
         self.pos = self.pos + vel * dt
-        Fm = _mat(self.F, d)
-        Fm = Fm + (grad * dt) @ Fm
+        tau = self._constitutive(grad)
+        Cn = grad * self.mass[:, None, None] - tau * (self.vol * invd * dt)[:, None, None]
+        assert vel.dtype == T and Cn.dtype == T and self.pos.dtype == T and self.F.dtype == T
+        self.vel = vel
+        self.C = unmat(Cn)
+        self.last_grad = grad
+
+    def _constitutive(self, grad):
+        """The model's part of the particle update: advances F (and what else the model keeps) by the velocity gradient `grad`
+        [n, r, c] and returns the Kirchhoff stress [n, r, c]. Here: the solids (F <- F + dt G F, fracture, Drucker-Prager)."""
+        d = self.d
+        Fm = mat(self.F, d)
+        Fm = Fm + (grad * self.dt_t) @ Fm
         phase = self.phase[:, 0].copy()
         max_stretch = self.phase[:, 1]
         chk = (phase > 0) & (max_stretch > 0)
@@ -174,15 +223,13 @@ class NpState:
             phase[idx] = 0.0
         plastic = phase == 0.0
         if plastic.any():
+            assert self.dtype == np.float64, "the plastic path is fp64 only"
             Fp, st = drucker_prager_project(self.dp[plastic], self.dp_state[plastic], Fm[plastic])
             Fm[plastic] = Fp
             self.dp_state[plastic] = st
         self.phase[:, 0] = phase
-        tau = kirchoff_stress(self.model, self.lam, self.mu, Fm)
-        Cn = grad * self.mass[:, None, None] - tau * (self.vol * invd * dt)[:, None, None]
-        self.vel = vel
-        self.F = _unmat(Fm)
-        self.C = _unmat(Cn)
+        self.F = unmat(Fm)
+        return kirchoff_stress(self.model, self.lam, self.mu, Fm).astype(self.dtype)   # (its np.eye is fp64: rounded back once)
 
     def grid_at(self, cells: np.ndarray):
         """(velocity, mass) of the given world node coordinates (zeros outside the touched box)."""
@@ -195,6 +242,29 @@ class NpState:
         vel[ok] = g["vel"][flat]
         mass[ok] = g["mass"][flat]
         return vel, mass
+
+    # -- what the GPU read-backs are compared with
+    def active_blocks(self):
+        """Virtual ids of the blocks active in the last substep (grid.wgsl:300-320: the block of every particle's associated cell
+        and its "+" neighbours), sorted lexicographically, and the particle count of each."""
+        b = np.floor_divide(self.cells0, bw_of(self.d))
+        own, cnt = np.unique(b, axis=0, return_counts=True)
+        allb = np.unique((own[:, None, :] + cube(2, self.d)[None, :, :]).reshape(-1, self.d), axis=0)
+        allb = allb[np.lexsort(allb.T[::-1])]
+        counts = {tuple(k): int(c) for k, c in zip(own.tolist(), cnt.tolist())}
+        return allb, np.array([counts.get(tuple(k), 0) for k in allb.tolist()], np.uint32)
+
+    def grid_records(self):
+        """(cells, velocity|mass) of every node of the active blocks, sorted by cell like MpmData.read_grid."""
+        cells = block_cells(self.active_blocks()[0], self.d)
+        v, m = self.grid_at(cells)
+        return cells.astype(np.int32), np.concatenate([v, m[:, None]], 1)
+
+    def kinetic(self):
+        return float(0.5 * np.sum(np.asarray(self.mass, np.float64) * np.sum(np.asarray(self.vel, np.float64) ** 2, 1)))
+
+    def momentum(self):
+        return np.sum(np.asarray(self.mass, np.float64)[:, None] * np.asarray(self.vel, np.float64), 0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -209,7 +279,7 @@ def prep_instances(pos, vel, def_grad, cdf_normal, cdf_dist, cdf_affinity, mode,
     n, d = pos.shape
     out = np.zeros((n, 24))
     m = np.tile(np.eye(3), (n, 1, 1))                       # [n, row, col]
-    m[:, :d, :d] = _mat(np.asarray(def_grad, np.float64), d)
+    m[:, :d, :d] = mat64(def_grad, d)
     for c in range(3):
         out[:, 4 * c:4 * c + 3] = m[:, :, c]
     out[:, 12:12 + d] = pos
@@ -218,7 +288,7 @@ def prep_instances(pos, vel, def_grad, cdf_normal, cdf_dist, cdf_affinity, mode,
     if mode == RENDER_VELOCITY:
         col[:, :d] = np.abs(vel) * dt * 100.0 + 0.2
     elif mode == RENDER_VOLUME:
-        S = np.linalg.svd(_mat(np.asarray(def_grad, np.float64), d), compute_uv=False)   # descending
+        S = np.linalg.svd(mat64(def_grad, d), compute_uv=False)   # descending
         col[:, :d] = (1.0 - S) / 0.005 + 0.2
     elif mode == RENDER_CDF_NORMALS:
         zero = np.all(cdf_normal == 0.0, axis=1)

@@ -22,7 +22,7 @@ import numpy as np
 
 import transfer_truth as T
 from helpers import report_margin
-from oracle.np_oracle import assoc_cell, eval_all
+from oracle.np_oracle import assoc_cell, block_cells, eval_all
 
 U32 = T.U32
 NONE = 0xFFFFFFFF
@@ -439,9 +439,7 @@ def active_cells(pos32, h, d):
     blk = assoc_cell(np.asarray(pos32, np.float32), h) // bw
     offs = np.unique(T.shifts_of(d) % 2, axis=0)
     blocks = np.unique((blk[:, None, :] + offs[None, :, :]).reshape(-1, d), axis=0)
-    loc = np.stack(np.meshgrid(*([np.arange(bw)] * d), indexing="ij"), -1).reshape(-1, d)
-    cells = (blocks[:, None, :] * bw + loc[None, :, :]).reshape(-1, d)
-    return cells[np.lexsort(cells.T[::-1])]
+    return block_cells(blocks, d)
 
 
 # ------------------------------------------------------------------------------------------------ scenes

@@ -19,6 +19,7 @@ import itertools
 import numpy as np
 
 from helpers import report_margin
+from oracle.np_oracle import mat64 as mat, unmat
 
 U32 = 2.0 ** -24          # unit round-off of fp32
 CUTOFF = 1.0e-7           # device_math.h svd: a singular value at or below CUTOFF * s_max is set to 0 (its U column rebuilt)
@@ -33,16 +34,6 @@ C_TAU = 64        # Kirchhoff stress, normwise
 C_DP = 128        # Drucker-Prager outputs (log, exp, sin on top of the SVD)
 C_DEC = 64        # width of the band around a discrete threshold inside which fp32 and fp64 may decide differently
 VEC_MAX_BOUND = 0.25   # singular vectors are compared only where the gap makes their bound smaller than this
-
-
-def mat(a, d):
-    """column-major [n, d*d] -> [n, row, col] float64"""
-    return np.asarray(a, np.float64).reshape(-1, d, d).transpose(0, 2, 1)
-
-
-def unmat(m):
-    n, d, _ = m.shape
-    return np.ascontiguousarray(m.transpose(0, 2, 1)).reshape(n, d * d)
 
 
 def rotations(rng, n, d):

@@ -3,15 +3,12 @@ sum in numpy float64, the fixed-point sums as Python integers, the bounds, and t
 the definitions of the header, nothing else. Takes ParticleSets (wgs_read_particles order and conventions: matrices column-major)."""
 import numpy as np
 
+from oracle.np_oracle import mat64 as _mat
+
 MODEL_COROTATED, MODEL_NEO_HOOKEAN = 0, 1
 SUM_COMPONENTS_3D = dict(mass=1, momentum=3, angular=3, mass_moment=3, kinetic=1, kinetic_affine=1, elastic=1, gravity_potential=1)
 U64 = np.uint64
 GOLDEN, SECOND = U64(0x9e3779b97f4a7c15), U64(0xd1b54a32d192ed03)
-
-
-def _mat(a, d):
-    """column-major [n, d*d] -> [n, row, col]"""
-    return np.asarray(a, np.float64).reshape(-1, d, d).transpose(0, 2, 1)
 
 
 # ---------------------------------------------------------------------------------------------- elastic energy

@@ -1,7 +1,8 @@
 """Truth of a simulation with per-particle constitutive models (MpmData.set_particle_models; include/wgsparkl_hip.h): the substep of
-tests/fluid_truth.py with the particle update chosen row by row — fluid rows advance J and take the Tait / viscous stress exactly as
-FluidState does, solid rows take F <- F + dt G F and oracle/np_oracle.py's kirchoff_stress of the solid's model. The transfers do not
-know the model, so everything else is FluidState's, statement for statement: an all-fluid mask reproduces it array for array.
+oracle/np_oracle.py with the particle update chosen row by row — fluid rows advance J and take the Tait / viscous stress exactly as
+tests/fluid_truth.py's FluidState does, solid rows take F <- F + dt G F and oracle/np_oracle.py's kirchoff_stress of the solid's model.
+The transfers do not know the model: they are NpState's own, and only the constitutive hook is here. An all-fluid mask reproduces
+FluidState array for array, an all-solid one NpState.
 
 TEST INFRASTRUCTURE ONLY. No colliders. float64 is the truth, float32 the error a plain restatement makes in the step's own precision
 (helpers.assert_close_to_truth's `ref32`). Also here: the coupled scenes the GPU parity test runs, and their two truths, computed once."""
@@ -10,7 +11,7 @@ import functools
 import numpy as np
 
 from fluid_truth import FluidState, advance_j, fluid_def_grad, kirchhoff
-from oracle.np_oracle import _mat, _unmat, assoc_cell, eval_all, kirchoff_stress
+from oracle.np_oracle import kirchoff_stress, mat, unmat
 from wgsparkl_amd import scenes
 from wgsparkl_amd.models import MODEL_FLUID, ElasticCoefficients, ParticlePhase
 from wgsparkl_amd.solver import ParticleSet, SimulationParams
@@ -32,67 +33,23 @@ class MixedState(FluidState):
         """The table MpmData.set_particle_models takes."""
         return np.where(self.fluid, MODEL_FLUID, self.solid_model).astype(np.uint8)
 
-    def _substep(self):
-        d, T = self.d, self.dtype
-        t = T.type
-        h, dt = self.h_t, self.dt_t
-        n = self.pos.shape[0]
-        cell = assoc_cell(self.pos.astype(np.float32), self.h)
-        self.cells0 = cell
-        ref = cell.astype(T) * h - self.pos
-        w = eval_all(-ref / h).astype(T)
-        shifts = np.stack(np.meshgrid(*([np.arange(3)] * d), indexing="ij"), -1).reshape(-1, d)
-        wn = np.ones((n, len(shifts)), T)
-        for k in range(d):
-            wn *= w[:, k, shifts[:, k]]
-        dpt = ref[:, None, :] + shifts[None, :, :].astype(T) * h
-        node = cell[:, None, :] + shifts[None, :, :]
-        # ---- P2G
-        Cm = _mat(self.C, d)
-        mom = np.einsum("nrc,nsc->nsr", Cm, dpt) + (self.mass[:, None] * self.vel)[:, None, :]
-        lo = node.reshape(-1, d).min(0)
-        ext = node.reshape(-1, d).max(0) - lo + 1
-        flat = np.ravel_multi_index(tuple((node - lo).reshape(-1, d).T), tuple(ext)).reshape(n, -1)
-        gm = np.zeros((int(np.prod(ext)), d), T)
-        gmass = np.zeros(int(np.prod(ext)), T)
-        np.add.at(gm, flat.reshape(-1), (mom * wn[:, :, None]).reshape(-1, d))
-        np.add.at(gmass, flat.reshape(-1), (self.mass[:, None] * wn).reshape(-1))
-        # ---- grid update
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = np.where(gmass > 0, t(1.0) / gmass, t(0.0)).astype(T)
-        gv = (gm + gmass[:, None] * self.g[None, :] * dt) * inv[:, None]
-        gv = np.clip(gv, -h / dt, h / dt)
-        self.grid = dict(lo=lo, ext=ext, vel=gv, mass=gmass)
-        # ---- G2P
-        nv = gv[flat]
-        vel = np.einsum("ns,nsr->nr", wn, nv)
-        invd = t(4.0) / (h * h)
-        grad = invd * np.einsum("ns,nsr,nsc->nrc", wn, nv, dpt)
-        # ---- particle update, no colliders: by the row's own model
-        speed = np.linalg.norm(vel, axis=1)
-        too_fast = speed > h / dt
-        vel[too_fast] = vel[too_fast] / speed[too_fast, None] * h / dt
-        self.pos = self.pos + vel * dt
+    def _constitutive(self, grad):
+        """by the row's own model"""
+        d, T, dt = self.d, self.dtype, self.dt_t
         fl, so = self.fluid, ~self.fluid
-        tau = np.zeros((n, d, d), T)
-        F = self.F.copy()
+        tau = np.zeros((len(fl), d, d), T)
         if fl.any():
             J = advance_j(self.J[fl], grad[fl], dt)
             tau[fl] = kirchhoff(J, grad[fl], self.lam[fl], self.mu[fl], self.gamma)
             self.J[fl] = J
-            F[fl] = fluid_def_grad(J, d)
+            self.F[fl] = fluid_def_grad(J, d)
         if so.any():
-            Fm = _mat(self.F[so], d)
+            Fm = mat(self.F[so], d)
             Fm = Fm + (grad[so] * dt) @ Fm
             tau[so] = kirchoff_stress(self.solid_model, self.lam[so], self.mu[so], Fm).astype(T)   # (its np.eye is fp64: rounded back once)
-            F[so] = _unmat(Fm)
+            self.F[so] = unmat(Fm)
             self.J[so] = np.linalg.det(Fm).astype(T)
-        Cn = grad * self.mass[:, None, None] - tau * (self.vol * invd * dt)[:, None, None]
-        assert vel.dtype == T and Cn.dtype == T and F.dtype == T and self.pos.dtype == T
-        self.vel = vel
-        self.F = F
-        self.C = _unmat(Cn)
-        self.last_grad = grad
+        return tau
 
 
 # ------------------------------------------------------------------------------------------------ the coupled scenes

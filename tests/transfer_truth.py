@@ -19,7 +19,7 @@ import numpy as np
 
 import devmath_truth as DM
 from helpers import report_margin
-from oracle.np_oracle import assoc_cell, eval_all
+from oracle.np_oracle import assoc_cell, bw_of, eval_all, mat64 as mat, shifts_of, unmat
 
 U32 = 2.0 ** -24
 U64 = 2.0 ** -53
@@ -42,19 +42,6 @@ def node_key(cells):
     for j in range(1, c.shape[1]):
         k = (k << 21) | c[:, j]
     return k
-
-
-def shifts_of(d):
-    return np.stack(np.meshgrid(*([np.arange(3)] * d), indexing="ij"), -1).reshape(-1, d)
-
-
-def mat(a, d):
-    return np.asarray(a, np.float64).reshape(-1, d, d).transpose(0, 2, 1)
-
-
-def unmat(m):
-    n, d, _ = m.shape
-    return m.transpose(0, 2, 1).reshape(n, d * d)
 
 
 class Inputs:
@@ -318,10 +305,6 @@ def check_particles(tag, pt: Particles, got, model, fails, sel=None):
 GRAVITY = (1.5, -9.81, 2.5)      # every component non-zero: a kernel that uses g[1] on every axis, or skips one, differs
 DT = 1.0e-3
 OCCUPANCY = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 17, 31, 32, 33, 63, 64, 65)   # around the rounds of four ranks
-
-
-def bw_of(d):
-    return 8 if d == 2 else 4
 
 
 def _finish(pos, h, rng, vel=None, uniform=False, model=0, vel_scale=1.0):
