@@ -10,7 +10,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "wgsparkl_hip.h")).read()
 # function declarations: "<ret> wgs_name(" at the start of a statement (skips the "wgs_status (0 = ok)" prose)
-DECLARED = sorted(set(re.findall(r"^(?:const char \*|int32_t |uint32_t |void |wgs_status )(wgs_[a-z_]+)\(", HEADER, re.M)))
+PROTOTYPES = re.findall(r"^(const char \*|int32_t |uint32_t |void |wgs_status )(wgs_[a-z_]+)\(([^)]*)\)", HEADER, re.M)
+DECLARED = sorted(set(name for _, name, _ in PROTOTYPES))
 
 
 def test_header_declares_the_expected_surface():
@@ -30,6 +31,41 @@ def test_library_exports_every_declared_symbol(hip_libs, dim):
         assert hasattr(lib, name), f"libwgsparkl{dim}d_hip.so does not export {name}"
     assert set(hip_libs.EXPORTS) == set(DECLARED)
     assert lib.wgs_dim() == dim
+
+
+def _num_params(params: str) -> int:
+    """Parameter count of a C declaration's parameter list: `(void)` = 0, else one more than its top-level commas."""
+    params = re.sub(r"/\*.*?\*/", " ", params, flags=re.S).strip()
+    if params == "void":
+        return 0
+    assert params, "an empty parameter list is not a C prototype"
+    depth = commas = 0
+    for ch in params:
+        depth += ch in "(["
+        depth -= ch in ")]"
+        commas += ch == "," and depth == 0
+    return commas + 1
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_every_export_has_a_full_prototype(hip_libs, dim):
+    """Every entry point of the header carries explicit ctypes `argtypes` (as many as the declaration has parameters; `[]` for
+    `(void)`) and the `restype` of its declared return type: nothing is left to ctypes' defaults."""
+    lib, _ = hip_libs.load(dim)
+    restype_of = {"wgs_status": C.c_int32, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "const char *": C.c_char_p, "void": None}
+    declared = {name: (ret.strip(), params) for ret, name, params in PROTOTYPES}
+    assert len(declared) == len(PROTOTYPES), "a function is declared twice"
+    # a declaration the pattern above cannot read to its closing parenthesis would be missing here
+    starts = set(re.findall(r"^(?:const char \*|int32_t |uint32_t |void |wgs_status )(wgs_[a-z_]+)\(", HEADER, re.M))
+    assert starts == set(declared), sorted(starts ^ set(declared))
+    for name in hip_libs.EXPORTS:
+        assert name in declared, f"{name}: no declaration in the header parses"
+        ret, params = declared[name]
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name}: no argtypes"
+        assert len(fn.argtypes) == _num_params(params), (name, len(fn.argtypes), params)
+        assert ret in restype_of, f"{name}: return type {ret!r} is not one this test knows"
+        assert fn.restype is restype_of[ret], (name, fn.restype, ret)
 
 
 @pytest.mark.parametrize("dim,size", [(3, 188), (2, 132)])

@@ -446,3 +446,43 @@ def test_native_sharded_step_over_rccl_one_rank(hip_libs):
     assert sh2.num_particles() == ps.n
     sh2.close(); comm.close()
 
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_single_domain_data_and_a_lone_slab_answer_alike(hip_libs, dim):
+    """`MpmData` and `NativeShard` are one `wgs_data` handle (pipeline.DataHandle): the same small scene with a kinematic ball that
+    moves and spins, as single-domain data and as one slab without neighbours, answers `stats()` and `read_body_poses()` alike —
+    the same keys, `com` among them — before any substep and after two. Host glue only: the particles are the other tests' matter."""
+    from helpers import pipeline
+    from wgsparkl_amd import MpmData
+    from wgsparkl_amd.sharded import INT_MAX, INT_MIN, NativeShard
+    if dim == 3:
+        sc = scenes.neo_hookean_cube(n_side=8)                         # 512 particles, cells 20..24 x 8..12 x 20..24
+        ball = Collider.ball(1.5, (22.0, 5.5, 22.0), linvel=(0.5, 0.25, -0.75), angvel=(0.3, -0.2, 0.4))
+    else:
+        sc = scenes.elastic_block_2d(nx=22, ny=22, with_floor=False)   # 484 particles, cells 7..18 x 7..18
+        ball = Collider.ball(1.5, (12.0, 4.5), linvel=(0.5, 0.25, 0.0), angvel=(0.3,))
+    ps, cols = sc["particles"], [ball]
+    pipe = pipeline(dim)
+    data = MpmData.new(pipe, sc["params"], ps, cols, sc["cell_width"], sc["grid_capacity"], sc["model"])
+    slab = NativeShard(pipe, sc["params"], ps, np.arange(ps.n, dtype=np.uint32), cols, sc["cell_width"], sc["grid_capacity"],
+                       INT_MIN, INT_MAX, has_lower=False, has_upper=False, particle_capacity=ps.n, model=sc["model"], comm=None)
+
+    def alike(when):
+        data.sync()
+        slab.sync()
+        assert data.stats()["num_particles"] == slab.stats()["num_particles"] == ps.n, when
+        a, b = data.read_body_poses(), slab.read_body_poses()
+        assert len(a) == len(b) == 1
+        assert set(a[0]) == set(b[0]) == {"rotation", "translation", "linvel", "angvel", "com"}, when
+        for key in a[0]:
+            assert a[0][key].shape == b[0][key].shape, (when, key)
+            err = max_abs(a[0][key], b[0][key])
+            print(f"dim {dim} {when}: body {key} abs difference {err:.3e} (bound {FUZZ_BODY_ATOL:g})")
+            assert err <= FUZZ_BODY_ATOL, (when, key, a[0][key], b[0][key])
+        return a[0]
+
+    start = alike("before any substep")
+    pipe.step(data, 2)
+    slab.step(2)
+    moved = alike("after two substeps")
+    assert not np.array_equal(moved["translation"], start["translation"]), "the ball must have moved"

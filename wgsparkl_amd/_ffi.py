@@ -16,24 +16,6 @@ ABI_VERSION = 7   # include/wgsparkl_hip.h WGS_ABI_VERSION
 WGS_NUM_PASSES = 10
 PASS_NAMES = ("update rigid particles", "grid sort", "grid_update_cdf", "p2g_cdf", "g2p_cdf", "p2g",
               "grid_update", "g2p", "particles_update", "integrate_bodies")  # src/pipeline.rs:201-271
-EXPORTS = (
-    "wgs_last_error", "wgs_dim", "wgs_pipeline_create", "wgs_pipeline_destroy", "wgs_data_create",
-    "wgs_data_destroy", "wgs_set_constitutive_model", "wgs_step", "wgs_sync", "wgs_set_sim_params",
-    "wgs_set_collider_poses", "wgs_set_body_velocities", "wgs_set_body_mass_properties", "wgs_read_body_poses", "wgs_set_plastic_state", "wgs_read_timing_overhead", "wgs_set_rigid_particles", "wgs_prep_vertex_buffer", "wgs_prep_vertex_buffer_device", "wgs_read_positions", "wgs_get_device_ptrs", "wgs_read_particles",
-    "wgs_read_grid", "wgs_read_blocks", "wgs_read_timings", "wgs_get_stats",
-    # multi-GPU (x-slab decomposition; new design, no reference counterpart)
-    "wgs_data_create_sharded", "wgs_shard_halo_record_bytes", "wgs_shard_particle_record_bytes",
-    "wgs_shard_buffer_header_bytes", "wgs_set_stream", "wgs_shard_export",
-    # one call per frame on sharded data (RCCL inside the library) + build identification
-    "wgs_comm_get_unique_id", "wgs_comm_create", "wgs_comm_destroy", "wgs_shard_attach", "wgs_sharded_step",
-    "wgs_sharded_step_lockstep", "wgs_build_info", "wgs_abi_version", "wgs_debug_scan", "wgs_set_grid_growth", "wgs_set_uniform_material",
-    # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
-    "wgs_read_diagnostics", "wgs_enqueue_diagnostics",
-    # WGS_MODEL_FLUID: the Tait exponent (same ABI version: older libraries of version 7 lack the symbol)
-    "wgs_set_fluid_eos",
-    # per-particle constitutive model (same ABI version again: detected by symbol lookup)
-    "wgs_set_particle_models", "wgs_read_particle_models",
-)
 
 
 class WgsError(RuntimeError):
@@ -141,6 +123,68 @@ class Diagnostics(C.Structure):
                 ("digest", C.c_uint64 * 2), ("what", C.c_uint32), ("model", C.c_uint32)]
 
 
+def prototypes(T):
+    """name -> (restype, argtypes) of every entry point of include/wgsparkl_hip.h, in the header's order; `T` = make_types(dim).
+    `[]` is `(void)`; `st` is wgs_status. Handles (wgs_pipeline / wgs_data / wgs_comm *) and untyped buffers are void pointers."""
+    P, vp, st, i32, u32, f32, size = C.POINTER, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
+    fp, u8p, u32p = P(f32), P(C.c_uint8), P(u32)
+    return {
+        "wgs_last_error": (C.c_char_p, []),
+        "wgs_dim": (i32, []),
+        "wgs_build_info": (C.c_char_p, []),
+        "wgs_abi_version": (u32, []),
+        "wgs_pipeline_create": (st, [i32, P(vp)]),
+        "wgs_pipeline_destroy": (None, [vp]),
+        "wgs_data_create": (st, [vp, P(T.SimParams), P(T.Particle), size, P(T.Collider), size, f32, u32, P(vp)]),
+        "wgs_data_destroy": (None, [vp]),
+        "wgs_set_constitutive_model": (st, [vp, i32]),
+        "wgs_set_fluid_eos": (st, [vp, f32]),
+        "wgs_set_particle_models": (st, [vp, u8p]),
+        "wgs_read_particle_models": (st, [vp, u8p]),
+        "wgs_step": (st, [vp, vp, u32, i32]),
+        "wgs_sync": (st, [vp]),
+        "wgs_set_sim_params": (st, [vp, P(T.SimParams)]),
+        "wgs_set_collider_poses": (st, [vp, P(T.Pose), fp, size]),
+        "wgs_set_body_velocities": (st, [vp, P(T.Velocity), size]),
+        "wgs_set_body_mass_properties": (st, [vp, P(T.MassProperties), size]),
+        "wgs_set_rigid_particles": (st, [vp, fp, vp, size, fp, u32p, size]),
+        "wgs_read_body_poses": (st, [vp, P(T.Pose), P(T.Velocity), fp, size]),
+        "wgs_read_positions": (st, [vp, fp]),
+        "wgs_get_device_ptrs": (st, [vp, P(DevicePtrs)]),
+        "wgs_read_particles": (st, [vp, P(T.Particle), P(T.PlasticState)]),
+        "wgs_prep_vertex_buffer": (st, [vp, u32, vp]),
+        "wgs_prep_vertex_buffer_device": (st, [vp, u32, vp]),
+        "wgs_set_plastic_state": (st, [vp, P(T.PlasticState)]),
+        "wgs_read_grid": (st, [vp, P(T.NodeRecord), size, P(size)]),
+        "wgs_read_blocks": (st, [vp, P(T.BlockRecord), size, P(size), u32p]),
+        "wgs_read_timings": (st, [vp, fp]),
+        "wgs_read_timing_overhead": (st, [vp, fp]),
+        "wgs_get_stats": (st, [vp, P(T.Stats)]),
+        "wgs_set_uniform_material": (st, [vp, f32, f32, f32, f32]),
+        "wgs_set_grid_growth": (st, [vp, i32]),
+        "wgs_debug_scan": (st, [vp, u32p, u32, u32p, u32p]),
+        # multi-GPU (x-slab decomposition; new design, no reference counterpart)
+        "wgs_data_create_sharded": (st, [vp, P(T.SimParams), P(T.Particle), size, u32p, P(T.Collider), size, f32, u32, u32,
+                                         i32, i32, i32, P(vp)]),
+        "wgs_shard_halo_record_bytes": (u32, []),
+        "wgs_shard_particle_record_bytes": (u32, []),
+        "wgs_shard_buffer_header_bytes": (u32, []),
+        "wgs_set_stream": (st, [vp, vp]),
+        "wgs_shard_export": (st, [vp, vp, u32, u32p]),
+        "wgs_comm_get_unique_id": (st, [C.c_char_p]),
+        "wgs_comm_create": (st, [vp, C.c_char_p, i32, i32, i32, P(vp)]),
+        "wgs_comm_destroy": (None, [vp]),
+        "wgs_shard_attach": (st, [vp, vp, i32, i32, u32, u32]),
+        "wgs_sharded_step": (st, [vp, vp, u32]),
+        "wgs_sharded_step_lockstep": (st, [vp, P(vp), u32, u32]),
+        # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
+        "wgs_read_diagnostics": (st, [vp, u32, P(Diagnostics)]),
+        "wgs_enqueue_diagnostics": (st, [vp, u32, vp]),
+    }
+
+
+EXPORTS = tuple(prototypes(make_types(3)))   # the names do not depend on the dimension
+
 _LIBS = {}
 
 
@@ -161,70 +205,11 @@ def load(dim: int):
         pass
     lib = C.CDLL(path)
     T = make_types(dim)
-    vp = C.c_void_p
-    lib.wgs_last_error.restype = C.c_char_p
-    lib.wgs_dim.restype = C.c_int32
-    lib.wgs_pipeline_create.argtypes = [C.c_int32, C.POINTER(vp)]
-    lib.wgs_pipeline_destroy.argtypes = [vp]
-    lib.wgs_pipeline_destroy.restype = None
-    lib.wgs_data_create.argtypes = [vp, C.POINTER(T.SimParams), C.POINTER(T.Particle), C.c_size_t,
-                                    C.POINTER(T.Collider), C.c_size_t, C.c_float, C.c_uint32, C.POINTER(vp)]
-    lib.wgs_data_destroy.argtypes = [vp]
-    lib.wgs_data_destroy.restype = None
-    lib.wgs_set_constitutive_model.argtypes = [vp, C.c_int32]
-    lib.wgs_set_fluid_eos.argtypes = [vp, C.c_float]
-    lib.wgs_set_particle_models.argtypes = [vp, C.POINTER(C.c_uint8)]
-    lib.wgs_read_particle_models.argtypes = [vp, C.POINTER(C.c_uint8)]
-    lib.wgs_step.argtypes = [vp, vp, C.c_uint32, C.c_int32]
-    lib.wgs_sync.argtypes = [vp]
-    lib.wgs_set_sim_params.argtypes = [vp, C.POINTER(T.SimParams)]
-    lib.wgs_set_collider_poses.argtypes = [vp, C.POINTER(T.Pose), C.POINTER(C.c_float), C.c_size_t]
-    lib.wgs_set_body_velocities.argtypes = [vp, C.POINTER(T.Velocity), C.c_size_t]
-    lib.wgs_set_body_mass_properties.argtypes = [vp, C.POINTER(T.MassProperties), C.c_size_t]
-    lib.wgs_read_body_poses.argtypes = [vp, C.POINTER(T.Pose), C.POINTER(T.Velocity), C.POINTER(C.c_float), C.c_size_t]
-    lib.wgs_read_positions.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.wgs_get_device_ptrs.argtypes = [vp, C.POINTER(DevicePtrs)]
-    lib.wgs_read_particles.argtypes = [vp, C.POINTER(T.Particle), C.POINTER(T.PlasticState)]
-    lib.wgs_set_plastic_state.argtypes = [vp, C.POINTER(T.PlasticState)]
-    lib.wgs_set_rigid_particles.argtypes = [vp, C.POINTER(C.c_float), vp, C.c_size_t, C.POINTER(C.c_float),
-                                            C.POINTER(C.c_uint32), C.c_size_t]
-    lib.wgs_prep_vertex_buffer.argtypes = [vp, C.c_uint32, vp]
-    lib.wgs_prep_vertex_buffer_device.argtypes = [vp, C.c_uint32, vp]
-    lib.wgs_read_grid.argtypes = [vp, C.POINTER(T.NodeRecord), C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.wgs_read_blocks.argtypes = [vp, C.POINTER(T.BlockRecord), C.c_size_t, C.POINTER(C.c_size_t),
-                                    C.POINTER(C.c_uint32)]
-    lib.wgs_read_timings.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.wgs_read_timing_overhead.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.wgs_get_stats.argtypes = [vp, C.POINTER(T.Stats)]
-    u32p = C.POINTER(C.c_uint32)
-    lib.wgs_data_create_sharded.argtypes = [vp, C.POINTER(T.SimParams), C.POINTER(T.Particle), C.c_size_t, u32p,
-                                            C.POINTER(T.Collider), C.c_size_t, C.c_float, C.c_uint32, C.c_uint32,
-                                            C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    lib.wgs_shard_halo_record_bytes.restype = C.c_uint32
-    lib.wgs_shard_particle_record_bytes.restype = C.c_uint32
-    lib.wgs_shard_buffer_header_bytes.restype = C.c_uint32
-    lib.wgs_set_stream.argtypes = [vp, vp]
-    lib.wgs_shard_export.argtypes = [vp, vp, C.c_uint32, u32p]
-    lib.wgs_build_info.restype = C.c_char_p
-    lib.wgs_abi_version.restype = C.c_uint32
+    for name, (restype, argtypes) in prototypes(T).items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)
         raise RuntimeError(f"{path}: ABI version {lib.wgs_abi_version()}, this binding mirrors {ABI_VERSION} — rebuild the library (csrc/build.sh)")
-    lib.wgs_set_grid_growth.argtypes = [vp, C.c_int32]
-    lib.wgs_set_uniform_material.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
-    lib.wgs_read_diagnostics.argtypes = [vp, C.c_uint32, C.POINTER(Diagnostics)]
-    lib.wgs_enqueue_diagnostics.argtypes = [vp, C.c_uint32, vp]
-    lib.wgs_debug_scan.argtypes = [vp, u32p, C.c_uint32, u32p, u32p]
-    lib.wgs_comm_get_unique_id.argtypes = [C.c_char_p]
-    lib.wgs_comm_create.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    lib.wgs_comm_destroy.argtypes = [vp]
-    lib.wgs_comm_destroy.restype = None
-    lib.wgs_shard_attach.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]
-    lib.wgs_sharded_step.argtypes = [vp, vp, C.c_uint32]
-    lib.wgs_sharded_step_lockstep.argtypes = [vp, C.POINTER(vp), C.c_uint32, C.c_uint32]
-    for name in EXPORTS:
-        fn = getattr(lib, name)
-        if fn.restype is C.c_int:  # default restype -> wgs_status
-            fn.restype = C.c_int32
     assert lib.wgs_dim() == dim
     _LIBS[dim] = (lib, T)
     return _LIBS[dim]

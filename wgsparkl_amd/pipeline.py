@@ -224,90 +224,48 @@ def _fill_collider(T, dst, c: Collider, D: int):
     dst.com = (C.c_float * 3)(*(com + [0.0] * (3 - len(com))))
 
 
-class MpmData:
-    """src/pipeline.rs:84-173. Owns every device buffer of one simulation."""
+class DataHandle:
+    """What is true of any `wgs_data *`, single-domain (`MpmData`) or one slab of a decomposition (`sharded.NativeShard`): the
+    setters, the body and diagnostics read-backs and the handle's lifetime. A subclass's constructor creates the data and stores
+    the handle in `self._h`."""
 
-    def __init__(self, pipeline: MpmPipeline, params: SimulationParams, particles: ParticleSet,
-                 colliders: Sequence[Collider], cell_width: float, grid_capacity: int,
-                 model: int = MODEL_COROTATED):
-        self.pipeline = pipeline
-        self.lib, self.T = pipeline.lib, pipeline.T
-        T, D = self.T, pipeline.dim
-        if particles.dim != D:
-            raise ValueError("particle dimension does not match the pipeline")
-        self.dim = D
-        self.n = particles.n
-        sp = T.SimParams()
-        sp.gravity = (C.c_float * D)(*params.gravity)
-        sp.dt = params.dt
-        raw = _pack_particles(T, particles)
-        cols = (T.Collider * max(1, len(colliders)))()
-        for i, c in enumerate(colliders):
-            _fill_collider(T, cols[i], c, D)
-        h = C.c_void_p()
-        _ffi.check(self.lib, self.lib.wgs_data_create(
-            pipeline._h, C.byref(sp), raw.ctypes.data_as(C.POINTER(T.Particle)), self.n,
-            cols, len(colliders), float(cell_width), int(grid_capacity), C.byref(h)))
-        self._h = h
+    def __init__(self, pipeline: MpmPipeline, colliders: Sequence[Collider]):
+        self.pipeline, self.lib, self.T, self.dim = pipeline, pipeline.lib, pipeline.T, pipeline.dim
         self.n_colliders = len(colliders)
-        if model != MODEL_COROTATED:
-            self.set_constitutive_model(model)
-        if any(_is_dynamic(c) for c in colliders):
-            self.set_body_mass_properties(colliders)
-        # mesh colliders: sampled on the host like GpuRigidParticles::from_rapier (sampling step = cell width)
-        from .sampling import build_rigid_particles
-        rb = build_rigid_particles(colliders, D, float(cell_width))
-        if rb is not None:
-            self.set_rigid_particles(rb)
+        self._h = None
 
-    @classmethod
-    def new(cls, pipeline, params, particles, colliders, cell_width, grid_capacity, model=MODEL_COROTATED):
-        """MpmData::new(device, params, &particles, &bodies, &colliders, cell_width, grid_capacity)
-        (src/pipeline.rs:98-128). `particles` may be a ParticleSet or a list of Particle."""
-        if not isinstance(particles, ParticleSet):
-            particles = ParticleSet.from_particles(particles)
-        return cls(pipeline, params, particles, colliders, cell_width, grid_capacity, model)
+    def _sim_params(self, params: SimulationParams):
+        sp = self.T.SimParams()
+        sp.gravity = (C.c_float * self.dim)(*params.gravity)
+        sp.dt = params.dt
+        return sp
+
+    def _collider_array(self, colliders: Sequence[Collider]):
+        cols = (self.T.Collider * max(1, len(colliders)))()
+        for i, c in enumerate(colliders):
+            _fill_collider(self.T, cols[i], c, self.dim)
+        return cols
 
     # -- host -> device writes the caller performs every frame (src_testbed/step.rs:79-119, ui.rs:91-104)
     def set_constitutive_model(self, model: int):
         _ffi.check(self.lib, self.lib.wgs_set_constitutive_model(self._h, int(model)))
 
     def set_fluid_eos(self, gamma: float):
-        """`wgs_set_fluid_eos`: the Tait exponent of MODEL_FLUID (default 7; finite and > 1). Stream-ordered."""
+        """`wgs_set_fluid_eos`: the Tait exponent of MODEL_FLUID (default 7; finite and > 1). Stream-ordered; every rank
+        of a sharded run passes the same value."""
         _ffi.check(self.lib, self.lib.wgs_set_fluid_eos(self._h, float(gamma)))
 
-    def set_particle_models(self, models):
-        """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —
-        fluid and solids in one simulation, coupled through the grid. `None` drops the table. Blocking."""
-        if models is None:
-            _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, None))
-            return
-        m = np.ascontiguousarray(models, np.uint8).reshape(-1)
-        if m.shape[0] != self.n:
-            raise ValueError("set_particle_models: one entry per particle")
-        _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
-
-    def read_particle_models(self) -> np.ndarray:
-        """`wgs_read_particle_models`: the model of every particle in the caller's order (np.uint8); the data's model without a table."""
-        out = np.zeros(self.n, np.uint8)
-        _ffi.check(self.lib, self.lib.wgs_read_particle_models(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out
-
     def set_sim_params(self, params: SimulationParams):
-        sp = self.T.SimParams()
-        sp.gravity = (C.c_float * self.dim)(*params.gravity)
-        sp.dt = params.dt
-        _ffi.check(self.lib, self.lib.wgs_set_sim_params(self._h, C.byref(sp)))
+        _ffi.check(self.lib, self.lib.wgs_set_sim_params(self._h, C.byref(self._sim_params(params))))
 
     def set_colliders(self, colliders: Sequence[Collider]):
         """Refresh poses + velocities of the coupled colliders."""
         n = len(colliders)
-        tmp = (self.T.Collider * max(1, n))()
+        tmp = self._collider_array(colliders)
         poses = (self.T.Pose * max(1, n))()
         vels = (self.T.Velocity * max(1, n))()
         coms = (C.c_float * (3 * max(1, n)))()
-        for i, c in enumerate(colliders):
-            _fill_collider(self.T, tmp[i], c, self.dim)
+        for i in range(n):
             poses[i] = tmp[i].pose
             vels[i] = tmp[i].velocity
             for k in range(3):
@@ -328,6 +286,13 @@ class MpmData:
             self._h, pts.ctypes.data_as(fp), ids.ctypes.data_as(C.c_void_p), len(pts), vtx.ctypes.data_as(fp),
             vcol.ctypes.data_as(up), len(vtx)))
 
+    def _set_mesh_samples(self, colliders: Sequence[Collider], cell_width: float):
+        """Mesh colliders are sampled on the host like GpuRigidParticles::from_rapier (sampling step = cell width)."""
+        from .sampling import build_rigid_particles
+        rb = build_rigid_particles(colliders, self.dim, float(cell_width))
+        if rb is not None:
+            self.set_rigid_particles(rb)
+
     def set_body_mass_properties(self, colliders: Sequence[Collider]):
         """GpuBodySet::from_rapier's local mass properties: all zero = kinematic, else two-way coupling."""
         n = len(colliders)
@@ -341,7 +306,8 @@ class MpmData:
 
     def read_body_poses(self):
         """poses_staging read-back (src_testbed/step.rs:129-132): one dict per collider with rotation
-        (3D quaternion (i,j,k,w); 2D (cos, sin)), translation, linvel, angvel, com as float64 arrays."""
+        (3D quaternion (i,j,k,w); 2D (cos, sin)), translation, linvel, angvel, com as float64 arrays.
+        Every rank of a sharded run integrates the same bodies, so any rank can be asked."""
         n, D = self.n_colliders, self.dim
         poses = (self.T.Pose * max(1, n))()
         vels = (self.T.Velocity * max(1, n))()
@@ -362,13 +328,79 @@ class MpmData:
 
     def diagnostics(self, what: int = _ffi.DIAG_PARTICLES) -> Diagnostics:
         """`wgs_read_diagnostics`: reproducible sums, bounds and the state digest of the state after the last enqueued substep,
-        reduced on the device (blocking; nothing but the small struct crosses PCIe). `what` = OR of _ffi.DIAG_*."""
+        reduced on the device (blocking; nothing but the small struct crosses PCIe). `what` = OR of _ffi.DIAG_*.
+        On a slab: over the slots this rank holds; counts, digests and `fixed` sums of equal exponent of the ranks add exactly, and
+        combining them is the caller's task."""
         return read_diagnostics(self.lib, self._h, self.dim, what)
 
     def enqueue_diagnostics(self, device_ptr: int, what: int = _ffi.DIAG_PARTICLES):
         """`wgs_enqueue_diagnostics`: the same, stream-ordered; the struct (`ctypes.sizeof(_ffi.Diagnostics)` bytes) is left at the
         DEVICE address `device_ptr`. Returns at once."""
         _ffi.check(self.lib, self.lib.wgs_enqueue_diagnostics(self._h, int(what), C.c_void_p(int(device_ptr))))
+
+    def stats(self):
+        s = self.T.Stats()
+        _ffi.check(self.lib, self.lib.wgs_get_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.wgs_data_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MpmData(DataHandle):
+    """src/pipeline.rs:84-173. Owns every device buffer of one simulation."""
+
+    def __init__(self, pipeline: MpmPipeline, params: SimulationParams, particles: ParticleSet,
+                 colliders: Sequence[Collider], cell_width: float, grid_capacity: int,
+                 model: int = MODEL_COROTATED):
+        super().__init__(pipeline, colliders)
+        if particles.dim != self.dim:
+            raise ValueError("particle dimension does not match the pipeline")
+        self.n = particles.n
+        raw = _pack_particles(self.T, particles)
+        h = C.c_void_p()
+        _ffi.check(self.lib, self.lib.wgs_data_create(
+            pipeline._h, C.byref(self._sim_params(params)), raw.ctypes.data_as(C.POINTER(self.T.Particle)), self.n,
+            self._collider_array(colliders), len(colliders), float(cell_width), int(grid_capacity), C.byref(h)))
+        self._h = h
+        if model != MODEL_COROTATED:
+            self.set_constitutive_model(model)
+        if any(_is_dynamic(c) for c in colliders):
+            self.set_body_mass_properties(colliders)
+        self._set_mesh_samples(colliders, cell_width)
+
+    @classmethod
+    def new(cls, pipeline, params, particles, colliders, cell_width, grid_capacity, model=MODEL_COROTATED):
+        """MpmData::new(device, params, &particles, &bodies, &colliders, cell_width, grid_capacity)
+        (src/pipeline.rs:98-128). `particles` may be a ParticleSet or a list of Particle."""
+        if not isinstance(particles, ParticleSet):
+            particles = ParticleSet.from_particles(particles)
+        return cls(pipeline, params, particles, colliders, cell_width, grid_capacity, model)
+
+    def set_particle_models(self, models):
+        """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —
+        fluid and solids in one simulation, coupled through the grid. `None` drops the table. Blocking."""
+        if models is None:
+            _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, None))
+            return
+        m = np.ascontiguousarray(models, np.uint8).reshape(-1)
+        if m.shape[0] != self.n:
+            raise ValueError("set_particle_models: one entry per particle")
+        _ffi.check(self.lib, self.lib.wgs_set_particle_models(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def read_particle_models(self) -> np.ndarray:
+        """`wgs_read_particle_models`: the model of every particle in the caller's order (np.uint8); the data's model without a table."""
+        out = np.zeros(self.n, np.uint8)
+        _ffi.check(self.lib, self.lib.wgs_read_particle_models(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
     def read_positions(self) -> np.ndarray:
         out = np.zeros((self.n, self.dim), F32)
@@ -448,19 +480,3 @@ class MpmData:
         ms = (C.c_float * _ffi.WGS_NUM_PASSES)()
         _ffi.check(self.lib, self.lib.wgs_read_timings(self._h, ms))
         return dict(zip(_ffi.PASS_NAMES, [float(x) for x in ms]))
-
-    def stats(self):
-        s = self.T.Stats()
-        _ffi.check(self.lib, self.lib.wgs_get_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.wgs_data_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

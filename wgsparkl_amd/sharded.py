@@ -23,11 +23,12 @@ import numpy as np
 
 from . import _ffi
 from .models import MODEL_COROTATED
-from .pipeline import MpmPipeline, _fill_collider, _pack_particles, read_diagnostics
+from .pipeline import DataHandle, MpmPipeline, _is_dynamic, _pack_particles
 from .solver import ParticleSet, SimulationParams
 
 INT_MIN, INT_MAX = -(2 ** 31), 2 ** 31 - 1
 MIN_INTERIOR_WIDTH = 3      # blocks; wgs_shard_attach refuses narrower slabs between two neighbours
+
 
 @dataclass
 class SlabPartition:
@@ -73,7 +74,6 @@ def associated_block_x(pos: np.ndarray, cell_width: float, dim: int) -> np.ndarr
     return np.floor(c / np.float32(bw)).astype(np.int64)
 
 
-
 # ------------------------------------------------------------------------------------------------
 # The substep driven from inside the library (include/wgsparkl_hip.h: wgs_comm_*, wgs_shard_attach,
 # wgs_sharded_step): what bench.py --gpus N and a Rust caller use.
@@ -111,7 +111,7 @@ class NativeComm:
             self._h = None
 
 
-class NativeShard:
+class NativeShard(DataHandle):
     """One slab as a Rust caller would hold it: a sharded `wgs_data` whose message buffers and substep protocol live
     in the library. `comm` = NativeComm (one process per GPU) or None (a slab of a lockstep group / no neighbours)."""
 
@@ -122,87 +122,37 @@ class NativeShard:
                  uniform_material=None):
         """`uniform_material` = (mass, init_volume, lambda, mu) shared by EVERY particle of EVERY rank (the caller's
         promise: a rank only sees its own), or None: the constants then travel with each particle."""
-        self.pipeline, self.lib, self.T = pipeline, pipeline.lib, pipeline.T
-        T, D = self.T, pipeline.dim
-        self.dim = D
+        super().__init__(pipeline, colliders)
         self.uniform_material = uniform_material
-        self.n_colliders = len(colliders)
-        sp = T.SimParams()
-        sp.gravity = (C.c_float * D)(*params.gravity)
-        sp.dt = params.dt
-        raw = _pack_particles(T, particles)
+        raw = _pack_particles(self.T, particles)
         gids = np.ascontiguousarray(global_ids, np.uint32)
-        cols = (T.Collider * max(1, len(colliders)))()
-        for i, c in enumerate(colliders):
-            _fill_collider(T, cols[i], c, D)
         h = C.c_void_p()
         cap = max(int(particle_capacity), particles.n)
         _ffi.check(self.lib, self.lib.wgs_data_create_sharded(
-            pipeline._h, C.byref(sp), raw.ctypes.data_as(C.POINTER(T.Particle)), particles.n,
-            gids.ctypes.data_as(C.POINTER(C.c_uint32)), cols, len(colliders), float(cell_width), int(grid_capacity),
-            cap, max(int(block_lo), INT_MIN), min(int(block_hi), INT_MAX), 1 if force_plastic else 0, C.byref(h)))
+            pipeline._h, C.byref(self._sim_params(params)), raw.ctypes.data_as(C.POINTER(self.T.Particle)), particles.n,
+            gids.ctypes.data_as(C.POINTER(C.c_uint32)), self._collider_array(colliders), len(colliders), float(cell_width),
+            int(grid_capacity), cap, max(int(block_lo), INT_MIN), min(int(block_hi), INT_MAX), 1 if force_plastic else 0, C.byref(h)))
         self._h = h
         self.capacity = cap
         if model != MODEL_COROTATED:
-            _ffi.check(self.lib, self.lib.wgs_set_constitutive_model(self._h, int(model)))
+            self.set_constitutive_model(model)
         if uniform_material is not None:
             _ffi.check(self.lib, self.lib.wgs_set_uniform_material(self._h, *[float(x) for x in uniform_material]))
-            _ffi.check(self.lib, self.lib.wgs_sync(self._h))       # (a particle with other constants is reported here)
-        if any(any(c.inv_mass) or any(c.inv_inertia_local) for c in colliders):   # dynamic bodies: two-way coupling
-            arr = (T.MassProperties * len(colliders))()
-            for i, c in enumerate(colliders):
-                arr[i].inv_mass = tuple(c.inv_mass)
-                arr[i].inv_inertia_local = tuple(c.inv_inertia_local)
-            _ffi.check(self.lib, self.lib.wgs_set_body_mass_properties(self._h, arr, len(colliders)))
+            self.sync()                                            # (a particle with other constants is reported here)
+        if any(_is_dynamic(c) for c in colliders):                 # dynamic bodies: two-way coupling
+            self.set_body_mass_properties(colliders)
         _ffi.check(self.lib, self.lib.wgs_shard_attach(self._h, comm._h if comm is not None else None, 1 if has_lower else 0,
                                                          1 if has_upper else 0, int(halo_capacity_records), int(migrant_capacity)))
-        # mesh colliders: sampled on the host like GpuRigidParticles::from_rapier; every rank holds every sample
-        from .sampling import build_rigid_particles
-        rb = build_rigid_particles(colliders, D, float(cell_width))
-        if rb is not None:
-            F32 = np.float32
-            pts, ids = np.ascontiguousarray(rb["local_pts"], F32), np.ascontiguousarray(rb["ids"], np.uint32)
-            vtx, vcol = np.ascontiguousarray(rb["local_vtx"], F32), np.ascontiguousarray(rb["vtx_collider"], np.uint32)
-            fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
-            _ffi.check(self.lib, self.lib.wgs_set_rigid_particles(self._h, pts.ctypes.data_as(fp), ids.ctypes.data_as(C.c_void_p), len(pts),
-                                                                  vtx.ctypes.data_as(fp), vcol.ctypes.data_as(up), len(vtx)))
+        self._set_mesh_samples(colliders, cell_width)              # every rank holds every sample
         self.part_rec = self.lib.wgs_shard_particle_record_bytes() // 4
         self.hdr = self.lib.wgs_shard_buffer_header_bytes() // 4
-
-    def set_fluid_eos(self, gamma: float):
-        """`wgs_set_fluid_eos` (every rank passes the same value)."""
-        _ffi.check(self.lib, self.lib.wgs_set_fluid_eos(self._h, float(gamma)))
 
     def step(self, num_substeps: int):
         """`wgs_sharded_step`: whole substeps incl. the neighbour exchange, asynchronous."""
         _ffi.check(self.lib, self.lib.wgs_sharded_step(self.pipeline._h, self._h, int(num_substeps)))
 
-    def sync(self):
-        _ffi.check(self.lib, self.lib.wgs_sync(self._h))
-
-    def stats(self):
-        s = self.T.Stats()
-        _ffi.check(self.lib, self.lib.wgs_get_stats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in s._fields_}
-
     def num_particles(self) -> int:
         return self.stats()["num_particles"]
-
-    def diagnostics(self, what: int = _ffi.DIAG_PARTICLES):
-        """`wgs_read_diagnostics` over the slots this rank holds. Counts, digests and `fixed` sums of equal exponent of the ranks add
-        exactly; combining them is the caller's task."""
-        return read_diagnostics(self.lib, self._h, self.dim, what)
-
-    def read_body_poses(self):
-        """Like MpmData.read_body_poses: every rank integrates the same bodies, any rank can be asked."""
-        n, D = self.n_colliders, self.dim
-        poses, vels = (self.T.Pose * max(1, n))(), (self.T.Velocity * max(1, n))()
-        coms = (C.c_float * (3 * max(1, n)))()
-        _ffi.check(self.lib, self.lib.wgs_read_body_poses(self._h, poses, vels, coms, n))
-        return [dict(rotation=np.array(list(poses[i].rotation)[:(2 if D == 2 else 4)], np.float64),
-                     translation=np.array(list(poses[i].translation)[:D], np.float64),
-                     linvel=np.array(list(vels[i].linear)[:D], np.float64),
-                     angvel=np.array(list(vels[i].angular)[:(1 if D == 2 else 3)], np.float64)) for i in range(n)]
 
     def export(self):
         """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now (blocking)."""
@@ -214,17 +164,6 @@ class NativeShard:
         _ffi.check(self.lib, self.lib.wgs_shard_export(self._h, C.c_void_p(buf.data_ptr()), self.capacity, C.byref(cnt)))
         rec = buf[self.hdr: self.hdr + cnt.value * self.part_rec].cpu().numpy().reshape(cnt.value, self.part_rec)
         return unpack_records(rec, self.dim, self.uniform_material if self.dim == 3 else None)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.wgs_data_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def native_lockstep(pipeline: MpmPipeline, shards: List[NativeShard], num_substeps: int):
