@@ -1,6 +1,9 @@
 """Shared helpers of the parity tests: run the same scene through the CPU oracle
 (fp32 restatement + fp64 "truth") and through the HIP path (C ABI), then compare
 by VIRTUAL ids (world cell coordinates), never by physical node index."""
+import contextlib
+import dataclasses
+import functools
 import os
 import re
 
@@ -13,14 +16,27 @@ _ORACLES = {}
 _LAYOUT_H = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wgsparkl_amd", "csrc", "layout.h")
 
 
+@functools.lru_cache(maxsize=None)
+def _debug_bits():
+    with open(_LAYOUT_H) as f:
+        return {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"^\s*DBG_(\w+) = 1u << (\d+),", f.read(), re.M)}
+
+
 def debug_switches(*names):
     """The WGS_DEBUG value that turns on the named developer switches: the DBG_* bits of layout.h, named without the prefix."""
-    with open(_LAYOUT_H) as f:
-        bits = {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"^\s*DBG_(\w+) = 1u << (\d+),", f.read(), re.M)}
+    bits = _debug_bits()
     value = 0
     for name in names:
         value |= bits[name]
     return str(value)
+
+
+@contextlib.contextmanager
+def debug(monkeypatch, *names):
+    """WGS_DEBUG = debug_switches(*names) inside the block; what was there before (a value, or nothing) after it."""
+    with monkeypatch.context() as m:
+        m.setenv("WGS_DEBUG", debug_switches(*names))
+        yield
 
 
 def oracle(dim, dtype):
@@ -48,14 +64,62 @@ def pipeline(dim):
     return _PIPES[dim]
 
 
-def run_gpu(scene, nsteps, timestamps=False):
-    ps = scene["particles"]
-    pipe = pipeline(ps.dim)
-    data = MpmData.new(pipe, scene["params"], ps, scene["colliders"], scene["cell_width"],
-                       scene["grid_capacity"], scene.get("model", 0))
-    pipe.step(data, nsteps, timestamps)
-    data.sync()
+def new_data(scene, **overrides):
+    """(pipeline, data) of a scene on the shared pipeline of its dimension; `overrides` as in MpmData.from_scene."""
+    pipe = pipeline(overrides.get("particles", scene["particles"]).dim)
+    return pipe, MpmData.from_scene(pipe, scene, **overrides)
+
+
+def step_chunks(scene_or_data, chunks, timestamps=False):
+    """One wgs_step call per entry of `chunks` with a wgs_sync after each, on existing data or on new data of a scene; returns the data."""
+    data = new_data(scene_or_data)[1] if isinstance(scene_or_data, dict) else scene_or_data
+    for k in chunks:
+        data.pipeline.step(data, k, timestamps)
+        data.sync()
     return data
+
+
+def run_gpu(scene, nsteps, timestamps=False):
+    return step_chunks(scene, (nsteps,), timestamps)
+
+
+# the read_particles() fields the bit-identity tests compare: the state a substep advances, + the affinity word of collider scenes,
+# + the plastic state, + the rest of the particle cdf
+BASE_FIELDS = ("pos", "vel", "def_grad", "affine")
+AFFINITY_FIELDS = BASE_FIELDS + ("cdf_affinity",)
+PLASTIC_FIELDS = AFFINITY_FIELDS + ("dp_state",)
+CDF_FIELDS = PLASTIC_FIELDS + ("cdf_normal", "cdf_dist")
+
+
+def assert_same_bits(a, b, fields, tag=None):
+    """np.array_equal field by field: -0.0 equals 0.0 and a NaN equals nothing, itself included."""
+    for f in fields:
+        assert np.array_equal(getattr(a, f), getattr(b, f)), f if tag is None else (tag, f)
+
+
+def assert_same_grid(ga, gb):
+    """two read_grid() tuples"""
+    assert len(ga) == len(gb), (len(ga), len(gb))
+    for k, (x, y) in enumerate(zip(ga, gb)):
+        assert np.array_equal(x, y), ("grid", k)
+
+
+def assert_same_bodies(ba, bb, keys=None):
+    """two read_body_poses() lists, by `keys` (default: every key of the first list's dicts)"""
+    assert len(ba) == len(bb), (len(ba), len(bb))
+    for i, (x, y) in enumerate(zip(ba, bb)):
+        for key in (x if keys is None else keys):
+            assert np.array_equal(np.asarray(x[key]), np.asarray(y[key])), (i, key)
+
+
+def restored_colliders(colliders, bodies, dim):
+    """The colliders a restarted run is created with: each at the pose and velocities of its read_body_poses() entry (2D poses are
+    handed over as an angle, linvel has three entries)."""
+    def restored(c, b):
+        rot = tuple(b["rotation"]) if dim == 3 else (float(np.arctan2(b["rotation"][1], b["rotation"][0])),)
+        return dataclasses.replace(c, translation=tuple(b["translation"]), rotation=rot, linvel=tuple(b["linvel"]) + (0.0,) * (3 - dim),
+                                   angvel=tuple(b["angvel"]), com=tuple(b["com"]))
+    return [restored(c, b) for c, b in zip(colliders, bodies)]
 
 
 def rel_rms(a, b):

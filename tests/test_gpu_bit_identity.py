@@ -3,13 +3,13 @@ binning inside the fused G2P or as a launch of its own, across a checkpoint / re
 import numpy as np
 import pytest
 
-from wgsparkl_amd import scenes
+from wgsparkl_amd import MpmData, scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
-from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
-                        _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
+from helpers import (AFFINITY_FIELDS, BASE_FIELDS, CDF_FIELDS, PLASTIC_FIELDS, assert_same_bits, assert_same_bodies, assert_same_grid, debug,
+                     new_data, pipeline, rel_rms, restored_colliders, run_gpu, step_chunks)
+from gpu_common import _random_scene, cloud_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -18,8 +18,7 @@ def test_determinism(hip_libs):
     sc = cloud_scene(n=30000, seed=11)
     a = run_gpu(sc, 5).read_particles()
     b = run_gpu(sc, 5).read_particles()
-    for name in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, name), getattr(b, name)), name
+    assert_same_bits(a, b, BASE_FIELDS)
 
 
 def test_uniform_material_mode_is_bit_identical(hip_libs, monkeypatch):
@@ -35,11 +34,9 @@ def test_uniform_material_mode_is_bit_identical(hip_libs, monkeypatch):
             data = run_gpu(sc, 30)
             return sc, data.read_particles(), data.read_grid()
         sc, a, ga = run()
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_UNIFORM"))
-        _, b, gb = run()
-        monkeypatch.delenv("WGS_DEBUG")
-        for f in ("pos", "vel", "def_grad", "affine", "mass", "init_volume", "lambda_", "mu", "cdf_affinity", "dp_state"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), f
+        with debug(monkeypatch, "NO_UNIFORM"):
+            _, b, gb = run()
+        assert_same_bits(a, b, PLASTIC_FIELDS + ("mass", "init_volume", "lambda_", "mu"))
         assert np.array_equal(a.mass, sc["particles"].mass) and np.array_equal(a.mu, sc["particles"].mu)
         assert np.array_equal(ga[0], gb[0]) and np.array_equal(ga[1], gb[1])
 
@@ -66,11 +63,9 @@ def test_uniform_plasticity_parameters_give_the_bits_of_the_general_layout(hip_l
             sc = dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0)[:dim], 5e-4), colliders=cols, cell_width=1.0, grid_capacity=4096, model=MODEL_COROTATED)
             return ps, run_gpu(sc, 30).read_particles()
         ps, a = run()
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_UNIFORM"))
-        _, b = run()
-        monkeypatch.delenv("WGS_DEBUG")
-        for f in ("pos", "vel", "def_grad", "affine", "dp", "dp_state", "phase"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), (kind, f)
+        with debug(monkeypatch, "NO_UNIFORM"):
+            _, b = run()
+        assert_same_bits(a, b, BASE_FIELDS + ("dp", "dp_state", "phase"), kind)
         assert np.array_equal(a.dp, ps.dp) and np.array_equal(a.phase[:, 1], ps.phase[:, 1]), kind
         assert (a.dp_state != np.array([1.0, 1.0, 0.0], np.float32)).any() and (kind == 3 or (a.phase[:, 0] == 0.0).any()), "the scene should have yielded and broken by now"
 
@@ -89,11 +84,9 @@ def test_g2p_launch_shapes_are_bit_identical(hip_libs, monkeypatch):
             sc["particles"].vel[:, 0] = 1.5
             return run_gpu(sc, 25).read_particles()
         a = run()
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_PASSES"))
-        b = run()
-        monkeypatch.delenv("WGS_DEBUG")
-        for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), f
+        with debug(monkeypatch, "G2P_TWO_PASSES"):
+            b = run()
+        assert_same_bits(a, b, PLASTIC_FIELDS)
 
 
 @pytest.mark.parametrize("seed", [1, 4, 9, 12])
@@ -103,31 +96,22 @@ def test_binning_inside_the_fused_g2p_is_bit_identical_to_the_rebin_launch(hip_l
     REBIN_LAUNCH brings k_rebin back. The sort is only a permutation with a canonical order inside a cell, so 150 substeps — random
     colliders, particles flying through blocks, two table rebuilds, the calls cut at odd places with a wgs_sync between them —
     must end bit-identical, particles, grid, block set and counts; and both must have counted the same cell-changers."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     monkeypatch.setenv("WGS_REHASH_PERIOD", "64")             # (developer override, same results; the default is 1024)
 
     def run():
-        sc = _random_scene(seed)
-        pipe = pipeline(sc["particles"].dim)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for k in (1, 7, 63, 2, 77):
-            pipe.step(data, k)
-            data.sync()
+        data = step_chunks(_random_scene(seed), (1, 7, 63, 2, 77))
         return data.read_particles(), data.read_grid(), data.read_blocks(), data.stats()
     a, ga, ka, sa = run()
     # (... and launch 2 of the sort puts the members of a dirty block's cells in order by ranking the newcomers among the stayers;
     # WGS_DEBUG CELL_INSERTION_SORT keeps the insertion sort that covers the cases the ranking does not: the same order)
     for switch in ("REBIN_LAUNCH", "CELL_INSERTION_SORT"):
-        monkeypatch.setenv("WGS_DEBUG", debug_switches(switch))
-        b, gb, kb, sb = run()
-        for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), (switch, f)
-        for x, y in zip(ga, gb):
-            assert np.array_equal(x, y)
-        assert np.array_equal(ka[0], kb[0]) and np.array_equal(ka[2], kb[2])   # (block set and counts; where a block sits in memory is up to the atomics)
-        assert sa["cell_changers"] == sb["cell_changers"] and sa["cell_changers"] > 0
-        assert sa["overflow"] == 0 and sb["overflow"] == 0
+        with debug(monkeypatch, switch):
+            b, gb, kb, sb = run()
+            assert_same_bits(a, b, PLASTIC_FIELDS, switch)
+            assert_same_grid(ga, gb)
+            assert np.array_equal(ka[0], kb[0]) and np.array_equal(ka[2], kb[2])   # (block set and counts; where a block sits in memory is up to the atomics)
+            assert sa["cell_changers"] == sb["cell_changers"] and sa["cell_changers"] > 0
+            assert sa["overflow"] == 0 and sb["overflow"] == 0
 
 
 @pytest.mark.parametrize("which", ["dynamic_ball_and_polyline_2d", "cube_on_floor_3d", "sand_between_walls_3d"])
@@ -137,9 +121,6 @@ def test_data_stepped_concurrently_on_their_own_streams_stay_bit_identical(hip_l
     progress, and hand over complete data, also while kernels of other data occupy the device. Four copies of a scene are
     stepped interleaved, no synchronisation between the calls (their kernels overlap), and must end with the same bits as a
     copy that ran alone; nobody may report a hand-over time-out."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
-
     def make():
         if which == "dynamic_ball_and_polyline_2d":
             sc = _random_scene(1)          # a dynamic ball pushed to its velocity cap, a kinematic cuboid, a moving polyline
@@ -149,8 +130,7 @@ def test_data_stepped_concurrently_on_their_own_streams_stay_bit_identical(hip_l
             sc["particles"].vel[:, 0] = 1.5
         else:
             sc = scenes.sand_column(nx=12, ny=20, nz=12, with_floor=True)
-        pipe = pipeline(sc["particles"].dim)
-        return pipe, MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+        return new_data(sc)
     pipe, alone = make()
     for k in (3, 17, 20):
         pipe.step(alone, k)
@@ -163,9 +143,7 @@ def test_data_stepped_concurrently_on_their_own_streams_stay_bit_identical(hip_l
                 pipe.step(c, 1)
     for c in copies:
         c.sync()                 # (raises on ERRBIT_HANDOVER)
-        got = c.read_particles()
-        for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-            assert np.array_equal(getattr(got, f), getattr(ref, f)), f
+        assert_same_bits(c.read_particles(), ref, PLASTIC_FIELDS)
         assert c.stats()["overflow"] == 0
 
 
@@ -184,34 +162,22 @@ def test_grid_update_inside_the_p2g_launch_is_bit_identical_to_its_own_launch(hi
             if sc["colliders"] and len(sc["colliders"]) == 1:
                 sc["particles"].pos[:, 1] -= 5.6 if sc["particles"].dim == 3 else 4.6
             sc["particles"].vel[:, 0] = 1.5
-            from helpers import pipeline
-            from wgsparkl_amd import MpmData
-            pipe = pipeline(sc["particles"].dim)
-            data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+            pipe, data = new_data(sc)
             pipe.step(data, 12)
             data.sync()          # (a long near-collider list seen here switches P2G to its paired launch)
             pipe.step(data, 13)
             return data.read_particles(), data.read_grid(), data.read_body_poses()
         a, ga, ba = run()
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("GU_OWN_LAUNCH"))
-        b, gb, bb = run()
-        monkeypatch.delenv("WGS_DEBUG")
-        for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), f
-        for x, y in zip(ga, gb):
-            assert np.array_equal(x, y)
-        for x, y in zip(ba, bb):
-            for key in ("translation", "rotation", "linvel", "angvel"):
-                assert np.array_equal(x[key], y[key]), key
+        with debug(monkeypatch, "GU_OWN_LAUNCH"):
+            b, gb, bb = run()
+        assert_same_bits(a, b, PLASTIC_FIELDS)
+        assert_same_grid(ga, gb)
+        assert_same_bodies(ba, bb, ("translation", "rotation", "linvel", "angvel"))
         if len(ba) > 1:      # moving bodies: integrate_bodies rides in the next substep's first sort launch (524288: a launch of its own)
-            monkeypatch.setenv("WGS_DEBUG", debug_switches("BODIES_OWN_LAUNCH"))
-            c, _, bc = run()
-            monkeypatch.delenv("WGS_DEBUG")
-            for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-                assert np.array_equal(getattr(a, f), getattr(c, f)), f
-            for x, y in zip(ba, bc):
-                for key in ("translation", "rotation", "linvel", "angvel"):
-                    assert np.array_equal(x[key], y[key]), key
+            with debug(monkeypatch, "BODIES_OWN_LAUNCH"):
+                c, _, bc = run()
+            assert_same_bits(a, c, AFFINITY_FIELDS)
+            assert_same_bodies(ba, bc, ("translation", "rotation", "linvel", "angvel"))
 
 
 @pytest.mark.parametrize("seed", [0, 3, 8])
@@ -223,10 +189,9 @@ def test_steady_state_rebinning_is_bit_identical_to_full_binning(hip_libs, seed,
     k = 150
     monkeypatch.setenv("WGS_REHASH_PERIOD", "64")             # (developer override, same results; the default is 1024)
     a = run_gpu(sc, k).read_particles()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_REBIN"))
-    b = run_gpu(sc, k).read_particles()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    with debug(monkeypatch, "NO_REBIN"):
+        b = run_gpu(sc, k).read_particles()
+        assert_same_bits(a, b, PLASTIC_FIELDS)
 
 
 def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
@@ -234,14 +199,11 @@ def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
     the fused G2P runs the variant compiled for 2 waves per SIMD (no spills in the CPIC body). Same source, another
     register budget: the results must be the bits of the 3-waves variant (WGS_DEBUG NO_G2P_DENSE keeps that one), because
     which of the two runs depends on when the host synchronised."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.sand_column(nx=40, ny=60, nz=40, with_walls=True)
     sc["particles"].pos[:, 1] -= 5.8
 
     def run():
-        pipe = pipeline(3)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+        pipe, data = new_data(sc)
         pipe.step(data, 4)
         data.sync()
         st = data.stats()
@@ -250,20 +212,18 @@ def test_plastic_pair_register_budgets_are_bit_identical(hip_libs, monkeypatch):
         data.sync()
         return data.read_particles()
     a = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_G2P_DENSE"))
-    b = run()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    assert np.isfinite(a.pos).all() and len(sc["colliders"]) == 5
+    with debug(monkeypatch, "NO_G2P_DENSE"):
+        b = run()
+        assert_same_bits(a, b, PLASTIC_FIELDS)
+        assert np.isfinite(a.pos).all() and len(sc["colliders"]) == 5
     # the one-way P2G pair has two register budgets too (chosen from the particle count and the list length): force the
     # small one by making the scene "large" is not possible at this size, so compare the large budget (this scene's
     # choice) with the separate launches, and the small budget at a size that selects it below
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("P2G_TWO_LAUNCHES"))
-    c = run()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "dp_state"):
-        assert np.array_equal(getattr(a, f), getattr(c, f)), f
-    for c in range(5):
-        assert ((a.cdf_affinity >> c) & 1).sum() > 100, c
+    with debug(monkeypatch, "P2G_TWO_LAUNCHES"):
+        c = run()
+        assert_same_bits(a, c, PLASTIC_FIELDS)
+        for c in range(5):
+            assert ((a.cdf_affinity >> c) & 1).sum() > 100, c
 
 
 def test_large_one_way_scenes_do_not_depend_on_when_the_host_synchronised(hip_libs, monkeypatch):
@@ -272,133 +232,90 @@ def test_large_one_way_scenes_do_not_depend_on_when_the_host_synchronised(hip_li
     the near-collider list the host last saw. 640 k neo-Hookean particles lying on the floor: eight substeps in one call
     and the same eight with a wgs_sync after the third end bit-identical; the unconstrained budget (WGS_DEBUG NO_P2G_SMALL_BUDGET)
     agrees to round-off."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.neo_hookean_cube(n_side=86, with_floor=True)
     sc["particles"].pos[:, 1] -= 5.7
     assert sc["particles"].n >= 600_000
 
     def run(chunks):
-        pipe = pipeline(3)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for k in chunks:
-            pipe.step(data, k)
-            data.sync()
+        data = step_chunks(sc, chunks)
         assert data.stats()["num_near_collider_blocks"] >= 8
         return data.read_particles()
     a, b = run((8,)), run((3, 5))
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_P2G_SMALL_BUDGET"))
-    c = run((3, 5))
-    assert np.array_equal(a.cdf_affinity, c.cdf_affinity)
-    for f in ("pos", "vel", "def_grad"):
-        assert rel_rms(getattr(c, f), getattr(a, f)) < 1e-6, f
+    assert_same_bits(a, b, AFFINITY_FIELDS)
+    with debug(monkeypatch, "NO_P2G_SMALL_BUDGET"):
+        c = run((3, 5))
+        assert np.array_equal(a.cdf_affinity, c.cdf_affinity)
+        for f in ("pos", "vel", "def_grad"):
+            assert rel_rms(getattr(c, f), getattr(a, f)) < 1e-6, f
 
 
 @pytest.mark.parametrize("seed", [1, 2, 6, 8])
 def test_checkpoint_restart_random_scenes(hip_libs, seed):
     """Bit-exact restart on the fuzz scenes: dynamic and kinematic bodies, mesh colliders, plasticity."""
-    import dataclasses
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = _random_scene(seed)
     dim = sc["particles"].dim
-    pipe = pipeline(dim)
-    args = (sc["cell_width"], sc["grid_capacity"], sc["model"])
-    full = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], *args)
+    pipe, full = new_data(sc)
     pipe.step(full, 20)
-    part = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], *args)
+    _, part = new_data(sc)
     pipe.step(part, 9)
     snap, bodies = part.read_particles(), part.read_body_poses()
-    def restored(c, b):
-        rot = tuple(b["rotation"]) if dim == 3 else (float(np.arctan2(b["rotation"][1], b["rotation"][0])),)
-        return dataclasses.replace(c, translation=tuple(b["translation"]), rotation=rot, linvel=tuple(b["linvel"]) + (0.0,) * (3 - dim),
-                                   angvel=tuple(b["angvel"]), com=tuple(b["com"]))
-    cols2 = [restored(c, b) for c, b in zip(sc["colliders"], bodies)]
-    rest = MpmData.new(pipe, sc["params"], snap, cols2, *args)
+    _, rest = new_data(sc, particles=snap, colliders=restored_colliders(sc["colliders"], bodies, dim))
     rest.set_plastic_state(snap.dp_state)
     pipe.step(rest, 11)
     a, b = full.read_particles(), rest.read_particles()
     exact = dim == 3     # 2D poses are handed over as an angle: cos / sin round-trip costs an ulp
-    for f in ("pos", "vel", "def_grad", "affine", "dp_state", "cdf_affinity"):
-        if exact or not sc["colliders"]:
-            assert np.array_equal(getattr(a, f), getattr(b, f)), f
-        elif f != "cdf_affinity":
+    if exact or not sc["colliders"]:
+        assert_same_bits(a, b, PLASTIC_FIELDS)
+    else:
+        for f in BASE_FIELDS + ("dp_state",):
             assert rel_rms(getattr(b, f), getattr(a, f)) < 1e-4, f
 
 
 def test_checkpoint_restart_is_bit_exact(hip_libs):
     """read_particles (+ plastic state, + body poses) -> MpmData.new -> set_plastic_state continues the
     run bit-for-bit (every reduction is in canonical particle order, whatever the storage order)."""
-    import dataclasses
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     ps = scenes.random_cloud(3000, dim=3, seed=5, extent=10.0, young=1e6, plasticity=DruckerPrager.new(1e6, 0.25), phase=None)
     ps.pos[:, 1] += 3.0
     cols = [Collider.cuboid((50.0, 1.0, 50.0), (8.0, 1.0, 8.0)),
             Collider.ball(1.5, (8.0, 12.0, 8.0), linvel=(0.0, -1.0, 0.0), angvel=(0.0, 0.0, 0.5))]
-    params = SimulationParams((0.0, -9.81, 0.0), 5e-4)
-    pipe = pipeline(3)
-    args = (1.0, 4096, MODEL_COROTATED)
-    full = MpmData.new(pipe, params, ps, cols, *args)
+    sc = dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0), 5e-4), colliders=cols, cell_width=1.0, grid_capacity=4096, model=MODEL_COROTATED)
+    pipe, full = new_data(sc)
     pipe.step(full, 24)
-    part = MpmData.new(pipe, params, ps, cols, *args)
+    _, part = new_data(sc)
     pipe.step(part, 12)
     snap, bodies = part.read_particles(), part.read_body_poses()
     assert (snap.dp_state != np.array([1.0, 1.0, 0.0], np.float32)).any(), "scene should have yielded by now"
-    cols2 = [dataclasses.replace(c, translation=tuple(b["translation"]), rotation=tuple(b["rotation"]),
-                                 linvel=tuple(b["linvel"]), angvel=tuple(b["angvel"]), com=tuple(b["com"]))
-             for c, b in zip(cols, bodies)]
-    rest = MpmData.new(pipe, params, snap, cols2, *args)
+    _, rest = new_data(sc, particles=snap, colliders=restored_colliders(cols, bodies, 3))
     rest.set_plastic_state(snap.dp_state)
     pipe.step(rest, 12)
-    a, b = full.read_particles(), rest.read_particles()
-    for f in ("pos", "vel", "def_grad", "affine", "dp_state", "phase", "cdf_affinity", "cdf_normal", "cdf_dist"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    pa, pb = full.read_body_poses(), rest.read_body_poses()
-    for x, y in zip(pa, pb):
-        for key in x:
-            assert np.array_equal(x[key], y[key]), key
-
+    assert_same_bits(full.read_particles(), rest.read_particles(), CDF_FIELDS + ("phase",))
+    assert_same_bodies(full.read_body_poses(), rest.read_body_poses())
 
 
 def test_checkpoint_restart_with_a_rotated_fixed_collider_next_to_a_moving_one(hip_libs):
     """A fixed collider is BIT-static whatever else moves (kernels_bodies.h bodies_integrate_one skips the identity
     integration of a body at rest): node cdfs cached out of reach of the moving colliders (Dev::cdf_moving) stay those a
     restarted run computes, and the pose a run reads back after any number of substeps is the one it was given."""
-    import dataclasses
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     ps = scenes.random_cloud(4000, dim=3, seed=11, extent=10.0, young=1e6)
     ps.pos[:, 1] += 4.0
     q = np.array([0.13, -0.31, 0.22, 0.91])
     q = tuple((q / np.linalg.norm(q)).astype(np.float32).astype(float))
     cols = [Collider.cuboid((50.0, 1.0, 50.0), (8.0, 0.5, 8.0), rotation=q),
             Collider.ball(1.5, (8.0, 13.0, 8.0), linvel=(0.0, -2.0, 0.0), angvel=(0.3, 0.0, 0.5))]
-    params = SimulationParams((0.0, -9.81, 0.0), 5e-4)
-    pipe = pipeline(3)
-    args = (1.0, 4096, MODEL_NEO_HOOKEAN)
-    full = MpmData.new(pipe, params, ps, cols, *args)
+    sc = dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0), 5e-4), colliders=cols, cell_width=1.0, grid_capacity=4096, model=MODEL_NEO_HOOKEAN)
+    pipe, full = new_data(sc)
     pose0 = full.read_body_poses()[0]
     pipe.step(full, 30)
-    part = MpmData.new(pipe, params, ps, cols, *args)
+    _, part = new_data(sc)
     pipe.step(part, 13)
     snap, bodies = part.read_particles(), part.read_body_poses()
     for key in ("translation", "rotation"):
         assert np.array_equal(bodies[0][key], pose0[key]), f"the fixed collider's {key} changed bits"
-    cols2 = [dataclasses.replace(c, translation=tuple(b["translation"]), rotation=tuple(b["rotation"]),
-                                 linvel=tuple(b["linvel"]), angvel=tuple(b["angvel"]), com=tuple(b["com"]))
-             for c, b in zip(cols, bodies)]
-    rest = MpmData.new(pipe, params, snap, cols2, *args)
+    _, rest = new_data(sc, particles=snap, colliders=restored_colliders(cols, bodies, 3))
     rest.set_plastic_state(snap.dp_state)   # (phase None: the reference's default Drucker-Prager, quirk B1 — the scene is plastic)
     pipe.step(rest, 17)
-    a, b = full.read_particles(), rest.read_particles()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity", "cdf_normal", "cdf_dist"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    ga, gb = full.read_grid(), rest.read_grid()
-    for x, y in zip(ga, gb):
-        assert np.array_equal(x, y)
+    assert_same_bits(full.read_particles(), rest.read_particles(), AFFINITY_FIELDS + ("cdf_normal", "cdf_dist"))
+    assert_same_grid(full.read_grid(), rest.read_grid())
 
 
 @pytest.mark.parametrize("plastic", [False, True])
@@ -407,8 +324,6 @@ def test_a_body_crossing_the_grid_evicts_blocks_and_stays_bit_identical_to_the_r
     the sort evicts them (their table slots are marked, their ids reused: kernels_sort.h regroup_block) — no table rebuild but the
     periodic ones; with WGS_DEBUG NO_EVICTION nothing is evicted and the table is rebuilt whenever three quarters of the ids are handed out.
     The sort is only a permutation: the same bits either way, and the evicting run rebuilds less often."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=True, grid_capacity=512)   # (~125-200 blocks at a time: the grid never grows; 384 ids run out every few hundred substeps)
     ps = sc["particles"]
     if plastic:   # (the variants with the plasticity / fracture branch bin in launch 1 of the sort, k_rebin, not in the fused G2P; a
@@ -421,21 +336,16 @@ def test_a_body_crossing_the_grid_evicts_blocks_and_stays_bit_identical_to_the_r
     ps.vel[:, 2] = 40.0 - 1.5 * rel[:, 0]
     sc["params"] = SimulationParams((0.0, 0.0, 0.0), 1.0 / 300.0)   # (270 cells along x and z, 170 along y in 2 000 substeps)
     monkeypatch.setenv("WGS_REHASH_PERIOD", "100000")   # (developer override, same results: no periodic rebuild inside the run)
-    pipe = pipeline(3)
     def run():
-        data = MpmData.new(pipe, sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for _ in range(20):
-            pipe.step(data, 100)
-            data.sync()
+        data = step_chunks(new_data(sc, particles=ps)[1], (100,) * 20)
         return data.read_particles(), data.stats()
     a, sa = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_EVICTION"))
-    b, sb = run()
-    for f in ("pos", "vel", "def_grad", "affine", "dp_state"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    assert sa["overflow"] == 0 and sb["overflow"] == 0
-    assert sa["table_rebuilds"] < sb["table_rebuilds"], (sa["table_rebuilds"], sb["table_rebuilds"])
-    assert sa["table_rebuilds"] <= 1 + sa["grid_growths"]     # the first substep (+ one per growth of the grid: none expected)
+    with debug(monkeypatch, "NO_EVICTION"):
+        b, sb = run()
+        assert_same_bits(a, b, BASE_FIELDS + ("dp_state",))
+        assert sa["overflow"] == 0 and sb["overflow"] == 0
+        assert sa["table_rebuilds"] < sb["table_rebuilds"], (sa["table_rebuilds"], sb["table_rebuilds"])
+        assert sa["table_rebuilds"] <= 1 + sa["grid_growths"]     # the first substep (+ one per growth of the grid: none expected)
 
 
 @pytest.mark.parametrize("scene", ["sand3", "paddle"])
@@ -445,8 +355,6 @@ def test_node_cdf_summaries_shared_between_blocks_give_the_bits_of_whole_tile_ev
     every block — each node up to eight times. The class of a block (listed for the CPIC bodies or not) and everything downstream must
     be what the whole-tile evaluation gives (WGS_DEBUG NO_CDF_SUMM), also when no word is ever waited for (WGS_DEBUG CDF_SUMM_NO_WAIT: every neighbour whose
     word is late is evaluated locally — the path taken when a neighbour's wave is not resident)."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     if scene == "sand3":
         sc = scenes.reference_sand3()
         steps = 150
@@ -458,20 +366,16 @@ def test_node_cdf_summaries_shared_between_blocks_give_the_bits_of_whole_tile_ev
                                  linvel=(30.0, 0.0, 0.0))
         sc["colliders"] = list(sc["colliders"]) + [paddle]
         steps = 200
-    pipe = pipeline(3)
     def run():
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        pipe.step(data, steps)
-        data.sync()
+        data = run_gpu(sc, steps)
         return data.read_particles(), data.stats()
     a, sa = run()
     assert sa["overflow"] == 0
     assert np.any(a.cdf_affinity != 0)   # (somebody is within reach of a collider)
     for dbg in ("NO_CDF_SUMM", "CDF_SUMM_NO_WAIT"):
-        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
-        b, sb = run()
-        for f in ("pos", "vel", "def_grad", "affine", "dp_state", "cdf_affinity", "cdf_normal", "cdf_dist"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), (dbg, f)
+        with debug(monkeypatch, dbg):
+            b, sb = run()
+            assert_same_bits(a, b, CDF_FIELDS, dbg)
 
 
 @pytest.mark.parametrize("scene", ["sand3", "paddle", "sand2"])
@@ -481,22 +385,14 @@ def test_particle_cdf_by_prologue_waves_of_the_p2g_launch_gives_the_bits_of_the_
     (written through, counted per block, fetched past the L2: kernels_transfer.h pcdf_waves) instead of in three to six rounds inside
     each block's CPIC workgroup. Same particles, same arithmetic: the same bits as with WGS_DEBUG NO_PCDF_WAVES (never prologue waves), substep
     after substep across host looks."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
-    dim = 3
     if scene == "sand3":
         sc = scenes.reference_sand3()
     elif scene == "sand2":
         sc = scenes.reference_sand2()
-        dim = 2
     else:
         sc = scenes.corotated_cube_with_paddle(n_side=32)
-    pipe = pipeline(dim)
     def run():
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for _ in range(12):
-            pipe.step(data, 10)
-            data.sync()      # (the host looks at the lists here: the next call sizes its launches from what it saw)
+        data = step_chunks(sc, (10,) * 12)   # (the host looks at the lists after each: the next call sizes its launches from what it saw)
         st = data.stats()
         return data.read_particles(), st, (data.read_body_poses() if sc["colliders"] else None)
     a, sa, ba = run()
@@ -504,14 +400,11 @@ def test_particle_cdf_by_prologue_waves_of_the_p2g_launch_gives_the_bits_of_the_
     # 4: never prologue waves; 8: prologue workgroups sized for an empty list whatever the host saw — the launch then decides from the
     # lists of the substep itself (too long for so few waves: the blocks' workgroups do the work; short enough: the waves do)
     for dbg in ("NO_PCDF_WAVES", "PCDF_WAVES_UNSIZED"):
-        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
-        b, sb, bb = run()
-        for f in ("pos", "vel", "def_grad", "affine", "dp_state", "cdf_affinity", "cdf_normal", "cdf_dist"):
-            assert np.array_equal(getattr(a, f), getattr(b, f)), (dbg, f)
-        if ba is not None:
-            for x, y in zip(ba, bb):
-                for key in x:
-                    assert np.array_equal(np.asarray(x[key]), np.asarray(y[key])), (dbg, key)
+        with debug(monkeypatch, dbg):
+            b, sb, bb = run()
+            assert_same_bits(a, b, CDF_FIELDS, dbg)
+            if ba is not None:
+                assert_same_bodies(ba, bb)
 
 
 @pytest.mark.parametrize("scene", ["at_rest", "landed", "flying"])
@@ -522,8 +415,6 @@ def test_direct_runs_of_unchanged_blocks_give_the_bits_of_the_gather_through_the
     WGS_DEBUG NO_DIRECT_RUNS (every block through the permutation) — a cube in free fall (every block direct), the cube landing on the floor
     (direct and gathered blocks side by side, listed blocks beside them) and the cube crossing the grid and spinning (hardly any direct
     block; blocks becoming direct and dirty again), with a host look in between."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.neo_hookean_cube(n_side=86, with_floor=True)
     ps = sc["particles"]
     nsub = 12
@@ -537,52 +428,52 @@ def test_direct_runs_of_unchanged_blocks_give_the_bits_of_the_gather_through_the
         nsub = 60
 
     def run():
-        pipe = pipeline(3)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        pipe.step(data, nsub // 2)
-        data.sync()
-        pipe.step(data, nsub - nsub // 2)
-        data.sync()
+        data = step_chunks(sc, (nsub // 2, nsub - nsub // 2))
         st = data.stats()
         assert st["overflow"] == 0
         return data.read_particles(), data.read_grid(), st
     a, ga, sta = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_DIRECT_RUNS"))
-    b, gb, stb = run()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    for x, y in zip(ga, gb):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-    if scene == "flying":
-        assert sta["cell_changers"] > 0   # (the scene does move: blocks are dirty)
+    with debug(monkeypatch, "NO_DIRECT_RUNS"):
+        b, gb, stb = run()
+        assert_same_bits(a, b, AFFINITY_FIELDS)
+        assert_same_grid(ga, gb)
+        if scene == "flying":
+            assert sta["cell_changers"] > 0   # (the scene does move: blocks are dirty)
 
 
 def test_large_two_way_scenes_with_the_near_collider_launch_first_give_the_bits_of_the_other_order(hip_libs, monkeypatch):
     """Large simulations with a body that moves (>= 600 k particles: BASELINE.json configs[3]) run P2G as two launches; since round 6 the
     near-collider launch goes FIRST and the grid update rides behind the plain launch (at the plain body's occupancy instead of the two-way
     body's). Same slabs, same gather: the bits of the plain-launch-first order (WGS_DEBUG PLAIN_P2G_FIRST), also across a host look."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.config_scene("c4", n_side=86)
     assert sc["particles"].n >= 600_000
 
     def run():
-        pipe = pipeline(3)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        pipe.step(data, 30)
-        data.sync()
-        pipe.step(data, 30)
-        data.sync()
+        data = step_chunks(sc, (30, 30))
         st = data.stats()
         assert st["overflow"] == 0 and st["num_near_collider_blocks"] > 0
         return data.read_particles(), data.read_grid(), data.read_body_poses()
     a, ga, pa = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("PLAIN_P2G_FIRST"))
-    b, gb, pb = run()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    for x, y in zip(ga, gb):
-        assert np.array_equal(np.asarray(x), np.asarray(y))
-    for x, y in zip(pa, pb):
-        for key in ("rotation", "translation", "linvel", "angvel"):
-            assert np.array_equal(np.asarray(x[key]), np.asarray(y[key])), key
+    with debug(monkeypatch, "PLAIN_P2G_FIRST"):
+        b, gb, pb = run()
+        assert_same_bits(a, b, AFFINITY_FIELDS)
+        assert_same_grid(ga, gb)
+        assert_same_bodies(pa, pb, ("rotation", "translation", "linvel", "angvel"))
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_from_scene_builds_what_new_builds(hip_libs, dim):
+    """MpmData.from_scene is MpmData.new with the scene's entries: the same small scene (a floor under it) created both ways and advanced
+    two substeps ends with the same bits in the particles, the grid and the body poses, and the same counters; a keyword replaces the
+    scene's entry."""
+    sc = scenes.neo_hookean_cube(n_side=8, with_floor=True) if dim == 3 else scenes.elastic_block_2d(22, 22)
+    assert sc["particles"].n == (512 if dim == 3 else 484)
+    pipe = pipeline(dim)
+    spelled = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    a, b = step_chunks(spelled, (2,)), step_chunks(MpmData.from_scene(pipe, sc), (2,))
+    assert_same_bits(a.read_particles(), b.read_particles(), CDF_FIELDS)
+    assert_same_grid(a.read_grid(), b.read_grid())
+    assert a.n_colliders == b.n_colliders == len(sc["colliders"])
+    assert_same_bodies(a.read_body_poses(), b.read_body_poses())
+    assert a.stats() == b.stats()
+    assert MpmData.from_scene(pipe, sc, colliders=[]).n_colliders == 0

@@ -7,6 +7,7 @@ affinity / sign bits and closest id are exact outside the undecided set and its 
 no voter hold exactly (1e10, NONE, 0); every particle's cdf_affinity is exact when decided and its cdf_dist / cdf_normal
 are within their bounds, twice: from the kernel's own read-back node field (isolated) and from the truth's (end to end).
 Every run asserts the caps on its undecided shares."""
+import contextlib
 import dataclasses
 
 import numpy as np
@@ -15,8 +16,8 @@ import pytest
 import cdf_truth as CT
 import transfer_truth as T
 from gpu_common import _native_slabs, check_blocks
-from helpers import debug_switches, pipeline, report_margin, run_oracle
-from wgsparkl_amd import MpmData
+from helpers import debug, new_data, pipeline, report_margin, run_oracle
+from wgsparkl_amd import MpmData, _ffi
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +26,7 @@ CASES = [(name, d, h) for name in CT.SCENES for d in (2, 3) for h in CT.HS]
 
 
 def _new(sc):
-    ps = sc["particles"]
-    return MpmData.new(pipeline(ps.dim), sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    return new_data(sc)[1]
 
 
 def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None):
@@ -61,8 +61,7 @@ def test_shapes_and_poses_one_substep(hip_libs, name, d, h):
     if name == "sixteen":
         # the library refuses a 17th coupled collider outright (the C oracle and the truth ignore it: test_cdf_truth.py);
         # what runs here is all 16 slots in use
-        from wgsparkl_amd._ffi import WgsError
-        with pytest.raises(WgsError):
+        with pytest.raises(_ffi.WgsError):
             _new(sc)
         sc["colliders"] = sc["colliders"][:16]
     data = _new(sc)
@@ -115,10 +114,8 @@ def test_each_node_field_path_agrees_with_the_truth(hip_libs, monkeypatch, path,
     sc = CT.two_equal(d, h)
     if path == "k_cdf":
         sc = _far_mesh(sc)
-    if path == "no_summaries":
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_CDF_SUMM"))
-    data = _new(sc)
-    monkeypatch.delenv("WGS_DEBUG", raising=False)
+    with debug(monkeypatch, "NO_CDF_SUMM") if path == "no_summaries" else contextlib.nullcontext():
+        data = _new(sc)
     fails = []
     nf, pf, got = _checked_substep(f"node field path {path} {d}D", sc, data, fails, first=True)
     if path == "k_cdf":
@@ -135,10 +132,8 @@ def test_each_particle_field_path_agrees_with_the_truth(hip_libs, monkeypatch, p
     workgroups (NO_PCDF_WAVES)"""
     h = 0.5
     sc = CT.capsule(d, h)
-    if path == "cpic_workgroups":
-        monkeypatch.setenv("WGS_DEBUG", debug_switches("NO_PCDF_WAVES"))
-    data = _new(sc)
-    monkeypatch.delenv("WGS_DEBUG", raising=False)
+    with debug(monkeypatch, "NO_PCDF_WAVES") if path == "cpic_workgroups" else contextlib.nullcontext():
+        data = _new(sc)
     pipeline(d).step(data, 1)
     data.sync()
     fails = []
@@ -206,7 +201,6 @@ def _export_cdf(shard):
     buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
     torch.cuda.current_stream(buf.device).synchronize()
     cnt = C.c_uint32(0)
-    from wgsparkl_amd import _ffi
     _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
     rec = buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
     ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)

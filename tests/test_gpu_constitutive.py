@@ -13,14 +13,14 @@ threshold; those are counted and the count bounded, and their result must be one
 compression F = c I is such a case by construction: in fp32 log c summed d times and divided by d is not always log c, so
 the kernel may keep F (gamma ≤ 0 on the cone branch) or project to the tip — both are computed in fp64 and accepted; the
 fp32 oracle is no arbiter there (its SVD runs in fp64 and returns s = c exactly, the kernel gets sqrt(c^2) in fp32)."""
+import contextlib
 import zlib
 
 import numpy as np
 import pytest
 
 import devmath_truth as T
-from helpers import debug_switches, pipeline, report_margin
-from wgsparkl_amd import MpmData
+from helpers import debug, new_data, report_margin
 from wgsparkl_amd.models import MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
@@ -81,9 +81,7 @@ def _scene(dim, model, plastic, mode, per_particle, collider, fracture, seed):
 
 
 def _run(sc, state=None):
-    ps = sc["particles"]
-    pipe = pipeline(ps.dim)
-    data = MpmData.new(pipe, sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc)
     if state is not None:
         data.set_plastic_state(state)
     pipe.step(data, 1)
@@ -110,11 +108,14 @@ CASES = {
 @pytest.mark.parametrize("dim", [3, 2])
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_one_substep_constitutive_update_per_particle(hip_libs, monkeypatch, case, dim):
-    model, plastic, mode, per_particle, collider, fracture, dbg = CASES[case]
-    if dbg is not None:
-        monkeypatch.setenv("WGS_DEBUG", debug_switches(dbg))
-    else:
-        monkeypatch.delenv("WGS_DEBUG", raising=False)
+    dbg = CASES[case][-1]
+    monkeypatch.delenv("WGS_DEBUG", raising=False)
+    with debug(monkeypatch, dbg) if dbg is not None else contextlib.nullcontext():
+        _check_case(case, dim)
+
+
+def _check_case(case, dim):
+    model, plastic, mode, per_particle, collider, fracture, _ = CASES[case]
     sc, fam = _scene(dim, model, plastic, mode, per_particle, collider, fracture, seed=zlib.crc32(case.encode()) % 1000 + dim)
     ps = sc["particles"]
     n = ps.n

@@ -10,9 +10,9 @@ import pytest
 
 import diag_truth as dt
 from gpu_common import _exploding_cube, _native_slabs, cloud_scene
-from helpers import debug_switches, pipeline, report_margin, run_gpu, run_oracle
-from wgsparkl_amd import MpmData, _ffi, scenes
-from wgsparkl_amd.models import MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ParticlePhase
+from helpers import BASE_FIELDS, assert_same_bits, assert_same_grid, debug, new_data, pipeline, report_margin, run_gpu, run_oracle
+from wgsparkl_amd import _ffi, scenes
+from wgsparkl_amd.models import MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager
 from wgsparkl_amd.solver import SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -35,8 +35,7 @@ PARTICLE_SUMS = ("mass", "momentum", "angular", "mass_moment", "kinetic", "kinet
 
 
 def _new(sc):
-    ps = sc["particles"]
-    return MpmData.new(pipeline(ps.dim), sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    return new_data(sc)[1]
 
 
 def _check_sums(tag, d, got, sc, quality=True):
@@ -208,9 +207,8 @@ def test_reproducible_across_runs_shapes_restarts_and_entry_points(monkeypatch):
         assert a.raw == a2.raw
         assert a.num_particles > 0 and a.digest != (0, 0)
         for switch in ("NO_UNIFORM", "NO_DIRECT_RUNS"):
-            monkeypatch.setenv("WGS_DEBUG", debug_switches(switch))
-            _, b = run(make)
-            monkeypatch.delenv("WGS_DEBUG")
+            with debug(monkeypatch, switch):
+                _, b = run(make)
             assert a.raw == b.raw, switch
     # (c)
     whole, a = run(_sand, 20)
@@ -353,8 +351,6 @@ def test_asking_changes_nothing():
         return data.read_particles(), data.read_grid(), seen
     a, ga, seen = run(True)
     b, gb, _ = run(False)
-    for f in ("pos", "vel", "def_grad", "affine", "dp_state", "phase", "mass"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
-    for x, y in zip(ga, gb):
-        assert np.array_equal(x, y)
+    assert_same_bits(a, b, BASE_FIELDS + ("dp_state", "phase", "mass"))
+    assert_same_grid(ga, gb)
     assert len({d.raw for d in seen}) == 3 and seen[-1].digest == dt.digest(a)

@@ -2,6 +2,7 @@
 bit identity across launch shapes, checkpoint / model switches, diagnostics, argument checks, sharded data.
 
 Figures measured on one MI355X are in profiles/r09_fluid_margins.json (every comparison goes through helpers.report_margin)."""
+import contextlib
 import math
 
 import numpy as np
@@ -9,8 +10,8 @@ import pytest
 
 import fluid_truth as ft
 from gpu_common import GRID_V_TOL, PART_TOL, _native_slabs
-from helpers import assert_close_to_truth, debug_switches, pipeline, rel_rms, report_margin
-from wgsparkl_amd import MpmData, _ffi, scenes
+from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, rel_rms, report_margin
+from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd._ffi import WgsError
 from wgsparkl_amd.models import MODEL_FLUID, MODEL_NEO_HOOKEAN, DruckerPrager, FluidCoefficients, ParticlePhase
 from wgsparkl_amd.solver import ParticleSet, SimulationParams
@@ -22,8 +23,7 @@ ELASTIC_ROUNDINGS = 256    # the allowance tests/test_gpu_diagnostics.py gives t
 
 
 def _new(sc):
-    ps = sc["particles"]
-    data = MpmData.new(pipeline(ps.dim), sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    _, data = new_data(sc)
     if "fluid_gamma" in sc:
         data.set_fluid_eos(sc["fluid_gamma"])
     return data
@@ -121,19 +121,15 @@ def test_launch_shapes_and_runs_are_bit_identical(hip_libs, monkeypatch, scene):
         return _falling_block(3 if scene == "block3" else 2, True, 10.0, 7.0)
     ref = None
     for names in SHAPES:
-        if names:
-            monkeypatch.setenv("WGS_DEBUG", debug_switches(*names))
-        data = _run(make(), (15, 15))
-        if names:
-            monkeypatch.delenv("WGS_DEBUG")
+        with debug(monkeypatch, *names) if names else contextlib.nullcontext():
+            data = _run(make(), (15, 15))
         got, digest = _state(data)
         assert data.stats()["overflow"] == 0
         if ref is None:
             ref = (got, digest)
             got2, digest2 = _state(_run(make(), (15, 15)))             # two runs
             assert digest2 == digest
-            for f in FIELDS:
-                assert np.array_equal(getattr(got2, f), getattr(got, f)), f
+            assert_same_bits(got2, got, FIELDS)
             assert np.isfinite(got.pos).all() and np.isfinite(got.vel).all() and np.isfinite(got.def_grad).all() and np.isfinite(got.affine).all()
             _assert_canonical(got, got.dim)
             if scene == "dam_break":
@@ -141,8 +137,7 @@ def test_launch_shapes_and_runs_are_bit_identical(hip_libs, monkeypatch, scene):
                 assert got.pos[:, 1].min() > 2.0 - 0.5 and got.pos[:, 0].min() > 8.0 - 0.5
                 assert np.abs(got.def_grad[:, 0] - 1.0).max() > 1e-4
             continue
-        for f in FIELDS:
-            assert np.array_equal(getattr(got, f), getattr(ref[0], f)), (names, f)
+        assert_same_bits(got, ref[0], FIELDS, names)
         assert digest == ref[1], names
 
 
@@ -157,9 +152,7 @@ def test_checkpoint_and_model_switches(hip_libs, dim):
     _assert_canonical(mid, dim)
     sc2 = dict(sc, particles=mid)
     rest = _run(sc2, (14,))
-    a, b = whole.read_particles(), rest.read_particles()
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(whole.read_particles(), rest.read_particles(), BASE_FIELDS)
     assert whole.diagnostics(_ffi.DIAG_DIGEST).digest == rest.diagnostics(_ffi.DIAG_DIGEST).digest
     # selecting the fluid again changes nothing
     before = rest.diagnostics(_ffi.DIAG_DIGEST).digest

@@ -7,7 +7,7 @@ import pytest
 from wgsparkl_amd import scenes
 from wgsparkl_amd.solver import SimulationParams
 
-from helpers import run_gpu
+from helpers import BASE_FIELDS, assert_same_bits, pipeline, run_gpu, step_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -66,14 +66,7 @@ def test_c3_sand_column_four_million(hip_libs):
     sc["particles"].pos[:, 1] -= 5.8                       # standing on the floor
     n = sc["particles"].n
     assert n == 4_000_000 and len(sc["colliders"]) == 5
-    pipe_steps = (3, 3)                                    # a sync in between: the long-list launch shapes run too
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-    for k in pipe_steps:
-        pipe.step(data, k)
-        data.sync()
+    data = step_chunks(sc, (3, 3))                         # a sync in between: the long-list launch shapes run too
     check_sort_structure(data, n)
     got = data.read_particles()
     assert np.isfinite(got.pos).all() and np.isfinite(got.def_grad).all()
@@ -162,7 +155,6 @@ def test_c5_strong_scaling_slabs_on_one_gpu(hip_libs):
     """The decomposition bench.py --config c5 --scaling strong uses, 8 x-slabs of the fluid block advanced in
     lockstep on one GPU (wgs_sharded_step_lockstep: the per-phase code of wgs_sharded_step, device-to-device copies as the
     transport) at a reduced y/z extent: nobody is lost, the slabs reproduce the single-domain run."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     world, dims, k = 8, (256, 24, 24), 12
     pipe = pipeline(3)
@@ -190,7 +182,6 @@ def test_c5_strong_scaling_slabs_on_one_gpu(hip_libs):
 def test_bench_slabs_at_full_size_fit_their_exchange_buffers(hip_libs):
     """bench.py's N > 1 workload at its real size per rank (1M particles, two neighbouring slabs of the bar on one
     GPU): the message buffers sized from the face area (bench.py's rule) do not overflow and nobody is lost."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     world, n_side, k = 2, 100, 20
     pipe = pipeline(3)
@@ -213,8 +204,7 @@ def test_bit_identical_reruns_at_scale(hip_libs):
     sc["particles"].vel[:] = rng.normal(0, 1.0, sc["particles"].vel.shape).astype(np.float32)
     a = run_gpu(sc, 30).read_particles()
     b = run_gpu(sc, 30).read_particles()
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(a, b, BASE_FIELDS)
 
 
 def test_momentum_conserved_without_gravity(hip_libs):

@@ -3,9 +3,11 @@ separated bodies against each body alone, coupled fluid + solid bodies against t
 the label's journey through the sort and a restart, diagnostics and drawing, argument checks.
 
 Figures measured on one MI355X are in profiles/r11_mixed_margins.json (every comparison goes through helpers.report_margin)."""
+import contextlib
 import ctypes as C
 import dataclasses
 import math
+import types
 
 import numpy as np
 import pytest
@@ -14,10 +16,10 @@ import diag_truth as dt_
 import fluid_truth as ft
 import mixed_truth as mt
 from gpu_common import GRID_V_TOL, PART_TOL, _native_slabs
-from helpers import assert_close_to_truth, debug_switches, pipeline, report_margin
+from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, report_margin
 from oracle import np_oracle
 from test_gpu_fluid import ELASTIC_ROUNDINGS, FIELDS, SHAPES
-from wgsparkl_amd import MpmData, _ffi, scenes
+from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd._ffi import WgsError
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, MODEL_PER_PARTICLE, DruckerPrager, ElasticCoefficients,
                                  FluidCoefficients, ParticlePhase)
@@ -31,9 +33,7 @@ ARRAYS = [f.name for f in dataclasses.fields(ParticleSet) if f.name != "dim"]
 
 def _new(sc, table=True, model=None):
     """The scene's data; with `table` its per-particle models are set (scene key "models")."""
-    ps = sc["particles"]
-    data = MpmData.new(pipeline(ps.dim), sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"],
-                       sc.get("model", 0) if model is None else model)
+    _, data = new_data(sc, **({} if model is None else {"model": model}))
     if "fluid_gamma" in sc:
         data.set_fluid_eos(sc["fluid_gamma"])
     if table and "models" in sc:
@@ -100,18 +100,17 @@ def _tank(dim):
 def test_uniform_table_is_the_global_model(hip_libs, monkeypatch, dim, m, switch):
     """A table that labels every particle m and wgs_set_constitutive_model(m): the same bits in every field of read_particles and
     read_grid and the same digest after 30 substeps over two calls — the mixed kernel's branch for m is m's own kernel."""
-    if switch:
-        monkeypatch.setenv("WGS_DEBUG", debug_switches(*switch))
-    make = (lambda: _tank(dim)) if m == MODEL_FLUID else (lambda: _landing_block(dim))
-    sc = make()
-    ref = _run(sc, model=m)
-    sc2 = dict(make(), models=np.full(sc["particles"].n, m, np.uint8))
-    got = _run(sc2, model=MODEL_COROTATED if m != MODEL_COROTATED else MODEL_NEO_HOOKEAN)   # (the data's own model is another one)
-    _assert_same_state(ref, got, (dim, m, switch))
-    assert got.diagnostics(_ffi.DIAG_PARTICLES).model == MODEL_PER_PARTICLE and ref.diagnostics(_ffi.DIAG_PARTICLES).model == m
-    p = got.read_particles()
-    assert (p.cdf_affinity != 0).sum() > 50, "the scene should touch its colliders"
-    assert np.isfinite(p.pos).all() and np.isfinite(p.affine).all() and got.stats()["overflow"] == 0
+    with debug(monkeypatch, *switch) if switch else contextlib.nullcontext():
+        make = (lambda: _tank(dim)) if m == MODEL_FLUID else (lambda: _landing_block(dim))
+        sc = make()
+        ref = _run(sc, model=m)
+        sc2 = dict(make(), models=np.full(sc["particles"].n, m, np.uint8))
+        got = _run(sc2, model=MODEL_COROTATED if m != MODEL_COROTATED else MODEL_NEO_HOOKEAN)   # (the data's own model is another one)
+        _assert_same_state(ref, got, (dim, m, switch))
+        assert got.diagnostics(_ffi.DIAG_PARTICLES).model == MODEL_PER_PARTICLE and ref.diagnostics(_ffi.DIAG_PARTICLES).model == m
+        p = got.read_particles()
+        assert (p.cdf_affinity != 0).sum() > 50, "the scene should touch its colliders"
+        assert np.isfinite(p.pos).all() and np.isfinite(p.affine).all() and got.stats()["overflow"] == 0
 
 
 # ------------------------------------------------------------------------------------------------ 2. separated bodies
@@ -149,8 +148,7 @@ def test_separated_bodies_equal_each_body_alone(hip_libs, dim):
     lo = 0
     for k, b in enumerate(bodies):
         alone = _run(dict(base, particles=b, model=k)).read_particles()
-        for f in ("pos", "vel", "def_grad", "affine"):
-            assert np.array_equal(getattr(both, f)[lo:lo + b.n], getattr(alone, f)), (k, f)
+        assert_same_bits(types.SimpleNamespace(**{f: getattr(both, f)[lo:lo + b.n] for f in BASE_FIELDS}), alone, BASE_FIELDS, k)
         assert np.abs(alone.def_grad - np.eye(dim, dtype=np.float32).reshape(-1)).max() > 0.02
         lo += b.n
 
@@ -206,12 +204,9 @@ def test_launch_shapes_and_runs_are_bit_identical(hip_libs, monkeypatch, dim, so
     default run twice and under each launch-shape switch of test_gpu_fluid.py — the same bits; the label arrives with its particle."""
     ref = None
     for names in SHAPES:
-        if names:
-            monkeypatch.setenv("WGS_DEBUG", debug_switches(*names))
-        sc = _drop(dim, solid_model)
-        data = _run(sc)
-        if names:
-            monkeypatch.delenv("WGS_DEBUG")
+        with debug(monkeypatch, *names) if names else contextlib.nullcontext():
+            sc = _drop(dim, solid_model)
+            data = _run(sc)
         got, digest = data.read_particles(), _digest(data)
         st = data.stats()
         assert st["overflow"] == 0
@@ -233,8 +228,7 @@ def test_launch_shapes_and_runs_are_bit_identical(hip_libs, monkeypatch, dim, so
             assert np.array_equal(got.def_grad[~solid][:, 1:], np.tile(eye[1:], (int((~solid).sum()), 1)))
             assert np.abs(got.def_grad[solid] - eye).max() > 1e-3, "the block should feel the fluid"
             continue
-        for f in FIELDS:
-            assert np.array_equal(getattr(got, f), getattr(ref[0], f)), (names, f)
+        assert_same_bits(got, ref[0], FIELDS, names)
         assert digest == ref[1], names
 
 
@@ -247,9 +241,7 @@ def test_restart_continues_bit_for_bit(hip_libs, dim, solid_model):
     snap, labels = first.read_particles(), first.read_particle_models()
     assert np.array_equal(labels, sc["models"])
     rest = _run(dict(sc, particles=snap, models=labels), (10,))
-    a, b = whole.read_particles(), rest.read_particles()
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(whole.read_particles(), rest.read_particles(), BASE_FIELDS)
     assert _digest(whole) == _digest(rest)
     assert np.array_equal(rest.read_particle_models(), sc["models"])
 
@@ -344,7 +336,8 @@ def test_refusals_leave_the_data_alone(hip_libs, dim):
 
     # data whose step carries plastic state
     ps = scenes.random_cloud(800, dim=dim, seed=3, young=1e6, plasticity=DruckerPrager.new(1e6, 0.25), phase=None)
-    pl = MpmData.new(pipeline(dim), SimulationParams((0.0, -9.81, 0.0)[:dim], 8e-4), ps, [], 1.0, 4096, MODEL_NEO_HOOKEAN)
+    _, pl = new_data(dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0)[:dim], 8e-4), colliders=[], cell_width=1.0, grid_capacity=4096,
+                          model=MODEL_NEO_HOOKEAN))
     pl.pipeline.step(pl, 2)
     pl.sync()
     st = (_digest(pl), pl.read_particles(), pl.read_particle_models())

@@ -4,14 +4,14 @@ size, the reference's own scenes, random scenes and API sequences, the committed
 import numpy as np
 import pytest
 
-from wgsparkl_amd import scenes
+from wgsparkl_amd import KernelInvocationQueue, _ffi, scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, oracle, pipeline, rel_rms, report_margin, run_gpu, run_oracle
-from wgsparkl_amd import MpmData
+from helpers import (AFFINITY_FIELDS, BASE_FIELDS, assert_close_to_truth, assert_same_bits, assert_same_bodies, compare_cpic, compare_grids, debug,
+                     grid_of, new_data, oracle, pipeline, rel_rms, report_margin, run_gpu, run_oracle, step_chunks)
 from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
-                        _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
+                        _exploding_cube, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
 import os as _os
 
 from golden_cases import CASES as _CASES
@@ -162,8 +162,6 @@ def test_reference_prefix_sum_vectors_through_the_hip_scan(hip_libs, oracle_libs
     that replaces WgPrefixSum (kernels_sort.h scan_chunk, via the wgs_debug_scan hook): out[i] = i, out[i] = i(i-1)/2,
     and equality with eval_cpu (restated in the oracle). Plus the edge lengths around the chunk and wave sizes."""
     import ctypes as C
-    from helpers import pipeline
-    from wgsparkl_amd import _ffi
     pipe = pipeline(dim)
     orc = oracle_libs.Oracle(3, np.float32)
 
@@ -218,8 +216,7 @@ def test_dense_blocks_take_the_global_memory_paths_of_the_sort(hip_libs, oracle_
     check_fields(data, st32, st64)
     a = data.read_particles()
     b = run_gpu(sc, k).read_particles()
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(a, b, BASE_FIELDS)
 
 
 def test_visit_list_many_listed_blocks_per_chunk(hip_libs, oracle_libs, monkeypatch):
@@ -247,23 +244,18 @@ def test_visit_list_many_listed_blocks_per_chunk(hip_libs, oracle_libs, monkeypa
     check_blocks(data, st32)
     got, same = compare_cpic(data, st32, st64, 3, CPIC_GRID_V_TOL, CPIC_PART_TOL, min_same=0.995)
     assert (got.cdf_affinity & 1).sum() > 500
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_PASSES"))
-    b = run_gpu(sc, k).read_particles()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-        assert np.array_equal(getattr(got, f), getattr(b, f)), f
+    with debug(monkeypatch, "G2P_TWO_PASSES"):
+        b = run_gpu(sc, k).read_particles()
+        assert_same_bits(got, b, AFFINITY_FIELDS)
 
 
 def test_device_ptrs_view_matches_the_read_back(hip_libs):
     """wgs_get_device_ptrs (the optional interop view of SURVEY 8b): the position quads and particle ids it points at, copied
     straight from device memory, are the positions wgs_read_positions returns — in sorted order, labelled by the ids."""
     import ctypes as C
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData, _ffi
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=True)
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-    pipe.step(data, 7)
-    data.sync()
+    pipe, data = new_data(sc)
+    step_chunks(data, (7,))
     view = _ffi.DevicePtrs()
     _ffi.check(pipe.lib, pipe.lib.wgs_get_device_ptrs(data._h, C.byref(view)))
     n = sc["particles"].n
@@ -280,10 +272,9 @@ def test_device_ptrs_view_matches_the_read_back(hip_libs):
 
 
 def test_grid_overflow_is_reported(hip_libs):
-    from wgsparkl_amd._ffi import WgsError
     sc = cloud_scene(n=5000)
     sc["grid_capacity"] = 8
-    with pytest.raises(WgsError):
+    with pytest.raises(_ffi.WgsError):
         run_gpu(sc, 1)
 
 
@@ -292,13 +283,8 @@ def test_grid_grows_before_it_overflows(hip_libs):
     active blocks outgrow the capacity it was created with. With growth (the default) the capacity doubles between
     wgs_step calls and the run is bit-identical to one that had a large capacity from the start; with growth switched
     off the overflow is reported, as before."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData, _ffi
-    pipe = pipeline(3)
-
     def run(cap, grow, frames=30, per=10):
-        sc = _exploding_cube()
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], cap, sc["model"])
+        pipe, data = new_data(_exploding_cube(), grid_capacity=cap)
         _ffi.check(pipe.lib, pipe.lib.wgs_set_grid_growth(data._h, 1 if grow else 0))
         for _ in range(frames):
             pipe.step(data, per)           # asynchronous: the growth check looks at what the PREVIOUS call left behind
@@ -310,9 +296,7 @@ def test_grid_grows_before_it_overflows(hip_libs):
     small = run(64, True)
     st = small.stats()
     assert st["overflow"] == 0 and st["grid_growths"] >= 1 and st["grid_capacity"] > 64
-    a, b = big.read_particles(), small.read_particles()
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(big.read_particles(), small.read_particles(), BASE_FIELDS)
     with pytest.raises(_ffi.WgsError):
         run(64, False)
 
@@ -322,13 +306,10 @@ def test_fast_translation_needs_no_more_capacity_than_its_active_blocks(hip_libs
     rebuild period, many more blocks than are ever active at once. The capacity bounds the ACTIVE blocks (like the
     reference's, which rebuilds its table every substep): the table is rebuilt early when three quarters of the ids are
     handed out, instead of reporting an overflow."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData, _ffi
-    pipe = pipeline(3)
     sc = scenes.neo_hookean_cube(n_side=16)
     sc["particles"].vel[:, 0] = 900.0                               # 0.75 cells per substep
     sc["params"] = SimulationParams(gravity=(0.0, 0.0, 0.0), dt=sc["params"].dt)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], [], sc["cell_width"], 128, sc["model"])   # 64 active blocks
+    pipe, data = new_data(sc, colliders=[], grid_capacity=128)   # 64 active blocks
     _ffi.check(pipe.lib, pipe.lib.wgs_set_grid_growth(data._h, 0))
     for _ in range(40):
         pipe.step(data, 4)
@@ -380,16 +361,7 @@ def test_random_breakable_plastic_scenes_match_oracle(hip_libs, oracle_libs, see
 def _fuzz_parity(sc, chunk):
     dim = sc["particles"].dim
     k = 12
-    if chunk:
-        from helpers import pipeline
-        from wgsparkl_amd import MpmData
-        pipe = pipeline(dim)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
-        for _ in range(k // chunk):
-            pipe.step(data, chunk)
-            data.sync()
-    else:
-        data = run_gpu(sc, k)
+    data = step_chunks(sc, (chunk,) * (k // chunk) if chunk else (k,))
     st = run_oracle(sc, k, np.float32)
     st64 = run_oracle(sc, k, np.float64)
     cells, vm, dist, aff, closest = data.read_grid()
@@ -436,38 +408,28 @@ def test_long_near_collider_list_paths_match_the_separate_launches_and_the_oracl
     launches (WGS_DEBUG P2G_TWO_LAUNCHES) — which path runs depends on when the host last synchronised, so the result must not —,
     the paired G2P agrees with the separate kernels (WGS_DEBUG G2P_TWO_LAUNCHES, a debug path; another compilation of the same
     source, one ulp apart), and the run matches the oracle."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     sc = scenes.corotated_cube_with_paddle(n_side=64)
 
     def run():
-        pipe = pipeline(3)
-        data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        pipe.step(data, 4)
-        data.sync()                                            # the host sees the list here
-        pipe.step(data, 4)
-        data.sync()
+        data = step_chunks(sc, (4, 4))                         # the host sees the list after the first call
         assert data.stats()["num_near_collider_blocks"] > 100  # a long list: the paired P2G launch is the one that ran
         return data.read_particles(), data.read_body_poses()
     pa, ba = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("P2G_TWO_LAUNCHES"))
-    pb, bb = run()
-    for f in ("pos", "vel", "def_grad", "affine", "cdf_affinity"):
-        assert np.array_equal(getattr(pa, f), getattr(pb, f)), f
-    for x, y in zip(ba, bb):
-        for key in ("translation", "rotation", "linvel", "angvel"):
-            assert np.array_equal(x[key], y[key]), key
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("G2P_TWO_LAUNCHES"))
-    pc, _ = run()
-    assert np.array_equal(pa.cdf_affinity, pc.cdf_affinity)
-    for f in ("pos", "vel", "def_grad"):
-        assert rel_rms(getattr(pc, f), getattr(pa, f)) < 1e-6, f
-    st, st64 = run_oracle(sc, 8, np.float32), run_oracle(sc, 8, np.float64)
-    same = pa.cdf_affinity == st.arr["cdf_affinity"]
-    assert same.mean() > 0.999
-    for f, tol in (("pos", 2e-6), ("vel", 2e-4)):
-        err, err32 = rel_rms(getattr(pa, f)[same], st64.arr[f][same]), rel_rms(st.arr[f][same], st64.arr[f][same])
-        assert err < max(tol, 10.0 * err32), (f, err, err32)
+    with debug(monkeypatch, "P2G_TWO_LAUNCHES"):
+        pb, bb = run()
+        assert_same_bits(pa, pb, AFFINITY_FIELDS)
+        assert_same_bodies(ba, bb, ("translation", "rotation", "linvel", "angvel"))
+    with debug(monkeypatch, "G2P_TWO_LAUNCHES"):
+        pc, _ = run()
+        assert np.array_equal(pa.cdf_affinity, pc.cdf_affinity)
+        for f in ("pos", "vel", "def_grad"):
+            assert rel_rms(getattr(pc, f), getattr(pa, f)) < 1e-6, f
+        st, st64 = run_oracle(sc, 8, np.float32), run_oracle(sc, 8, np.float64)
+        same = pa.cdf_affinity == st.arr["cdf_affinity"]
+        assert same.mean() > 0.999
+        for f, tol in (("pos", 2e-6), ("vel", 2e-4)):
+            err, err32 = rel_rms(getattr(pa, f)[same], st64.arr[f][same]), rel_rms(st.arr[f][same], st64.arr[f][same])
+            assert err < max(tol, 10.0 * err32), (f, err, err32)
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -475,17 +437,13 @@ def test_random_api_sequences_match_oracle(hip_libs, oracle_libs, seed):
     """Fuzz of the per-frame host writes (src_testbed/step.rs:79-119, ui.rs:91-104) interleaved with steps: random
     sequences of step / set_sim_params / set_body_velocities / full collider refresh, mirrored on the fp32 oracle."""
     import dataclasses
-    from helpers import oracle, pipeline
-    from wgsparkl_amd import MpmData, _ffi
     sc = _random_scene(seed)
     if not sc["colliders"]:
         sc["colliders"] = [Collider.ball(1.5, tuple([5.0] * sc["particles"].dim))]
     dim = sc["particles"].dim
     rng = np.random.default_rng(7000 + seed)
-    pipe = pipeline(dim)
-    args = (sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-    data = MpmData.new(pipe, sc["params"], sc["particles"], *args)
-    st = oracle(dim, np.float32).new_state(sc["particles"], sc["params"], *args)
+    pipe, data = new_data(sc)
+    st = oracle(dim, np.float32).new_state(sc["particles"], sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
     cols = list(sc["colliders"])
     nc = len(cols)
     for _ in range(7):
@@ -530,14 +488,10 @@ def test_body_setters_and_readback(hip_libs, oracle_libs):
     pose read-back of the testbed (src_testbed/step.rs:79-132): the device-integrated poses are not rolled back
     by a velocity write, a pose write moves the centre of mass with the body."""
     from golden_cases import dynamic_ball3d
-    from helpers import oracle, pipeline
-    from wgsparkl_amd import MpmData
     import dataclasses
     sc = dynamic_ball3d()
-    args = (sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], *args)
-    st = oracle(3, np.float64).new_state(sc["particles"], sc["params"], *args)
+    pipe, data = new_data(sc)
+    st = oracle(3, np.float64).new_state(sc["particles"], sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
     pipe.step(data, 30); st.step(30)
     # velocity write only: poses keep what the device integrated
     cur = st.collider_states()
@@ -545,7 +499,6 @@ def test_body_setters_and_readback(hip_libs, oracle_libs):
     vel = (data.T.Velocity * 2)()
     vel[0].linear = (0.1, -1.0, 0.0); vel[0].angular = (0.0, 0.5, 0.0)
     vel[1].linear = (0.0, 0.2, 0.0); vel[1].angular = (0.0, 0.0, -0.3)
-    from wgsparkl_amd import _ffi
     _ffi.check(data.lib, data.lib.wgs_set_body_velocities(data._h, vel, 2))
     for i in range(2):
         for k in range(3):
@@ -603,12 +556,9 @@ def test_c_abi_rejects_bad_arguments(hip_libs):
     wgs_last_error explains."""
     import ctypes as C
     from golden_cases import mesh_floor3d
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     from wgsparkl_amd.sampling import build_rigid_particles
     sc = mesh_floor3d()
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc)
     lib, T, h = data.lib, data.T, data._h
     assert lib.wgs_step(None, h, 1, 0) != 0 and lib.wgs_step(pipe._h, None, 1, 0) != 0
     assert lib.wgs_set_sim_params(h, None) != 0
@@ -639,7 +589,7 @@ def test_c_abi_rejects_bad_arguments(hip_libs):
     assert np.isfinite(data.read_positions()).all()
     many = [Collider.ball(1.0, (0.0, 0.0, 0.0))] * 17                    # the CPIC mask has 16 bits
     with pytest.raises(Exception):
-        MpmData.new(pipe, sc["params"], sc["particles"], many, sc["cell_width"], sc["grid_capacity"], sc["model"])
+        new_data(sc, colliders=many)
 
 
 _GOLD = np.load(_os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "golden", "oracle_regression.npz"))
@@ -711,11 +661,8 @@ def test_timestamps_and_stats(hip_libs):
 
 def test_queue_step_replay_api(hip_libs, oracle_libs):
     """The reference's call shape: queue_step once, encode N times (src_testbed/step.rs:122-128)."""
-    from wgsparkl_amd import KernelInvocationQueue, MpmData
-    from helpers import pipeline
     sc = cloud_scene(n=5000, seed=13)
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], [], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc, colliders=[])
     q = KernelInvocationQueue()
     pipe.queue_step(data, q, add_timestamps=False)
     for _ in range(3):
@@ -728,12 +675,8 @@ def test_queue_step_replay_api(hip_libs, oracle_libs):
 
 def test_set_sim_params_and_colliders(hip_libs, oracle_libs):
     """Per-frame host->device writes of the testbed (src_testbed/step.rs:79-119, ui.rs:91-104)."""
-    from helpers import oracle, pipeline
-    from wgsparkl_amd import MpmData
     sc = _CASES["tilted_box2d"][0]()
-    pipe = pipeline(2)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"],
-                       sc["model"])
+    pipe, data = new_data(sc)
     st = oracle(2, np.float32).new_state(sc["particles"], sc["params"], sc["colliders"], sc["cell_width"],
                                          sc["grid_capacity"], sc["model"])
     pipe.step(data, 5); st.step(5)
@@ -751,7 +694,6 @@ def test_set_sim_params_and_colliders(hip_libs, oracle_libs):
     assert same.mean() > 0.995
     assert rel_rms(got.pos[same], st.arr["pos"][same]) < 1e-5
     assert rel_rms(got.vel[same], st.arr["vel"][same]) < 1e-4
-
 
 
 def _flying_cube(speed, dt, capacity):
@@ -774,8 +716,7 @@ def test_oracle_parity_through_eviction_id_reuse_table_refresh_and_host_looks(hi
     of the fp64 oracle — and the run did evict, did reuse ids and did refresh the table (wgs_stats), with no table rebuild after the first substep."""
     sc = _flying_cube(150.0, 1.0 / 300.0, 512)
     ps = sc["particles"]
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc)
     st32 = oracle(3, np.float32).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], 4096, sc["model"])
     st64 = oracle(3, np.float64).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], 4096, sc["model"])
     handed_out = 0
@@ -814,8 +755,7 @@ def test_oracle_parity_of_the_reference_sand3_scene_across_host_looks(hip_libs, 
     oracle at the end."""
     sc = scenes.reference_sand3()
     ps = sc["particles"]
-    pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc)
     st32 = oracle(3, np.float32).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
     st64 = oracle(3, np.float64).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
     def block_of_particle(vid, first, num, ids):
@@ -861,19 +801,13 @@ def test_one_call_of_two_thousand_substeps_keeps_its_table_in_order(hip_libs):
     counters every 64 substeps it has queued (capi_lifecycle.inc wgs_step: watch_counters + maintain_grid of host_grid.inc): the run ends without overflow, the table was refreshed on the way, and
     the result is the bits of the same 2 000 substeps queued a hundred at a time."""
     sc = _flying_cube(40.0, 1.0 / 300.0, 512)
-    ps = sc["particles"]
-    pipe = pipeline(3)
 
     def run(chunks):
-        data = MpmData.new(pipe, sc["params"], ps, sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for k in chunks:
-            pipe.step(data, k)
-            data.sync()
+        data = step_chunks(sc, chunks)
         return data.read_particles(), data.stats()
     a, sa = run((2000,))
     b, sb = run((100,) * 20)
     assert sa["overflow"] == 0 and sb["overflow"] == 0, (sa, sb)
     assert sa["table_rebuilds"] == 1 and sb["table_rebuilds"] == 1, (sa["table_rebuilds"], sb["table_rebuilds"])
     assert sa["table_marks"] <= sa["grid_capacity"], sa      # (the marks never outnumber half the table's slots: 2 x capacity)
-    for f in ("pos", "vel", "def_grad", "affine"):
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert_same_bits(a, b, BASE_FIELDS)

@@ -4,13 +4,11 @@ import numpy as np
 import pytest
 
 from wgsparkl_amd import scenes
-from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
-from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
+from wgsparkl_amd.models import ParticlePhase
+from wgsparkl_amd.solver import Collider, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, debug_switches, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
-from gpu_common import (CPIC_GRID_V_TOL, CPIC_PART_TOL, FUZZ_BODY_ATOL, FUZZ_NODE_MISMATCH, FUZZ_PART_MISMATCH, FUZZ_VEL_TOL, GRID_V_TOL, PART_TOL,
-                        _exploding_cube, _native_slabs, _random_scene, check_blocks, check_fields, check_grid, cloud_scene)
-import os as _os
+from helpers import debug, max_abs, new_data, pipeline, rel_rms, report_margin, run_gpu
+from gpu_common import FUZZ_BODY_ATOL, _native_slabs
 
 from golden_cases import CASES as _CASES
 
@@ -22,16 +20,12 @@ def test_bench_decomposition_eight_ranks_on_one_gpu(hip_libs):
     the floor collider, bench.py's buffer capacities) advanced as a lockstep group on one GPU — wgs_sharded_step_lockstep:
     the per-phase code of wgs_sharded_step with device-to-device copies as the transport —: same particles as the
     single-domain run of the whole bar, none lost."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     from wgsparkl_amd.sharded import NativeShard, native_lockstep, uniform_material_of
     world, n_side, k = 8, 24, 40
-    pipe = pipeline(3)
     full = scenes.neo_hookean_bar(n_side=n_side, world=world, rank=None)
     vx = lambda gid: (8.0 + 3.0 * np.sin(0.37 * gid.astype(np.float64))).astype(np.float32)   # particles cross the faces
     full["particles"].vel[:, 0] = vx(full["global_ids"])
-    ref_data = MpmData.new(pipe, full["params"], full["particles"], full["colliders"], full["cell_width"],
-                           full["grid_capacity"] * 4, full["model"])
+    pipe, ref_data = new_data(full, grid_capacity=full["grid_capacity"] * 4)
     pipe.step(ref_data, k)
     ref = ref_data.read_particles()
     shards, total = [], 0
@@ -68,7 +62,6 @@ def test_random_scenes_sharded_match_single_domain(hip_libs, seed):
     """Fuzz-style check of the decomposition: random clouds (stretched along x so that every slab is a few blocks wide)
     with kinematic analytic colliders, cut into 2-4 slabs, advanced as a lockstep group (wgs_sharded_step_lockstep),
     against the single-domain run on the same GPU."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     rng = np.random.default_rng(500 + seed)
     dim = 3 if seed % 2 == 0 else 2
@@ -114,7 +107,6 @@ def test_sharded_run_with_kinematic_collider(hip_libs):
     """configs[3]'s decomposition on one GPU at a small size: the corotated bar on the floor, cut into 4 slabs, and the
     kinematic rotating cuboid at its end, which every rank integrates identically; particles, CPIC state and the body
     pose match the single-domain run (the bar slides towards the cuboid, so particles cross the cuts)."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import NativeShard, native_lockstep, uniform_material_of
     k, world, n = 30, 4, 24
 
@@ -160,7 +152,6 @@ def test_dynamic_bodies_on_sharded_data(hip_libs, name):
     fixed-point impulses of its own particles, the sums are reduced over the slabs before integrate_bodies. Against
     the single-domain run of the golden scene: the bodies to the fixed-point resolution (1e-5 per node and substep:
     a node's impulse is truncated per slab here, once in a single domain), the particles to fp32 round-off."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     make, k = _CASES[name]
     sc = make()
@@ -200,7 +191,6 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
     the P2G launch (GU = 3: slabs handed over word by word); the interface layers are updated after the
     exchange. WGS_DEBUG GU_OWN_LAUNCH brings the k_pack_face launch and the one grid update back: the same bits on every slab
     (3 slabs in lockstep, a floor, particles migrating, a table rebuild inside the run)."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     monkeypatch.setenv("WGS_REHASH_PERIOD", "64")
     world = 3
@@ -226,21 +216,18 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
             sh.sync()
         return [sh.export() for sh in shards]
     a = run()
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("GU_OWN_LAUNCH"))
-    b = run()
-    monkeypatch.delenv("WGS_DEBUG")
+    with debug(monkeypatch, "GU_OWN_LAUNCH"):
+        b = run()
     # wgs_sharded_step with neighbours splits P2G: the two block layers at each cut first (their slabs are what the messages
     # are gathered from: they run beside the exchange on a stream of their own), every other block and the interior's grid
     # update in a second launch. WGS_DEBUG SHARD_SPLIT_LAYERS splits the lockstep slabs the same way (on their one stream): same bits.
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("SHARD_SPLIT_LAYERS"))
-    c = run()
-    monkeypatch.delenv("WGS_DEBUG")
+    with debug(monkeypatch, "SHARD_SPLIT_LAYERS"):
+        c = run()
     # A slab's fused G2P bins its residents for the next substep (the guests it drops leave their block's total) and
     # k_g2p_arrivals the particles that arrive (Dev::bin_next); WGS_DEBUG REBIN_LAUNCH brings launch 1 of the sort, k_rebin, back:
     # the same bits, the same storage order.
-    monkeypatch.setenv("WGS_DEBUG", debug_switches("REBIN_LAUNCH"))
-    e = run()
-    monkeypatch.delenv("WGS_DEBUG")
+    with debug(monkeypatch, "REBIN_LAUNCH"):
+        e = run()
     for other in (b, c, e):
         for x, y in zip(a, other):
             ox, oy = np.argsort(x["ids"]), np.argsort(y["ids"])    # (the storage order of a slab follows the arrival order of its guests)
@@ -253,7 +240,6 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
 def test_native_lockstep_matches_single_domain(hip_libs, world, dim, monkeypatch):
     """wgs_sharded_step_lockstep — the C++ driver of the substep protocol that wgs_sharded_step runs per rank over
     RCCL — reproduces the single-domain run (80 substeps: crosses a table rebuild; particles migrate)."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import associated_block_x, native_lockstep
     monkeypatch.setenv("WGS_REHASH_PERIOD", "64")             # table rebuilds inside the run (developer override, same results)
     # a bar along x, a few blocks per slab (a slab between two neighbours must be at least 3 blocks wide)
@@ -297,7 +283,6 @@ def test_particles_enter_an_empty_slab_and_leave_theirs_empty(hip_libs, with_flo
     the first arrivals find none of their blocks active on their new rank and read their nodes from the message (the old
     owner's partial sums are then the totals; with the floor also the node cdfs, evaluated on the spot) — and keeps going
     until slab 0 is empty. Both against the single-domain run."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, native_lockstep, split_scene, uniform_material_of
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=with_floor)
     ps = sc["particles"]
@@ -338,7 +323,6 @@ def test_slabs_evict_the_blocks_a_body_leaves_behind(hip_libs):
     rebuilt its table every 1 024 substeps and whenever a moving body had used up the ids). A 16^3 cube flies through three slabs at a third of
     a cell per substep, with a block capacity that 150 substeps of its trail would exhaust: every slab builds its table once, ids come back
     on the free lists, nothing overflows, and the particles are those of the single-domain run."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, native_lockstep, split_scene, uniform_material_of
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=False)
     ps = sc["particles"]
@@ -384,7 +368,6 @@ def test_mesh_colliders_on_sharded_data(hip_libs, name):
     """Mesh colliders (rigid-particle samples) on slabs: every slab holds every sample, the node cdfs of the
     nodes two slabs share are computed by both from the same inputs. Two slabs in lockstep against the single-domain run of
     the golden scene: the same particles on the same side of the mesh, fields to fp32 round-off."""
-    from helpers import pipeline
     from wgsparkl_amd.sharded import native_lockstep
     make, k = _CASES[name]
     sc = make()
@@ -413,9 +396,6 @@ def test_native_sharded_step_over_rccl_one_rank(hip_libs):
     (b) WGS_COMM_SELF_NEIGHBOURS: the rank is its own lower and upper neighbour, so every ncclSend / ncclRecv group
     of an interior rank is issued and matched (its physics is meaningless: the slab adds its own halo to itself) —
     the run must complete, keep its particles and report no error."""
-    import ctypes as C
-    from helpers import pipeline
-    from wgsparkl_amd import _ffi
     from wgsparkl_amd.sharded import INT_MAX, INT_MIN, NativeComm, NativeShard
     sc = scenes.neo_hookean_cube(n_side=24, with_floor=True)
     ps = sc["particles"]
@@ -452,8 +432,6 @@ def test_single_domain_data_and_a_lone_slab_answer_alike(hip_libs, dim):
     """`MpmData` and `NativeShard` are one `wgs_data` handle (pipeline.DataHandle): the same small scene with a kinematic ball that
     moves and spins, as single-domain data and as one slab without neighbours, answers `stats()` and `read_body_poses()` alike —
     the same keys, `com` among them — before any substep and after two. Host glue only: the particles are the other tests' matter."""
-    from helpers import pipeline
-    from wgsparkl_amd import MpmData
     from wgsparkl_amd.sharded import INT_MAX, INT_MIN, NativeShard
     if dim == 3:
         sc = scenes.neo_hookean_cube(n_side=8)                         # 512 particles, cells 20..24 x 8..12 x 20..24
@@ -462,8 +440,7 @@ def test_single_domain_data_and_a_lone_slab_answer_alike(hip_libs, dim):
         sc = scenes.elastic_block_2d(nx=22, ny=22, with_floor=False)   # 484 particles, cells 7..18 x 7..18
         ball = Collider.ball(1.5, (12.0, 4.5), linvel=(0.5, 0.25, 0.0), angvel=(0.3,))
     ps, cols = sc["particles"], [ball]
-    pipe = pipeline(dim)
-    data = MpmData.new(pipe, sc["params"], ps, cols, sc["cell_width"], sc["grid_capacity"], sc["model"])
+    pipe, data = new_data(sc, colliders=cols)
     slab = NativeShard(pipe, sc["params"], ps, np.arange(ps.n, dtype=np.uint32), cols, sc["cell_width"], sc["grid_capacity"],
                        INT_MIN, INT_MAX, has_lower=False, has_upper=False, particle_capacity=ps.n, model=sc["model"], comm=None)
 

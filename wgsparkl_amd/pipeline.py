@@ -385,6 +385,13 @@ class MpmData(DataHandle):
             particles = ParticleSet.from_particles(particles)
         return cls(pipeline, params, particles, colliders, cell_width, grid_capacity, model)
 
+    @classmethod
+    def from_scene(cls, pipeline, scene, **overrides):
+        """`new` from one of the dicts `wgsparkl_amd.scenes` returns (a missing "model" is MODEL_COROTATED); a keyword replaces the
+        scene's entry of that name for this call: `colliders=[]`, `grid_capacity=128`, `particles=snap`."""
+        sc = {"model": MODEL_COROTATED, **scene, **overrides}
+        return cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+
     def set_particle_models(self, models):
         """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —
         fluid and solids in one simulation, coupled through the grid. `None` drops the table. Blocking."""

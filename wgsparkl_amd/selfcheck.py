@@ -62,7 +62,7 @@ def compare_with_single_domain(pipe, dist, comm, world, rank, slab, full_scene, 
         full = full_scene()
         fp = full["particles"]
         gid = np.asarray(full.get("global_ids", np.arange(fp.n)), np.int64)
-        data = MpmData.new(pipe, full["params"], fp, full["colliders"], full["cell_width"], full["grid_capacity"], full["model"])
+        data = MpmData.from_scene(pipe, full)
         pipe.step(data, substeps)
         data.sync()
         ref = data.read_particles()
