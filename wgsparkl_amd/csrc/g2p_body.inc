@@ -11,6 +11,11 @@
     constexpr bool CPIC = G2P_CMODE == 2;
     constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE, NN = Dim<D>::NNBR;
     constexpr int DD = D * D;
+    // the node tile staged slice by slice (below): the one-chunk main body of the neo-Hookean elastic kernels in 3D on single-domain data — the
+    // headline's pair and its collider-free twin, the two instantiations the change was timed on (notes/round_15.md). The list walk and the
+    // multi-chunk kernels keep a staged tile across chunks, 2D tiles have no slices; the other models' one-chunk kernels, the plastic ones and a
+    // slab's would take the same text and keep the whole tile until somebody times them.
+    constexpr bool SLICES = D == 3 && G2P_CMODE != 2 && npass == 1u && MODEL == 1 && !PLASTIC && !SHARD;
     using P = Pl<D>;
 
     const float *in = d.buf[side];
@@ -308,12 +313,43 @@
                 // g2p.wgsl:72-132: velocities of the block's nodes and of its +1 rim -> LDS tile. The grid
                 // update left them in the block's own slab, so this is one contiguous read.
                 // (the slab is stored by regions, layout.h: read linearly, placed by tile index)
-                // (the tile index of a slab position comes from a table in constant memory, fetched with the slab itself)
-                for (int n = tid; n < TILE; n += G2P_THREADS) {
-                    uint32_t np = (uint32_t)n;
-                    // (pinned in the list walk: slab + 16 n would otherwise live as a 64-bit loop invariant per round — in scratch, there)
-                    if constexpr (G2P_CMODE == 2) asm volatile("" : "+v"(np));
-                    s_node[g_slab_tile_map.t[n]] = d.slab[(size_t)b * TILE + np];
+                // (the tile index of a slab position comes from a table in constant memory, fetched with the slab itself;
+                // the slice-wise staging walks in tile order and computes the slab position: layout.h slab_pos_of_tile)
+                if constexpr (SLICES) {
+                    // One chunk per wave, in 3D: only the z-slices of the tile that this chunk's cells of b reach. A chunk covers consecutive
+                    // cells of the sorted order — at 8 particles per cell half a z-layer of the block —, and a particle in cell layer z reads
+                    // the slices z .. z + 2: 108 of the 216 nodes, two rounds of slab loads and LDS writes per lane instead of four. The
+                    // layers come from the lanes this body advances in b (four ballots, scalar); LDS is indexed by tile node as before.
+                    const uint32_t lz = (cid >> (2 * BS)) & (uint32_t)(BW - 1);
+                    uint32_t zmask = 0u;
+    #pragma unroll
+                    for (int k = 0; k < BW; k++) zmask |= __ballot(mine && lz == (uint32_t)k) != 0ull ? 1u << k : 0u;
+                    const int n0 = (__ffs((int)zmask) - 1) * TW * TW, n1 = (32 - __clz((int)zmask) + 2) * TW * TW;
+                    // (every load before the first LDS write, like the unrolled whole-tile loop; a lane past the end asks for the last node
+                    // again instead of leaving the round through a branch; the rounds nobody needs are skipped by the whole wave)
+                    static_assert(!SLICES || (TILE > 3 * G2P_THREADS && TILE <= 4 * G2P_THREADS && 3 * TW * TW > G2P_THREADS), "four rounds at most, the first two always");
+                    auto slab_node = [&](int r) -> float4 {
+                        const uint32_t sp = slab_pos_of_tile<D>((uint32_t)min(n0 + r * G2P_THREADS + tid, n1 - 1));
+                        return d.slab[(size_t)b * TILE + sp];
+                    };
+                    const bool r2 = n0 + 2 * G2P_THREADS < n1, r3 = n0 + 3 * G2P_THREADS < n1;   // (wave-uniform)
+                    const float4 q0 = slab_node(0), q1 = slab_node(1);
+                    float4 q2 = make_float4(0.f, 0.f, 0.f, 0.f), q3 = q2;   // (not copies of q1: a copy waits for q1)
+                    if (r2) q2 = slab_node(2);
+                    if (r3) q3 = slab_node(3);
+                    s_node[n0 + tid] = q0;
+                    if (n0 + G2P_THREADS + tid < n1) s_node[n0 + G2P_THREADS + tid] = q1;
+                    if (n0 + 2 * G2P_THREADS + tid < n1) s_node[n0 + 2 * G2P_THREADS + tid] = q2;
+                    if (n0 + 3 * G2P_THREADS + tid < n1) s_node[n0 + 3 * G2P_THREADS + tid] = q3;
+                    // (`staged = b` below then names a PARTLY staged tile. Nobody can take it for a whole one: with one chunk per wave the
+                    // outer loop runs once and `while (todo)` meets every block once. A kernel that revisits a block must not set SLICES.)
+                } else {   // the whole tile, for the chunks and visits that follow in this wave
+                    for (int n = tid; n < TILE; n += G2P_THREADS) {
+                        uint32_t np = (uint32_t)n;
+                        // (pinned in the list walk: slab + 16 n would otherwise live as a 64-bit loop invariant per round — in scratch, there)
+                        if constexpr (G2P_CMODE == 2) asm volatile("" : "+v"(np));
+                        s_node[g_slab_tile_map.t[n]] = d.slab[(size_t)b * TILE + np];
+                    }
                 }
                 if constexpr (CPIC) {
                     if constexpr (G2P_CMODE == 2) stage_node_cdf_tile_links<D, G2P_THREADS>(d, visit_link, s_cdf, tid);   // (b is the visit's block: its links are here)

@@ -417,6 +417,26 @@ template <int D> struct SlabTileMap {
     }
 };
 __constant__ SlabTileMap<WGS_DIM> g_slab_tile_map = SlabTileMap<WGS_DIM>();
+// ... and the other way round, slab position of tile index t: for the kernel that walks a PART of the tile in tile order (the one-pass
+// fused G2P stages only the z-slices its chunk's cells reach, g2p_body.inc). Arithmetic, not a second table: the position stands in
+// front of the slab load, and a table entry would be a dependent load in front of it.
+template <int D> __host__ __device__ constexpr uint32_t slab_pos_of_tile(uint32_t t) {
+    constexpr uint32_t BW = Dim<D>::BW, TW = Dim<D>::TW, BS = Dim<D>::BSHIFT;
+    const uint32_t tz = D == 3 ? t / (TW * TW) : 0u, r = D == 3 ? t - tz * (TW * TW) : t, ty = r / TW, tx = r - ty * TW;
+    const uint32_t ox = tx >= BW ? 1u : 0u, oy = ty >= BW ? 1u : 0u, oz = tz >= BW ? 1u : 0u;
+    const uint32_t o = ox | (oy << 1) | (oz << 2);
+    unsigned long long bases = 0ull;   // slab_region_base of the 2^D regions, a byte each
+    for (int q = 0; q < (1 << D); q++) bases |= (unsigned long long)slab_region_base<D>(q) << (8 * q);
+    const uint32_t sx = ox ? 1u : BS, sy = oy ? 1u : BS;   // log2 of the region's extents
+    return (uint32_t)((bases >> (8u * o)) & 0xffull) + (tx - ox * BW) + (((ty - oy * BW) + ((tz - oz * BW) << sy)) << sx);
+}
+template <int D> constexpr bool slab_pos_of_tile_inverts_the_map() {
+    static_assert(slab_region_base<D>((1 << D) - 1) < 256, "the region bases are packed a byte each");
+    for (int p = 0; p < Dim<D>::TILE; p++)
+        if (slab_pos_of_tile<D>(slab_tile_of<D>((uint32_t)p)) != (uint32_t)p) return false;
+    return true;
+}
+static_assert(slab_pos_of_tile_inverts_the_map<2>() && slab_pos_of_tile_inverts_the_map<3>(), "slab_pos_of_tile is the inverse of slab_tile_of at every node");
 
 // Quad access = (one uniform 64-bit buffer base in SGPRs) + (32-bit per-lane byte offset):
 // `global_load_dwordx4 v[..], v_off, s[base:base+1]`. Valid while one ping-pong buffer is
