@@ -102,6 +102,9 @@ class Oracle:
         for name in ("orc_grid_update_cdf", "orc_grid_update"):
             getattr(L, name).argtypes = [C.POINTER(Params), C.POINTER(Grid)]
         L.orc_particle_update.argtypes = [C.POINTER(Particles), C.POINTER(Params)]
+        L.orc_update_rigid_particles.argtypes = [C.POINTER(Params), C.POINTER(Rigid)]
+        L.orc_sort_rigid.argtypes = [C.POINTER(Particles), C.POINTER(Params), C.POINTER(Grid), C.POINTER(Rigid)]
+        L.orc_p2g_cdf.argtypes = [C.POINTER(Params), C.POINTER(Grid), C.POINTER(Rigid)]
         L.orc_step.argtypes = [C.POINTER(Particles), C.POINTER(Params), C.POINTER(Grid), C.c_int]
 
     # ---- small helpers -------------------------------------------------
@@ -330,6 +333,21 @@ class OracleState:
     def grid_update(self): self.orc.lib.orc_grid_update(C.byref(self.prm), C.byref(self.G))
     def g2p(self): self.orc.lib.orc_g2p(C.byref(self.P), C.byref(self.prm), C.byref(self.G))
     def particle_update(self): self.orc.lib.orc_particle_update(C.byref(self.P), C.byref(self.prm))
+
+    # the rigid-particle passes of mesh colliders, in the order of orc_step_full: update_rigid_particles, sort_rigid,
+    # grid_update_cdf, p2g_cdf, g2p_cdf (without a mesh collider the first and the last are no-ops and sort_rigid is sort)
+    def update_rigid_particles(self):
+        if self.R is not None:
+            self.orc.lib.orc_update_rigid_particles(C.byref(self.prm), C.byref(self.R))
+
+    def sort_rigid(self):
+        if self.R is None:
+            return self.sort()
+        self.orc.lib.orc_sort_rigid(C.byref(self.P), C.byref(self.prm), C.byref(self.G), C.byref(self.R))
+
+    def p2g_cdf(self):
+        if self.R is not None:
+            self.orc.lib.orc_p2g_cdf(C.byref(self.prm), C.byref(self.G), C.byref(self.R))
 
     def update_world_mass_properties(self):
         self.orc.lib.orc_update_world_mass_properties(self.cols, self.bodies, self.n_colliders)

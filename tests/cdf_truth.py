@@ -82,6 +82,8 @@ def colliders_of(colliders, d, poses=None):
         shape[:len(c.shape)] = f32(c.shape)
         out.append(dict(shape_type=int(c.shape_type), shape=shape, R=rot_matrix(f32(rot), d), trans=f32(tr)[:d].copy(),
                         scale=float(np.float32(c.scale))))
+        if getattr(c, "vertices", None) is not None:        # a mesh collider: its local fp32 vertices and primitives
+            out[-1].update(vertices=f32(c.vertices).reshape(-1, d), indices=np.asarray(c.indices, np.int64).reshape(-1, d))
     return out
 
 
@@ -137,9 +139,12 @@ class NodeField:
 
     aff, dist, closest: what the kernel stores. b_dist [M]: bound of `dist`. und_bits [M]: the affinity / sign bits an
     fp32 evaluation may decide either way; und_dist [M]: the voter set is undecided (distance and closest id are then
-    not compared); und_tie [M]: two voters tie for the closest id within their bounds."""
+    not compared); und_tie [M]: two voters tie for the closest id within their bounds.
 
-    def __init__(self, cols, d, h, cells, u=U32, variant=()):
+    rigid: the mesh_truth.Rigid of the scene's mesh colliders at the same poses (None: mesh colliders leave no trace, as
+    without one); it fills their columns, which merge like the analytic ones."""
+
+    def __init__(self, cols, d, h, cells, u=U32, variant=(), rigid=None):
         cells = np.asarray(cells, np.int64)
         M = len(cells)
         self.d, self.h, self.cells = d, float(h), cells
@@ -152,7 +157,7 @@ class NodeField:
         dist_c, b_c = big.copy(), np.zeros_like(big)
         voter = np.zeros_like(big, bool)
         inside = voter.copy()
-        aff_und, in_und, exact_c = voter.copy(), voter.copy(), voter.copy()
+        aff_und, in_und, exact_c, dist_und = voter.copy(), voter.copy(), voter.copy(), voter.copy()
         self.sd = big.copy()
         for i in range(nc):
             c = cols[i]
@@ -188,6 +193,8 @@ class NodeField:
             voter[:, i], inside[:, i], dist_c[:, i], b_c[:, i] = ins | within, ins, dist, b_d
             aff_und[:, i], in_und[:, i], exact_c[:, i] = au, iu, exact
             self.sd[:, i] = sd * s
+        if rigid is not None:
+            rigid.fill(cells, nc, voter, inside, dist_c, b_c, aff_und, in_und, exact_c, dist_und)
         dm = np.where(voter, dist_c, np.inf)
         dmin = dm.min(1)
         any_v = np.isfinite(dmin)
@@ -199,7 +206,7 @@ class NodeField:
         sh = np.arange(dm.shape[1], dtype=np.uint32)
         self.aff = ((voter.astype(np.uint32) << sh) | (inside.astype(np.uint32) << (sh + 16))).sum(1).astype(np.uint32) if nc else np.zeros(M, np.uint32)
         self.und_bits = ((aff_und.astype(np.uint32) << sh) | (in_und.astype(np.uint32) << (sh + 16))).sum(1).astype(np.uint32) if nc else np.zeros(M, np.uint32)
-        self.und_dist = aff_und.any(1)
+        self.und_dist = aff_und.any(1) | dist_und.any(1)
         # ties for the closest id: another voter within the two bounds of the minimum (equal and exact: decided, lowest id)
         rows = np.arange(M)
         bmin = b_c[rows, first]
@@ -325,7 +332,8 @@ class ParticleField:
             fresh = ((prev >> np.uint32(c)) & 1) == 0
             bit = np.where(fresh, vote < 0.0, ((prev >> np.uint32(16 + c)) & 1).astype(bool))
             signs |= bit.astype(np.uint32) << np.uint32(16 + c)
-            und_vote |= fresh & has.any(1) & (np.abs(vote) <= bvote)
+            # (a vote of exact zeros, every term w * 0 with nothing to round, is decided: not negative)
+            und_vote |= fresh & has.any(1) & (np.abs(vote) <= bvote) & ~((bvote == 0.0) & (vote == 0.0))
             self.vote[:, c], self.b_vote[:, c] = vote, bvote
         und |= und_vote
         self.why['vote'] = und_vote
@@ -433,8 +441,11 @@ def from_truth_nodes(pos, h, nf: NodeField, prev_aff=None, variant=()):
     return ParticleField(pos, h, nf.cells, nf.dist, nf.aff, prev_aff, node_b=nb, node_und=nf.und_bits & np.uint32(0xffff), variant=variant)
 
 
-def active_cells(pos32, h, d):
-    """world cells of the nodes of the active blocks (the associated block of every particle and its + neighbours), sorted"""
+def active_cells(pos32, h, d, rigid=None):
+    """world cells of the nodes of the active blocks (the associated block of every particle and its + neighbours; with
+    `rigid`, a mesh_truth.Rigid, the blocks its samples add to them as well), sorted"""
+    if rigid is not None:
+        return block_cells(rigid.set_particles(pos32), d)
     bw = T.bw_of(d)
     blk = assoc_cell(np.asarray(pos32, np.float32), h) // bw
     offs = np.unique(T.shifts_of(d) % 2, axis=0)
@@ -478,13 +489,15 @@ def signed_distance(cols, x, d):
     return out
 
 
-def _static(d, h, rng, colliders, boxes, n, uniform=False, keep=None, rim_keep=None):
+def _static(d, h, rng, colliders, boxes, n, uniform=False, keep=None, rim_keep=None, rim_units=None):
     """n particles at rest (v = 0, C = 0, F = I, no gravity) uniformly in the union of the boxes [(lo, hi)].
     A particle at the rim of a collider's reach has one layer of collider-affine nodes in its stencil: its Gram matrix
     is singular, and whether an fp32 determinant of it passes the absolute 1e-8 test depends on h (at h = 2 it is noise
     of 1e-7). Such particles are undecided by nature; of the candidates farther than RIM h from every collider the
     scenes keep `rim_keep`, so n counts candidates, not particles. Where h makes them decidable (h <= RIM_H: the noise
-    of the determinant, ~3000 u (h^2 / 4)^D, stays below 1e-8) all are kept by default."""
+    of the determinant, ~3000 u (h^2 / 4)^D, stays below 1e-8) all are kept by default.
+    `rim_units`: the distance of fp32 positions to the colliders in units of the rim (scenes with mesh colliders, whose
+    reach is their samples' stencil: mesh_truth.rim_units); default: the analytic signed distance / (RIM h)."""
     if rim_keep is None:
         rim_keep = 1.0 if h <= RIM_H else RIM_KEEP
     from wgsparkl_amd.solver import SimulationParams
@@ -493,7 +506,8 @@ def _static(d, h, rng, colliders, boxes, n, uniform=False, keep=None, rim_keep=N
     pos = np.concatenate([rng.uniform(np.asarray(lo[:d], np.float64), np.asarray(hi[:d], np.float64), (k, d)) for (lo, hi), k in zip(boxes, cnt)])
     if keep is not None:
         pos = pos[keep(pos)]
-    sd = signed_distance(colliders_of(colliders, d), pos.astype(np.float32).astype(np.float64), d) / h
+    x32 = pos.astype(np.float32).astype(np.float64)
+    sd = signed_distance(colliders_of(colliders, d), x32, d) / h if rim_units is None else rim_units(x32) * RIM
     pos = pos[(sd <= RIM) | (rng.random(len(pos)) < rim_keep)]
     sc = T._finish(pos, h, rng, vel=np.zeros_like(pos), uniform=uniform, vel_scale=0.0)
     ps = sc["particles"]

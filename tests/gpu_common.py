@@ -6,7 +6,10 @@ from wgsparkl_amd import scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
-from helpers import assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, rel_rms, report_margin, run_gpu, run_oracle
+import cdf_truth as CT
+import mesh_truth as MT
+from helpers import (assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, pipeline, rel_rms, report_margin, run_gpu,
+                     run_oracle)
 
 GRID_V_TOL = 1e-5      # relative RMS of grid velocity vs the fp64 oracle (north_star target)
 PART_TOL = 2e-5        # relative RMS of particle x, v, F, C' vs the fp64 oracle
@@ -44,6 +47,39 @@ def check_blocks(data, st):
         got = frozenset(ids[first[b]:first[b] + num[b]].tolist())
         assert got == oracle_sets[tuple(vid[b])]
     assert sorted(ids.tolist()) == list(range(st.n))
+
+
+def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None, rigid=False):
+    """one substep of `data`, checked against the fp64 truth of the collider distance fields; `first`: the uploaded state is
+    the state before it (else it is read back). `rigid`: the scene has mesh colliders, and the truth includes the blocks
+    and the votes of their samples (tests/mesh_truth.py); returns (node truth, end-to-end particle truth, particles) and
+    with `rigid` the mesh_truth.Rigid of the substep as a fourth."""
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    if first:
+        pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
+    else:
+        before = data.read_particles()
+        pos, prev = before.pos, before.cdf_affinity
+    poses = data.read_body_poses()
+    pipeline(d).step(data, 1)
+    data.sync()
+    cells, _, dist, aff, closest = data.read_grid()
+    rg = None
+    if rigid:
+        rg = MT.rigid_of(sc, poses, colliders)
+    assert np.array_equal(cells, CT.active_cells(pos, h, d, rigid=rg)), f"{tag}: the active cells are not those of the positions"
+    if rg is not None:
+        assert not rg.und_blocks, f"{tag}: blocks whose membership depends on an undecided sample: {rg.und_blocks}"
+    nf = CT.NodeField(CT.colliders_of(colliders or sc["colliders"], d, poses), d, h, cells, rigid=rg)
+    CT.check_nodes(f"{tag} nodes", nf, dist, aff, closest, fails)
+    got = data.read_particles()
+    iso = CT.ParticleField(pos, h, cells, dist, aff, prev)
+    CT.check_particle_cdf(f"{tag} isolated", iso, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
+    e2e = CT.from_truth_nodes(pos, h, nf, prev)
+    CT.check_particle_cdf(f"{tag} end to end", e2e, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
+    CT.assert_caps(tag, nf, e2e, part_cap)
+    return (nf, e2e, got, rg) if rigid else (nf, e2e, got)
 
 
 def check_fields(data, st32, st64, tol=PART_TOL):
@@ -127,3 +163,32 @@ def _native_slabs(sc, world, pipe, **kw):
                                   uniform_material=uniform_material_of(ps), **kw))
     return shards, part
 
+
+def _export_cdf(shard):
+    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds: the exchange
+    records carry every quad of the particle and the substep its cdf was computed in"""
+    import ctypes as C
+    import torch
+    from wgsparkl_amd import _ffi
+    D = shard.dim
+    buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
+    torch.cuda.current_stream(buf.device).synchronize()
+    cnt = C.c_uint32(0)
+    _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
+    rec = buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
+    ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
+    q = lambda k: rec[:, 4 * k:4 * k + 4]
+    if D == 3:
+        return ids, q(0)[:, :3].copy(), q(11)[:, 3].copy().view(np.uint32), q(10)[:, 3].copy(), q(10)[:, :3].copy(), stamp
+    return ids, q(0)[:, :2].copy(), q(7)[:, 3].copy().view(np.uint32), q(7)[:, 2].copy(), q(7)[:, :2].copy(), stamp
+
+
+def _export_all(shards, n, d):
+    """the particles of all slabs in the order of their global ids; a cdf whose stamp is not the newest is the default one"""
+    parts = [_export_cdf(s) for s in shards]
+    ids = np.concatenate([p[0] for p in parts]).astype(np.int64)
+    assert np.array_equal(np.sort(ids), np.arange(n)), "every particle exactly once"
+    order = np.argsort(ids)
+    pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
+    live = stamp == stamp.max()
+    return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)

@@ -15,7 +15,7 @@ import pytest
 
 import cdf_truth as CT
 import transfer_truth as T
-from gpu_common import _native_slabs, check_blocks
+from gpu_common import _checked_substep, _export_all, _native_slabs, check_blocks
 from helpers import debug, new_data, pipeline, report_margin, run_oracle
 from wgsparkl_amd import MpmData, _ffi
 from wgsparkl_amd.solver import Collider
@@ -27,31 +27,6 @@ CASES = [(name, d, h) for name in CT.SCENES for d in (2, 3) for h in CT.HS]
 
 def _new(sc):
     return new_data(sc)[1]
-
-
-def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None):
-    """one substep of `data`, checked; `first`: the uploaded state is the state before it (else it is read back)"""
-    ps = sc["particles"]
-    d, h = ps.dim, sc["cell_width"]
-    if first:
-        pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
-    else:
-        before = data.read_particles()
-        pos, prev = before.pos, before.cdf_affinity
-    poses = data.read_body_poses()
-    pipeline(d).step(data, 1)
-    data.sync()
-    cells, _, dist, aff, closest = data.read_grid()
-    assert np.array_equal(cells, CT.active_cells(pos, h, d)), f"{tag}: the active cells are not those of the positions"
-    nf = CT.NodeField(CT.colliders_of(colliders or sc["colliders"], d, poses), d, h, cells)
-    CT.check_nodes(f"{tag} nodes", nf, dist, aff, closest, fails)
-    got = data.read_particles()
-    iso = CT.ParticleField(pos, h, cells, dist, aff, prev)
-    CT.check_particle_cdf(f"{tag} isolated", iso, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
-    e2e = CT.from_truth_nodes(pos, h, nf, prev)
-    CT.check_particle_cdf(f"{tag} end to end", e2e, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
-    CT.assert_caps(tag, nf, e2e, part_cap)
-    return nf, e2e, got
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
@@ -190,35 +165,6 @@ def test_kept_node_cdfs_follow_a_moving_ball_and_a_moved_floor(hip_libs, d):
     _checked_substep(f"moving ball {d}D after the floor moved", sc, data, fails, first=False, colliders=moved)
     assert not fails, "\n".join(fails)
     assert len(entered) >= 2 and len(left) >= 2, (len(entered), len(left))
-
-
-def _export_cdf(shard):
-    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds: the exchange
-    records carry every quad of the particle and the substep its cdf was computed in"""
-    import ctypes as C
-    import torch
-    D = shard.dim
-    buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
-    torch.cuda.current_stream(buf.device).synchronize()
-    cnt = C.c_uint32(0)
-    _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
-    rec = buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
-    ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
-    q = lambda k: rec[:, 4 * k:4 * k + 4]
-    if D == 3:
-        return ids, q(0)[:, :3].copy(), q(11)[:, 3].copy().view(np.uint32), q(10)[:, 3].copy(), q(10)[:, :3].copy(), stamp
-    return ids, q(0)[:, :2].copy(), q(7)[:, 3].copy().view(np.uint32), q(7)[:, 2].copy(), q(7)[:, :2].copy(), stamp
-
-
-def _export_all(shards, n, d):
-    """the particles of all slabs in the order of their global ids; a cdf whose stamp is not the newest is the default one"""
-    parts = [_export_cdf(s) for s in shards]
-    ids = np.concatenate([p[0] for p in parts]).astype(np.int64)
-    assert np.array_equal(np.sort(ids), np.arange(n)), "every particle exactly once"
-    order = np.argsort(ids)
-    pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
-    live = stamp == stamp.max()
-    return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)
 
 
 @pytest.mark.parametrize("d", [2, 3])
