@@ -1,8 +1,11 @@
 """fp64 truth of the CPIC colour distance field of analytic colliders (ball, cuboid, capsule): the node field from closed
 forms of the signed distance, the particle field (g2p_cdf.wgsl:39-250) from a given node field, per-element rounding
-bounds, the sets of elements an fp32 evaluation may decide either way, and the scenes. Shared by tests/test_cdf_truth.py
-(CPU: the truth against the C fp64 oracle, the bounds against the C fp32 oracle, perturbations) and tests/test_gpu_cdf.py
-(the HIP kernels node by node and particle by particle).
+bounds, the sets of elements an fp32 evaluation may decide either way, and the scenes. truth_of builds the Truth (rigid,
+nodes, particles) of any scene: with mesh colliders tests/mesh_truth.py fills their columns of the node field, without one
+`rigid` is None. The comparisons with the C oracle (_oracle_fields, assert_matches_fp64_oracle,
+assert_fp32_oracle_fits_and_caps_hold) are shared by tests/test_cdf_truth.py and tests/test_mesh_truth.py (CPU: the truth
+against the C fp64 oracle, the bounds against the C fp32 oracle, perturbations); tests/test_gpu_cdf.py and
+tests/test_gpu_mesh_cdf.py check the HIP kernels node by node and particle by particle (gpu_common.checked_substep).
 
 Inputs are the values the library receives: fp32 positions, fp32 collider parameters (the scenes round every collider
 parameter to fp32, the 2D rotation is (cos, sin) of the fp32 angle in fp32), h as the Python float (the kernel's fp32 h
@@ -17,11 +20,12 @@ settled against the C fp32 oracle in tests/test_cdf_truth.py, never against the 
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 import transfer_truth as T
-from helpers import report_margin
+from helpers import oracle, report_margin
 from oracle.np_oracle import assoc_cell, block_cells, eval_all
 
 U32 = T.U32
@@ -87,14 +91,10 @@ def colliders_of(colliders, d, poses=None):
     return out
 
 
-def _pow2(h):
-    return math.frexp(h)[0] == 0.5
-
-
 def _is_exact(c, d, h):
     """every operation of the kernel is exact for this collider: an axis-aligned unscaled cuboid whose translation and
     half extents are multiples of h / 64, h a power of two (nodes within 2^15 cells of it)"""
-    if c["shape_type"] != 1 or not _pow2(h) or c["scale"] != 1.0 or not np.array_equal(c["R"], np.eye(d)):
+    if c["shape_type"] != 1 or not T._pow2(h) or c["scale"] != 1.0 or not np.array_equal(c["R"], np.eye(d)):
         return False
     q = np.concatenate([c["trans"], c["shape"][:d]]) * (64.0 / h)
     return bool(np.all(q == np.rint(q)) and np.all(np.abs(q) < 2 ** 21))
@@ -177,7 +177,7 @@ class NodeField:
             near = np.linalg.norm(pt - t, axis=1) + s * extent
             far = np.linalg.norm(pt, axis=1) + np.linalg.norm(t)
             exact = _is_exact(c, d, self.h)
-            b = np.zeros(M) if exact else u * ((C_FAR if not _pow2(self.h) else C_FAR - 2.0) * far + C_NEAR[d] * near)
+            b = np.zeros(M) if exact else u * ((C_FAR if not T._pow2(self.h) else C_FAR - 2.0) * far + C_NEAR[d] * near)
             bv = b * amp                                   # bound of every component of proj - pt
             e = bv + np.where(bv > 0, 2.0 * u * cap, 0.0)  # ... against cap = fl(1.5 fl(h))
             iu = (np.abs(sd * s) <= bv) & (bv > 0)
@@ -299,7 +299,7 @@ class ParticleField:
         # absolute error of a kernel's weights: per axis dt = u (2 |cell| [cell * h and the fp32 h, unless h is a power of two]
         # + C_ABS_T), dw <= |w'(t)| dt + dt^2 (|w''| <= 2); the product of D factors, and the D - 1 roundings of the product
         cell = st.node[:, 0, :]
-        dt = u * ((0.0 if _pow2(h) else 2.0) * np.abs(cell) + C_ABS_T)                 # [n, d]
+        dt = u * ((0.0 if T._pow2(h) else 2.0) * np.abs(cell) + C_ABS_T)                 # [n, d]
         w1 = eval_all(-st.ref / h)                                                       # [n, d, 3]
         shf = T.shifts_of(d)
         dw = np.zeros((n, S))
@@ -467,6 +467,11 @@ def _quat(axis, deg):
     return tuple(float(v) for v in f32(np.append(a * math.sin(t), math.cos(t))))
 
 
+def ident(d):
+    """the identity rotation as a Collider takes it: the angle 0 / the quaternion (0, 0, 0, 1)"""
+    return (0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0)
+
+
 def _rot(d, deg=33.0):
     return (float(np.float32(math.radians(deg))),) if d == 2 else _quat((1.0, 2.0, 3.0), deg)
 
@@ -562,8 +567,8 @@ def aligned(d, h, seed=3, **kw):
     of two)"""
     from wgsparkl_amd.solver import Collider
     rng = np.random.default_rng(seed)
-    rot = (0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0)
-    he = np.array([2.0, 1.0, 2.0]) if _pow2(h) else np.array([2.25, 1.25, 2.25])    # (other h: no node can lie on a face exactly)
+    rot = ident(d)
+    he = np.array([2.0, 1.0, 2.0]) if T._pow2(h) else np.array([2.25, 1.25, 2.25])    # (other h: no node can lie on a face exactly)
     cols = [Collider.cuboid(_v(he * h, d), (0.0,) * d, rotation=rot)]
     return _static(d, h, rng, cols, [(np.full(3, -4.4 * h), np.full(3, 4.4 * h))], _n(d), **kw)
 
@@ -574,7 +579,7 @@ def two_equal(d, h, seed=4, **kw):
     nodes in reach of three colliders"""
     from wgsparkl_amd.solver import Collider
     rng = np.random.default_rng(seed)
-    rot = (0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0)
+    rot = ident(d)
     he = _v(np.array([1.5, 2.0, 1.25]) * h, d)
     cols = [Collider.cuboid(he, _v(np.array([1.75, -1.75, 0.0]) * h, d), rotation=rot),
             Collider.cuboid(he, _v(np.array([6.25, 1.75, 0.0]) * h, d), rotation=rot),
@@ -595,7 +600,7 @@ FAR_BLOCKS_NOT_POW2 = {3: (100, -50, -100), 2: (100, -100)}
 
 
 def far_blocks(d, h):
-    return (FAR_BLOCKS if _pow2(h) else FAR_BLOCKS_NOT_POW2)[d]
+    return (FAR_BLOCKS if T._pow2(h) else FAR_BLOCKS_NOT_POW2)[d]
 
 
 def far(d, h, seed=6, **kw):
@@ -629,14 +634,24 @@ SCENES = dict(ball=ball, capsule=capsule, cuboid=cuboid, aligned=aligned, two_eq
 HS = (0.2, 0.5, 2.0)
 
 
-def truth_of(sc, cells=None, poses=None, prev_aff=None, pos=None, variant=()):
-    """(NodeField, end-to-end ParticleField) of a scene at its uploaded (or given) positions"""
+class Truth(NamedTuple):
+    """what truth_of returns"""
+    rigid: Optional[object]        # the mesh_truth.Rigid of the scene's mesh colliders (None without one)
+    nodes: NodeField
+    particles: ParticleField       # end to end: from `nodes`
+
+
+def truth_of(sc, cells=None, poses=None, prev_aff=None, pos=None, colliders=None, variant=()):
+    """the Truth of a scene at its uploaded (or given) positions, poses and colliders; the nodes are those of the active
+    cells (with mesh colliders: the blocks their samples add included) unless `cells` are given"""
+    from mesh_truth import rigid_of
     ps = sc["particles"]
     d, h = ps.dim, sc["cell_width"]
     pos = ps.pos if pos is None else pos
-    cols = colliders_of(sc["colliders"], d, poses)
-    nf = NodeField(cols, d, h, active_cells(pos, h, d) if cells is None else cells, variant=variant)
-    return nf, from_truth_nodes(pos, h, nf, prev_aff, variant=variant)
+    rg = rigid_of(sc, poses, colliders, variant)
+    cols = colliders_of(colliders or sc["colliders"], d, poses)
+    nf = NodeField(cols, d, h, active_cells(pos, h, d, rigid=rg) if cells is None else cells, rigid=rg, variant=variant)
+    return Truth(rg, nf, from_truth_nodes(pos, h, nf, prev_aff, variant=variant))
 
 
 def assert_caps(tag, nf: NodeField, pf: ParticleField, part_cap=PART_CAP):
@@ -647,3 +662,92 @@ def assert_caps(tag, nf: NodeField, pf: ParticleField, part_cap=PART_CAP):
     assert cn > 0 and cp > 0, f"{tag}: no node / particle near a collider"
     assert un <= NODE_CAP * cn, f"{tag}: {un} of {cn} affinity-carrying nodes are undecided"
     assert up <= part_cap * cp, f"{tag}: {up} of {cp} near-collider particles are undecided"
+
+
+# ------------------------------------------------------------------------------------------------ the C oracle beside the truth
+REL = 1.0e-10
+_CACHE = {}
+
+
+def _prev(sc, seed=11):
+    """previous affinity words: a third of the particles carried collider 0 with a positive sign, a third with a negative one"""
+    rng = np.random.default_rng(seed)
+    return rng.choice(np.array([0, 0x1, 0x10001], np.uint32), sc["particles"].n)
+
+
+class Case(NamedTuple):
+    sc: dict
+    prev: np.ndarray               # the particles' previous affinity words (_prev)
+    truth: Truth
+
+
+def _case(make, d, h):
+    """the Case of the scene builder `make` (an entry of a SCENES table), built once per process"""
+    key = (make, d, h)
+    if key not in _CACHE:
+        sc = make(d, h)
+        prev = _prev(sc)
+        _CACHE[key] = Case(sc, prev, truth_of(sc, prev_aff=prev))
+    return _CACHE[key]
+
+
+def _oracle_fields(sc, dtype, prev):
+    """The distance fields of the C oracle, run pass by pass in the order of orc_step_full: update_rigid_particles,
+    sort_rigid, grid_update_cdf, p2g_cdf, g2p_cdf. Without a mesh collider update_rigid_particles and p2g_cdf do nothing and
+    sort_rigid is sort (oracle/orc.py), which leaves the analytic sequence sort, grid_update_cdf, g2p_cdf."""
+    ps = sc["particles"]
+    st = oracle(ps.dim, dtype).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], 0)
+    st.arr["cdf_affinity"][:] = prev
+    st.update_rigid_particles()
+    st.sort_rigid()
+    assert not st.overflow
+    st.grid_update_cdf()
+    st.p2g_cdf()
+    st.g2p_cdf()
+    cells, _, dist, aff, closest = st.grid_records()
+    return dict(cells=cells, dist=dist, aff=aff, closest=closest, paff=st.arr["cdf_affinity"].copy(),
+                pdist=st.arr["cdf_dist"].copy(), pnormal=st.arr["cdf_normal"].copy())
+
+
+def assert_matches_fp64_oracle(sc, prev, truth: Truth):
+    """the truth's active cells, node field and particle field are the C fp64 oracle's: bits equal outside the undecided sets,
+    distances and normals to REL"""
+    nf, pf = truth.nodes, truth.particles
+    h = sc["cell_width"]
+    o = _oracle_fields(sc, np.float64, prev)
+    assert np.array_equal(o["cells"], nf.cells), "the truth's active cells are not the oracle's"
+    assert not ((o["aff"] ^ nf.aff) & ~nf.und_bits).any(), "decided node bits differ"
+    sure = ~nf.und_dist
+    idc = sure & ~nf.und_tie
+    assert np.array_equal(o["closest"][idc], nf.closest[idc])
+    assert np.all(np.abs(o["dist"][sure] - nf.dist[sure]) <= REL * np.maximum(np.abs(nf.dist[sure]), h)), \
+        float(np.max(np.abs(o["dist"][sure] - nf.dist[sure])))
+    # particle field from the oracle's own nodes (isolated) and end to end
+    iso = ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
+    for tag, p in (("isolated", iso), ("end to end", pf)):
+        dec = ~p.undecided
+        assert np.array_equal(o["paff"][dec], p.aff[dec]), f"{tag}: decided particle affinity words differ"
+        tol = REL * np.maximum(1.0, p.cond)               # (the fp64 solves themselves differ by cond(G) 2^-53)
+        assert np.all(np.abs(o["pdist"] - p.dist)[dec] <= (tol * np.maximum(np.abs(p.dist), h))[dec]), tag
+        big = dec & (p.grad_len > 1e-3)
+        assert np.all(np.linalg.norm(o["pnormal"] - p.normal, axis=1)[big] <= (tol / np.maximum(p.grad_len, 1e-3))[big]), tag
+
+
+def assert_fp32_oracle_fits_and_caps_hold(name, sc, prev, truth: Truth):
+    """the C fp32 oracle lands inside every bound of the truth, the undecided shares meet the caps and no block's membership
+    depends on an undecided sample; `name`: the scene's (the margins of a scene with mesh colliders are named "mesh ...")"""
+    rg, nf, pf = truth.rigid, truth.nodes, truth.particles
+    d, h = sc["particles"].dim, sc["cell_width"]
+    name = f"{'mesh ' if rg is not None else ''}{name} {d}D h={h}"
+    tag = f"{name} fp32 oracle"
+    assert_caps(f"{name} truth", nf, pf)
+    if rg is not None:
+        assert not rg.und_blocks, f"blocks whose membership depends on an undecided sample: {rg.und_blocks}"
+    o = _oracle_fields(sc, np.float32, prev)
+    assert np.array_equal(o["cells"], nf.cells)
+    fails = []
+    check_nodes(tag, nf, o["dist"], o["aff"], o["closest"], fails)
+    iso = ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
+    check_particle_cdf(f"{tag} isolated", iso, o["paff"], o["pdist"], o["pnormal"], fails)
+    check_particle_cdf(f"{tag} end to end", pf, o["paff"], o["pdist"], o["pnormal"], fails)
+    assert not fails, "\n".join(fails)

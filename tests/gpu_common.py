@@ -1,13 +1,16 @@
 """Shared by the -m gpu test files: tolerances, seeded scenes, the oracle comparisons of block sets / particle fields / grid."""
+from typing import NamedTuple
+
 import numpy as np
 import pytest
 
-from wgsparkl_amd import scenes
+from wgsparkl_amd import MpmData, scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
 import cdf_truth as CT
 import mesh_truth as MT
+import transfer_truth as T
 from helpers import (assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, pipeline, rel_rms, report_margin, run_gpu,
                      run_oracle)
 
@@ -49,11 +52,19 @@ def check_blocks(data, st):
     assert sorted(ids.tolist()) == list(range(st.n))
 
 
-def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None, rigid=False):
+class Checked(NamedTuple):
+    """what checked_substep returns"""
+    nodes: CT.NodeField            # the node truth of the substep
+    particles: CT.ParticleField    # the end-to-end particle truth
+    got: object                    # read_particles() after the substep
+    rigid: object                  # the mesh_truth.Rigid of the substep (None without a mesh collider)
+
+
+def checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None):
     """one substep of `data`, checked against the fp64 truth of the collider distance fields; `first`: the uploaded state is
-    the state before it (else it is read back). `rigid`: the scene has mesh colliders, and the truth includes the blocks
-    and the votes of their samples (tests/mesh_truth.py); returns (node truth, end-to-end particle truth, particles) and
-    with `rigid` the mesh_truth.Rigid of the substep as a fourth."""
+    the state before it (else it is read back). Where the scene has mesh colliders the truth includes the blocks and the
+    votes of their samples (tests/mesh_truth.py); without one mesh_truth.rigid_of gives None and every step below is the
+    analytic one."""
     ps = sc["particles"]
     d, h = ps.dim, sc["cell_width"]
     if first:
@@ -65,9 +76,7 @@ def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, collider
     pipeline(d).step(data, 1)
     data.sync()
     cells, _, dist, aff, closest = data.read_grid()
-    rg = None
-    if rigid:
-        rg = MT.rigid_of(sc, poses, colliders)
+    rg = MT.rigid_of(sc, poses, colliders)
     assert np.array_equal(cells, CT.active_cells(pos, h, d, rigid=rg)), f"{tag}: the active cells are not those of the positions"
     if rg is not None:
         assert not rg.und_blocks, f"{tag}: blocks whose membership depends on an undecided sample: {rg.und_blocks}"
@@ -79,7 +88,12 @@ def _checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, collider
     e2e = CT.from_truth_nodes(pos, h, nf, prev)
     CT.check_particle_cdf(f"{tag} end to end", e2e, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
     CT.assert_caps(tag, nf, e2e, part_cap)
-    return (nf, e2e, got, rg) if rigid else (nf, e2e, got)
+    return Checked(nf, e2e, got, rg)
+
+
+def blocks_in_reach(nf, col, d):
+    """the blocks that hold a node at which collider `col` votes"""
+    return set(map(tuple, np.unique(nf.cells[nf.voter[:, col]] // T.bw_of(d), axis=0).tolist()))
 
 
 def check_fields(data, st32, st64, tol=PART_TOL):
@@ -192,3 +206,47 @@ def _export_all(shards, n, d):
     pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
     live = stamp == stamp.max()
     return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)
+
+
+def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):
+    """`nsteps` lockstep substeps of the scene's two slabs (_native_slabs), each with the poses read before it: every particle
+    against the truth of the whole domain (the samples of a mesh collider included; without one mesh_truth.rigid_of gives
+    None), the nodes of each slab's own blocks against the truth restricted to them, and no collider-affine node of a
+    slab's range missing from its grid. Returns, per substep, whether collider 1 votes at a node past the cut."""
+    from wgsparkl_amd.sharded import native_lockstep
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    bw = T.bw_of(d)
+    ranges = [part.block_range(r) for r in range(len(shards))]
+    cut = ranges[1][0]
+    pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
+    crossed = []
+    for k in range(nsteps):
+        poses = shards[0].read_body_poses()
+        native_lockstep(shards[0].pipeline, shards, 1)
+        for s in shards:
+            s.sync()
+        cols = CT.colliders_of(sc["colliders"], d, poses)
+        tag_k = f"{tag} substep {k}"
+        rg = MT.rigid_of(sc, poses)
+        whole = CT.NodeField(cols, d, h, CT.active_cells(pos, h, d, rigid=rg), rigid=rg)
+        if rg is not None:
+            assert not rg.und_blocks
+        e2e = CT.from_truth_nodes(pos, h, whole, prev)
+        npos, aff, dist, normal = _export_all(shards, ps.n, d)
+        CT.check_particle_cdf(f"{tag_k} end to end", e2e, aff, dist, normal, fails)
+        CT.assert_caps(tag_k, whole, e2e)
+        for r, s in enumerate(shards):
+            cells, _, ndist, naff, nclosest = MpmData.read_grid(s)
+            blk = cells[:, 0] // bw
+            own = (blk >= ranges[r][0]) & (blk < ranges[r][1])
+            assert own.any()
+            nf = CT.NodeField(cols, d, h, cells[own], rigid=rg)       # (the samples' own blocks: those of the whole domain)
+            CT.check_nodes(f"{tag_k} slab {r} own nodes", nf, ndist[own], naff[own], nclosest[own], fails)
+            inside = set(map(tuple, cells[own].tolist()))
+            missing = [c for c in whole.cells[(whole.aff != 0) & (whole.cells[:, 0] // bw >= ranges[r][0]) & (whole.cells[:, 0] // bw < ranges[r][1])].tolist()
+                       if tuple(c) not in inside]
+            assert not missing, f"{tag_k} slab {r}: {len(missing)} collider-affine nodes of its range are not in its grid"
+        crossed.append(bool((whole.voter[:, 1] & (whole.cells[:, 0] >= cut * bw)).any()))
+        pos, prev = npos, aff
+    return crossed

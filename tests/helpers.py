@@ -161,7 +161,7 @@ _MARGINS = []
 
 def report_margin(name, value, bound, **extra):
     """Parity margins are REPORTED, not only bounded: every floating-point comparison appends (measured, bound) to
-    $WGS_MARGINS_FILE (JSON lines; tools/gpu_margins.sh collects them into profiles/rNN_parity_margins.json)."""
+    $WGS_MARGINS_FILE when it is set (JSON lines; tools/summarize_margins.py reduces such a file to the worst record per check name)."""
     import json
     import os
     rec = dict(test=os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0], name=name, value=float(value), bound=float(bound), **extra)

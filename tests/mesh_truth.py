@@ -1,8 +1,9 @@
 """fp64 truth of the node distance field of mesh colliders (trimesh, heightfield, polyline): which blocks the surface
 samples add, which (sample, node) pairs vote, what a vote says, and how the votes of a collider combine at a node. It fills
 the per-collider columns that cdf_truth.NodeField merges (the minimum across colliders, the lowest id on ties and the
-particle field are that module's, unchanged). Shared by tests/test_mesh_truth.py (CPU: the truth against the C fp64 oracle,
-the bounds against the C fp32 oracle, perturbations) and tests/test_gpu_mesh_cdf.py (the HIP kernels node by node).
+particle field are that module's, unchanged): cdf_truth.truth_of asks rigid_of here for a scene's Rigid and passes it on.
+Shared by tests/test_mesh_truth.py (CPU: the truth against the C fp64 oracle, the bounds against the C fp32 oracle,
+perturbations) and tests/test_gpu_mesh_cdf.py (the HIP kernels node by node).
 
 Inputs are what the library receives: the fp32 local samples, primitive vertex ids and fp32 local vertices of
 wgsparkl_amd.sampling.build_rigid_particles, the collider records of cdf_truth.colliders_of, h as the Python float.
@@ -83,7 +84,7 @@ def mesh_is_exact(c, local_vtx, d, h):
     for the integers to stay below 2^24: with g the coarsest granule of h / 2^k the coordinates share, edges of at
     most e g and nodes within 3 h of the surface, the largest intermediate of the barycentric numerators is a sum of
     3 products of (2 e^3) by (e + 3 h / g)."""
-    if not CT._pow2(h) or c["scale"] != 1.0 or not np.array_equal(c["R"], np.eye(d)):
+    if not T._pow2(h) or c["scale"] != 1.0 or not np.array_equal(c["R"], np.eye(d)):
         return False
     g = _granule(np.concatenate([np.ravel(local_vtx), c["trans"]]), h)
     if g is None:
@@ -133,7 +134,7 @@ class Rigid:
             self.bv[mv] = 0.0 if (ex or same) else u * (C_POSE[d] * _norm(s * lv[mv]) + _norm(self.vw[mv]))
             self.bx[ms] = 0.0 if same else u * ((0.0 if ex else C_POSE[d]) * _norm(s * lp[ms]) + _norm(self.xs[ms]))
         q = self.xs / self.h
-        bq = self.bx[:, None] / self.h + (0.0 if CT._pow2(self.h) else C_CELL) * u * np.abs(q)
+        bq = self.bx[:, None] / self.h + (0.0 if T._pow2(self.h) else C_CELL) * u * np.abs(q)
         self.cell = (np.rint(q) - 1.0).astype(np.int64)
         if "cell_floor" in variant:
             self.cell = (np.floor(q) - 1.0).astype(np.int64)
@@ -356,7 +357,7 @@ class Rigid:
         akeys = _keys(self.blocks if self.blocks is not None else np.unique(cells // bw, axis=0))
         si, nj, nominal, certain = self._pairs(cells, akeys)
         p = cells[nj] * self.h
-        bp = np.zeros(len(nj)) if CT._pow2(self.h) else C_PT * self.u * _norm(p)
+        bp = np.zeros(len(nj)) if T._pow2(self.h) else C_PT * self.u * _norm(p)
         valid, valid_und, neg, neg_und, dist, b, exact_d = (self._votes3 if d == 3 else self._votes2)(si, p, bp)
         col = self.col[si]
         self.pairs = dict(sample=si, node=nj, nominal=nominal, certain=certain, valid=valid, valid_und=valid_und, neg=neg,
@@ -529,22 +530,7 @@ def rigid_of(sc, poses=None, colliders=None, variant=()):
     return Rigid(rb, CT.colliders_of(cl, d, poses), d, h, variant=variant)
 
 
-def truth_of(sc, poses=None, prev_aff=None, pos=None, colliders=None, variant=()):
-    """(Rigid, NodeField, end-to-end ParticleField) of a scene with mesh colliders"""
-    ps = sc["particles"]
-    d, h = ps.dim, sc["cell_width"]
-    pos = ps.pos if pos is None else pos
-    rg = rigid_of(sc, poses, colliders, variant)
-    cols = CT.colliders_of(colliders or sc["colliders"], d, poses)
-    nf = CT.NodeField(cols, d, h, CT.active_cells(pos, h, d, rigid=rg), rigid=rg, variant=variant)
-    return rg, nf, CT.from_truth_nodes(pos, h, nf, prev_aff, variant=variant)
-
-
 # ------------------------------------------------------------------------------------------------ scenes
-def _ident(d):
-    return (0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0)
-
-
 def _sheet_mesh(d, h, ext=(9.0, 7.0)):
     """3D: two triangles sharing the diagonal of a rectangle in the local xz plane; 2D: six segments that zigzag"""
     from wgsparkl_amd.solver import Collider
@@ -575,12 +561,12 @@ def _aligned_mesh(d, h, at):
     # (a second piece 2.75 h above the first, between node planes: there the cell of a sample depends on how x / h is rounded)
     if d == 3:
         v = np.array([[0, 0, 0], [6, 0, 0], [0, 0, 4], [6, 0, 4], [0, 2.75, 0], [6, 2.75, 0], [0, 2.75, 4], [6, 2.75, 4]], np.float32) * np.float32(h)
-        return Collider.trimesh(v, np.array([[0, 1, 2], [2, 1, 3], [4, 5, 6], [6, 5, 7]], np.uint32), CT._v(np.asarray(at) * h, d), rotation=_ident(d))
+        return Collider.trimesh(v, np.array([[0, 1, 2], [2, 1, 3], [4, 5, 6], [6, 5, 7]], np.uint32), CT._v(np.asarray(at) * h, d), rotation=CT.ident(d))
     # (segments of 2 h, 8 h, 16 h, 8 h, 2 h, 1 h: |ab|^2 a power of two, so that t and the projection are exact as well)
     v = np.array([[x, 0] for x in ALIGNED_X] + [[2, 2.75], [10, 2.75]], np.float32) * np.float32(h)
     n = len(ALIGNED_X)
     idx = np.concatenate([np.stack([np.arange(n - 1), np.arange(1, n)], 1), [[n, n + 1]]]).astype(np.uint32)
-    return Collider.polyline(v, idx, CT._v(np.asarray(at) * h, d), rotation=_ident(d))
+    return Collider.polyline(v, idx, CT._v(np.asarray(at) * h, d), rotation=CT.ident(d))
 
 
 def aligned(d, h, seed=21, **kw):
@@ -667,7 +653,7 @@ def mixed(d, h, seed=24, mesh_first=False, **kw):
     at = np.array([2.0, 4.0, 2.0])
     mesh = _aligned_mesh(d, h, at)
     he = np.array([2.0 if d == 3 else 12.0, 1.0, 2.0])
-    box = Collider.cuboid(CT._v(he * h, d), CT._v((at + np.array([he[0], -1.0, 2.0])) * h, d), rotation=_ident(d))
+    box = Collider.cuboid(CT._v(he * h, d), CT._v((at + np.array([he[0], -1.0, 2.0])) * h, d), rotation=CT.ident(d))
     cols = [mesh, box] if mesh_first else [box, mesh]
     lo, hi = (at - np.array([1.9, 3.3, 1.9])) * h, (at + np.array([7.9 if d == 3 else 38.9, 4.0, 5.9])) * h
     return _static(d, h, rng, cols, [(lo, hi)], 3000 if d == 3 else 1500, **kw)
@@ -702,13 +688,13 @@ def degenerate(d, h, seed=26, **kw):
                       [3.37, y + 1.5, 5.13],                                   # 7: with 2 twice: a repeated vertex
                       [4.3, y + 1.25, 4.1], [4.7, y + 1.25, 4.2], [4.4, y + 1.25, 4.6]], np.float32) * np.float32(h)   # 8-10: smaller than a cell
         idx = np.array([[0, 1, 2], [2, 1, 3], [4, 5, 6], [2, 2, 7], [8, 9, 10]], np.uint32)
-        cols = [Collider.trimesh(v, idx, (0.0,) * 3, rotation=_ident(3))]
+        cols = [Collider.trimesh(v, idx, (0.0,) * 3, rotation=CT.ident(3))]
         lo, hi = np.array([1.0, y - 1.3, 1.0]) * h, np.array([9.5, y + 2.7, 8.5]) * h
     else:
         y = 4.25
         v = np.array([[2, y], [9, y + 0.4], [9, y + 0.4], [16, y], [16.3, y + 0.2], [23, y - 0.1], [3.4, y + 1.3], [19.6, y + 1.2]], np.float32) * np.float32(h)
         idx = np.array([[0, 1], [1, 2], [2, 3], [3, 4], [4, 5], [6, 6], [7, 7]], np.uint32)
-        cols = [Collider.polyline(v, idx, (0.0,) * 2, rotation=_ident(2))]
+        cols = [Collider.polyline(v, idx, (0.0,) * 2, rotation=CT.ident(2))]
         lo, hi = np.array([0.5, y - 2.5]) * h, np.array([24.5, y + 2.8]) * h
     return _static(d, h, rng, cols, [(lo, hi)], 3000 if d == 3 else 1500, near=(2.2, 1.05, 4.0), **kw)
 
@@ -759,10 +745,27 @@ def lonely(d, h, seed=27, **kw):
     return _static(d, h, rng, cols, boxes, 2990 if d == 3 else 1490, **kw)
 
 
+def far_mesh(sc):
+    """the scene plus a small mesh collider more than 4 blocks from every particle: it adds no block and leaves no bit"""
+    from wgsparkl_amd.solver import Collider
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    at = tuple(float(np.float32(v)) for v in ps.pos.max(0) + 7 * T.bw_of(d) * h)
+    if d == 3:
+        v = np.array([[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 1]], np.float32) * np.float32(2 * h)
+        mesh = Collider.trimesh(v, np.array([[0, 1, 2], [2, 1, 3]]), at)
+    else:
+        v = np.array([[0, 0], [1, 0.2], [2, 0]], np.float32) * np.float32(2 * h)
+        mesh = Collider.polyline(v, np.array([[0, 1], [1, 2]]), at)
+    out = dict(sc)
+    out["colliders"] = list(sc["colliders"]) + [mesh]
+    return out
+
+
 SCENES = dict(sheet=sheet, aligned=aligned, solid=solid, heightfield=heightfield, mixed=mixed, mixed_mesh_first=mixed_mesh_first,
               slot15=slot15, degenerate=degenerate, lonely=lonely)
 POW2_ONLY = ("aligned", "mixed", "mixed_mesh_first")
-CASES = [(name, d, h) for name in SCENES for d in (2, 3) for h in CT.HS if CT._pow2(h) or name not in POW2_ONLY]
+CASES = [(name, d, h) for name in SCENES for d in (2, 3) for h in CT.HS if T._pow2(h) or name not in POW2_ONLY]
 
 
 def counts(rg: Rigid, nf):

@@ -12,77 +12,24 @@ import pytest
 
 import cdf_truth as CT
 import transfer_truth as T
-from helpers import oracle, report_margin
+from helpers import report_margin
 
 CASES = [(name, d, h) for name in CT.SCENES for d in (2, 3) for h in CT.HS]
-REL = 1.0e-10
-_CACHE = {}
 
 
-def _prev(sc, seed=11):
-    """previous affinity words: a third of the particles carried collider 0 with a positive sign, a third with a negative one"""
-    rng = np.random.default_rng(seed)
-    return rng.choice(np.array([0, 0x1, 0x10001], np.uint32), sc["particles"].n)
-
-
-def _oracle_fields(sc, dtype, prev):
-    ps = sc["particles"]
-    st = oracle(ps.dim, dtype).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], 0)
-    st.arr["cdf_affinity"][:] = prev
-    st.sort()
-    assert not st.overflow
-    st.grid_update_cdf()
-    st.g2p_cdf()
-    cells, _, dist, aff, closest = st.grid_records()
-    return dict(cells=cells, dist=dist, aff=aff, closest=closest, paff=st.arr["cdf_affinity"].copy(),
-                pdist=st.arr["cdf_dist"].copy(), pnormal=st.arr["cdf_normal"].copy())
-
-
-def _case(name, d, h):
-    key = (name, d, h)
-    if key not in _CACHE:
-        sc = CT.SCENES[name](d, h)
-        prev = _prev(sc)
-        nf, pf = CT.truth_of(sc, prev_aff=prev)
-        _CACHE[key] = (sc, prev, nf, pf)
-    return _CACHE[key]
+def _scene(name, d, h):
+    """the cdf_truth.Case of CT.SCENES[name], from the cache test_mesh_truth.py shares"""
+    return CT._case(CT.SCENES[name], d, h)
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_truth_matches_the_fp64_oracle(oracle_libs, name, d, h):
-    sc, prev, nf, pf = _case(name, d, h)
-    o = _oracle_fields(sc, np.float64, prev)
-    assert np.array_equal(o["cells"], nf.cells), "the truth's active cells are not the oracle's"
-    assert not ((o["aff"] ^ nf.aff) & ~nf.und_bits).any(), "decided node bits differ"
-    sure = ~nf.und_dist
-    idc = sure & ~nf.und_tie
-    assert np.array_equal(o["closest"][idc], nf.closest[idc])
-    assert np.all(np.abs(o["dist"][sure] - nf.dist[sure]) <= REL * np.maximum(np.abs(nf.dist[sure]), h)), \
-        float(np.max(np.abs(o["dist"][sure] - nf.dist[sure])))
-    # particle field from the oracle's own nodes (isolated) and end to end
-    iso = CT.ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
-    for tag, p in (("isolated", iso), ("end to end", pf)):
-        dec = ~p.undecided
-        assert np.array_equal(o["paff"][dec], p.aff[dec]), f"{tag}: decided particle affinity words differ"
-        tol = REL * np.maximum(1.0, p.cond)               # (the fp64 solves themselves differ by cond(G) 2^-53)
-        assert np.all(np.abs(o["pdist"] - p.dist)[dec] <= (tol * np.maximum(np.abs(p.dist), h))[dec]), tag
-        big = dec & (p.grad_len > 1e-3)
-        assert np.all(np.linalg.norm(o["pnormal"] - p.normal, axis=1)[big] <= (tol / np.maximum(p.grad_len, 1e-3))[big]), tag
+    CT.assert_matches_fp64_oracle(*_scene(name, d, h))
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_fp32_oracle_fits_the_bounds_and_the_caps_hold(oracle_libs, name, d, h):
-    sc, prev, nf, pf = _case(name, d, h)
-    tag = f"{name} {d}D h={h} fp32 oracle"
-    CT.assert_caps(f"{name} {d}D h={h} truth", nf, pf)
-    o = _oracle_fields(sc, np.float32, prev)
-    assert np.array_equal(o["cells"], nf.cells)
-    fails = []
-    CT.check_nodes(tag, nf, o["dist"], o["aff"], o["closest"], fails)
-    iso = CT.ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
-    CT.check_particle_cdf(f"{tag} isolated", iso, o["paff"], o["pdist"], o["pnormal"], fails)
-    CT.check_particle_cdf(f"{tag} end to end", pf, o["paff"], o["pdist"], o["pnormal"], fails)
-    assert not fails, "\n".join(fails)
+    CT.assert_fp32_oracle_fits_and_caps_hold(name, *_scene(name, d, h))
 
 
 @pytest.mark.parametrize("d", [2, 3])
@@ -95,11 +42,11 @@ def test_far_node_field_at_the_full_distance_for_h_02(oracle_libs, d):
     report_margin(f"far nodes {d}D h={h}: undecided share of the nodes that carry an affinity", un / cn, CT.NODE_CAP, count=un, of=cn)
     assert un <= CT.NODE_CAP * cn
     prev = np.zeros(sc["particles"].n, np.uint32)
-    o = _oracle_fields(sc, np.float64, prev)
+    o = CT._oracle_fields(sc, np.float64, prev)
     assert np.array_equal(o["cells"], nf.cells) and not ((o["aff"] ^ nf.aff) & ~nf.und_bits).any()
     sure = ~nf.und_dist
-    assert np.all(np.abs(o["dist"][sure] - nf.dist[sure]) <= REL * np.maximum(np.abs(nf.dist[sure]), h))
-    o = _oracle_fields(sc, np.float32, prev)
+    assert np.all(np.abs(o["dist"][sure] - nf.dist[sure]) <= CT.REL * np.maximum(np.abs(nf.dist[sure]), h))
+    o = CT._oracle_fields(sc, np.float32, prev)
     fails = []
     CT.check_nodes(f"far nodes {d}D h={h} fp32 oracle", nf, o["dist"], o["aff"], o["closest"], fails)
     assert not fails, "\n".join(fails)
@@ -108,29 +55,31 @@ def test_far_node_field_at_the_full_distance_for_h_02(oracle_libs, d):
 def test_the_scenes_reach_the_edges_they_are_named_for():
     for d in (2, 3):
         # ball: a node exactly at a centre; the small ball still has voters
-        _, _, nf, _ = _case("ball", d, 0.5)
+        nf = _scene("ball", d, 0.5).truth.nodes
         o = np.nonzero(np.all(nf.cells == 0, axis=1))[0]
         assert len(o) == 1 and nf.sd[o[0], 2] == -float(np.float32(0.15)) and nf.inside[o[0], 2]
         assert nf.voter[:, 1].sum() >= 4
         # cuboid: nodes and particles inside; an extent below h
-        sc, _, nf, pf = _case("cuboid", d, 0.5)
+        truth = _scene("cuboid", d, 0.5).truth
+        nf, pf = truth.nodes, truth.particles
         assert nf.inside[:, 0].sum() >= 4 and ((pf.aff >> 16) != 0).sum() >= 20
         # aligned, power-of-two h: nodes exactly on a face are inside by equality, and decided
-        _, _, nf, _ = _case("aligned", d, 0.5)
+        nf = _scene("aligned", d, 0.5).truth.nodes
         on = nf.sd[:, 0] == 0.0
         assert on.sum() >= 8 and nf.inside[on, 0].all() and not (nf.und_bits[on] != 0).any()
         # two_equal, power-of-two h: exact decided ties, and a node in reach of three colliders
-        _, _, nf, _ = _case("two_equal", d, 2.0)
+        nf = _scene("two_equal", d, 2.0).truth.nodes
         tie = nf.voter[:, 0] & nf.voter[:, 1] & (nf.dist_c[:, 0] == nf.dist_c[:, 1]) & (nf.dist_c[:, 0] == nf.dist)
         assert tie.sum() >= 1 and not nf.und_tie[tie].any() and (nf.closest[tie] == 0).all()
         assert (nf.voter[:, :3].sum(1) == 3).any()
         # sixteen: collider 16 leaves no trace although nodes are in its reach
-        sc, _, nf, pf = _case("sixteen", d, 0.5)
+        case = _scene("sixteen", d, 0.5)
+        sc, nf = case.sc, case.truth.nodes
         assert nf.voter.shape[1] == 16 and nf.voter[:, 15].any()
         c16 = CT.colliders_of(sc["colliders"], d)[16:]
         assert CT.NodeField(c16, d, 0.5, nf.cells).voter[:, 0].any()
         # far: the block coordinates
-        sc, _, nf, _ = _case("far", d, 0.5)
+        sc = _scene("far", d, 0.5).sc
         blk = T.assoc_cell(sc["particles"].pos, 0.5) // T.bw_of(d)
         assert np.all(np.abs(blk.mean(0) - np.array(CT.FAR_BLOCKS[d])) < 3)
         assert np.all(np.abs(np.array(CT.FAR_BLOCKS[d])) >= 1000 // (2 if d == 3 else 1))
@@ -190,8 +139,8 @@ def test_curvature_term_of_round_shapes_is_reported():
     for name in ("ball", "capsule"):
         for d in (2, 3):
             h = 0.5
-            sc, _, _, _ = _case(name, d, h)
-            nf, pf = CT.truth_of(sc)
+            sc = _scene(name, d, h).sc
+            pf = CT.truth_of(sc).particles
             c = CT.colliders_of(sc["colliders"], d)[0]
             x = sc["particles"].pos.astype(np.float64)
             xl = (x - c["trans"]) @ c["R"] / c["scale"]
@@ -216,7 +165,8 @@ PART_VARIANTS = ("no_persistence", "unmirrored", "swap_dist_normal0")
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_perturbations_are_caught(monkeypatch, name, d, h):
     monkeypatch.setattr(T, "report_margin", lambda *a, **k: None)     # (perturbed fields are no measured margins)
-    sc, prev, nf, pf = _case(name, d, h)
+    sc, prev, truth = _scene(name, d, h)
+    nf, pf = truth.nodes, truth.particles
     cols = CT.colliders_of(sc["colliders"], d)
     # control: the unperturbed truth, rounded to fp32 like every perturbed field below, passes the same checks
     fails = []
@@ -224,8 +174,8 @@ def test_perturbations_are_caught(monkeypatch, name, d, h):
     CT.check_particle_cdf("control", pf, pf.aff, pf.dist.astype(np.float32), pf.normal.astype(np.float32), fails)
     assert not fails, "\n".join(fails)
     for v, scenes in NODE_VARIANTS.items():
-        if name not in scenes or (v == "closest_highest" and not CT._pow2(h)) or \
-                (v == "euclid_within" and name == "aligned" and not (d == 3 and CT._pow2(h))):
+        if name not in scenes or (v == "closest_highest" and not T._pow2(h)) or \
+                (v == "euclid_within" and name == "aligned" and not (d == 3 and T._pow2(h))):
             continue
         bad = CT.NodeField(cols, d, h, nf.cells, variant=(v,))
         fails = []
@@ -240,13 +190,14 @@ def test_perturbations_are_caught(monkeypatch, name, d, h):
 
 def test_det_edge_scene_has_decided_particles_on_both_sides(oracle_libs):
     sc = CT.det_edge()
-    nf, pf = CT.truth_of(sc)
+    truth = CT.truth_of(sc)
+    nf, pf = truth.nodes, truth.particles
     CT.assert_caps("det edge truth", nf, pf, part_cap=CT.DET_EDGE_CAP)
     dec = pf.reaches & ~pf.undecided
     below, above = int((dec & ~pf.ok).sum()), int((dec & pf.ok).sum())
     report_margin("det edge: decided particles below / above 1e-8", below, 20, above=above)
     assert below >= 20 and above >= 20
-    o = _oracle_fields(sc, np.float32, np.zeros(sc["particles"].n, np.uint32))
+    o = CT._oracle_fields(sc, np.float32, np.zeros(sc["particles"].n, np.uint32))
     fails = []
     CT.check_nodes("det edge fp32 oracle", nf, o["dist"], o["aff"], o["closest"], fails)
     CT.check_particle_cdf("det edge fp32 oracle end to end", pf, o["paff"], o["pdist"], o["pnormal"], fails)

@@ -14,19 +14,16 @@ import numpy as np
 import pytest
 
 import cdf_truth as CT
+import mesh_truth as MT
 import transfer_truth as T
-from gpu_common import _checked_substep, _export_all, _native_slabs, check_blocks
+from gpu_common import _native_slabs, blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
 from helpers import debug, new_data, pipeline, report_margin, run_oracle
-from wgsparkl_amd import MpmData, _ffi
+from wgsparkl_amd import _ffi
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(name, d, h) for name in CT.SCENES for d in (2, 3) for h in CT.HS]
-
-
-def _new(sc):
-    return new_data(sc)[1]
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
@@ -37,11 +34,11 @@ def test_shapes_and_poses_one_substep(hip_libs, name, d, h):
         # the library refuses a 17th coupled collider outright (the C oracle and the truth ignore it: test_cdf_truth.py);
         # what runs here is all 16 slots in use
         with pytest.raises(_ffi.WgsError):
-            _new(sc)
+            new_data(sc)[1]
         sc["colliders"] = sc["colliders"][:16]
-    data = _new(sc)
+    data = new_data(sc)[1]
     fails = []
-    nf, pf, got = _checked_substep(f"{name} {d}D h={h}", sc, data, fails, first=True)
+    checked_substep(f"{name} {d}D h={h}", sc, data, fails, first=True)
     check_blocks(data, run_oracle(sc, 1, np.float32))
     assert not fails, "\n".join(fails)
 
@@ -51,7 +48,7 @@ def test_far_node_field_at_the_full_distance_for_h_02(hip_libs, d):
     """h = 0.2 at the full distance of the far scene: the node field alone (there the particle caps cannot hold)"""
     h = 0.2
     sc = CT.far_nodes(d, h)
-    data = _new(sc)
+    data = new_data(sc)[1]
     pipeline(d).step(data, 1)
     data.sync()
     cells, _, dist, aff, closest = data.read_grid()
@@ -64,22 +61,6 @@ def test_far_node_field_at_the_full_distance_for_h_02(hip_libs, d):
     assert not fails, "\n".join(fails)
 
 
-def _far_mesh(sc):
-    """the scene plus a small mesh collider more than 4 blocks from every particle"""
-    ps = sc["particles"]
-    d, h = ps.dim, sc["cell_width"]
-    at = tuple(float(np.float32(v)) for v in ps.pos.max(0) + 7 * T.bw_of(d) * h)
-    if d == 3:
-        v = np.array([[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 1]], np.float32) * np.float32(2 * h)
-        mesh = Collider.trimesh(v, np.array([[0, 1, 2], [2, 1, 3]]), at)
-    else:
-        v = np.array([[0, 0], [1, 0.2], [2, 0]], np.float32) * np.float32(2 * h)
-        mesh = Collider.polyline(v, np.array([[0, 1], [1, 2]]), at)
-    out = dict(sc)
-    out["colliders"] = list(sc["colliders"]) + [mesh]
-    return out
-
-
 @pytest.mark.parametrize("d", [2, 3])
 @pytest.mark.parametrize("path", ["summaries", "no_summaries", "k_cdf"])
 def test_each_node_field_path_agrees_with_the_truth(hip_libs, monkeypatch, path, d):
@@ -88,11 +69,11 @@ def test_each_node_field_path_agrees_with_the_truth(hip_libs, monkeypatch, path,
     h = 0.5
     sc = CT.two_equal(d, h)
     if path == "k_cdf":
-        sc = _far_mesh(sc)
+        sc = MT.far_mesh(sc)
     with debug(monkeypatch, "NO_CDF_SUMM") if path == "no_summaries" else contextlib.nullcontext():
-        data = _new(sc)
+        data = new_data(sc)[1]
     fails = []
-    nf, pf, got = _checked_substep(f"node field path {path} {d}D", sc, data, fails, first=True)
+    got = checked_substep(f"node field path {path} {d}D", sc, data, fails, first=True).got
     if path == "k_cdf":
         bit = np.uint32(0x10001 << (len(sc["colliders"]) - 1))
         _, _, _, aff, _ = data.read_grid()
@@ -108,19 +89,15 @@ def test_each_particle_field_path_agrees_with_the_truth(hip_libs, monkeypatch, p
     h = 0.5
     sc = CT.capsule(d, h)
     with debug(monkeypatch, "NO_PCDF_WAVES") if path == "cpic_workgroups" else contextlib.nullcontext():
-        data = _new(sc)
+        data = new_data(sc)[1]
     pipeline(d).step(data, 1)
     data.sync()
     fails = []
-    _checked_substep(f"particle field path {path} {d}D", sc, data, fails, first=False)
+    checked_substep(f"particle field path {path} {d}D", sc, data, fails, first=False)
     n_near = data.stats()["num_near_collider_blocks"]
     report_margin(f"particle field path {path} {d}D: near-collider blocks", n_near, 0)
     assert n_near > 0, "no near-collider block: the prologue-waves path was not reached"
     assert not fails, "\n".join(fails)
-
-
-def _blocks_in_reach(nf, col, d):
-    return set(map(tuple, np.unique(nf.cells[nf.voter[:, col]] // T.bw_of(d), axis=0).tolist()))
 
 
 def _ball_scene(d, h, ball_x=None):
@@ -129,7 +106,7 @@ def _ball_scene(d, h, ball_x=None):
     bw = T.bw_of(d)
     rng = np.random.default_rng(40 + d)
     floor = Collider.cuboid(CT._v(np.array([3.2 * bw, 1.0, 3.0 * bw]) * h, d), CT._v(np.array([3.0 * bw + 0.13, bw - 0.8, 1.5 * bw + 0.21]) * h, d),
-                            rotation=(0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0))
+                            rotation=CT.ident(d))
     # (the ball stays 1.6 h clear of the bed: no node inside it receives mass, so it takes no impulse, and its velocity is
     # not limited to 0.1 h / dt as that of a body in contact is)
     ball = Collider.ball(float(np.float32(1.5 * h)), CT._v(np.array([2 * bw + 1.5 if ball_x is None else ball_x, 2 * bw + 6.13, 1.5 * bw + 0.27]) * h, d),
@@ -146,12 +123,12 @@ def test_kept_node_cdfs_follow_a_moving_ball_and_a_moved_floor(hip_libs, d):
     or leave its reach must be rebuilt. Then the floor moves by 0.37 h (set_colliders): every kept field is stale."""
     h = 0.2
     sc, floor, ball = _ball_scene(d, h)
-    data = _new(sc)
+    data = new_data(sc)[1]
     fails = []
     entered, left, reach = set(), set(), None
     for k in range(12):
-        nf, _, _ = _checked_substep(f"moving ball {d}D substep {k}", sc, data, fails, first=k == 0)
-        now = _blocks_in_reach(nf, 1, d)
+        nf = checked_substep(f"moving ball {d}D substep {k}", sc, data, fails, first=k == 0).nodes
+        now = blocks_in_reach(nf, 1, d)
         if reach is not None:
             entered |= now - reach
             left |= reach - now
@@ -162,7 +139,7 @@ def test_kept_node_cdfs_follow_a_moving_ball_and_a_moved_floor(hip_libs, d):
     moved = [dataclasses.replace(floor, translation=CT._v(np.asarray(floor.translation) + np.array([0.0, 0.37 * h, 0.0])[:d], d)),
              dataclasses.replace(ball, translation=tuple(float(v) for v in poses[1]["translation"]))]
     data.set_colliders(moved)
-    _checked_substep(f"moving ball {d}D after the floor moved", sc, data, fails, first=False, colliders=moved)
+    checked_substep(f"moving ball {d}D after the floor moved", sc, data, fails, first=False, colliders=moved)
     assert not fails, "\n".join(fails)
     assert len(entered) >= 2 and len(left) >= 2, (len(entered), len(left))
 
@@ -172,7 +149,6 @@ def test_lockstep_slabs_of_the_moving_ball_scene(hip_libs, d):
     """The moving-ball scene as two lockstep slabs, 4 substeps: the ball's reach starts 0.7 h short of the cut and crosses
     it. Every particle against the truth of the whole domain; the nodes of each slab's own blocks against the truth
     restricted to them."""
-    from wgsparkl_amd.sharded import native_lockstep
     h = 0.2
     bw = T.bw_of(d)
     sc, _, _ = _ball_scene(d, h)
@@ -185,35 +161,8 @@ def test_lockstep_slabs_of_the_moving_ball_scene(hip_libs, d):
     sc, floor, ball = _ball_scene(d, h, ball_x=cut * bw - 3.7)       # (its reach ends 3 h ahead of its centre)
     assert np.array_equal(sc["particles"].pos, ps.pos)
     shards, part = _native_slabs(sc, 2, pipe)
-    ranges = [part.block_range(r) for r in range(2)]
     fails = []
-    pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
-    crossed = []
-    for k in range(4):
-        poses = shards[0].read_body_poses()
-        native_lockstep(pipe, shards, 1)
-        for s in shards:
-            s.sync()
-        cols = CT.colliders_of(sc["colliders"], d, poses)
-        tag = f"slabs moving ball {d}D substep {k}"
-        whole = CT.NodeField(cols, d, h, CT.active_cells(pos, h, d))
-        e2e = CT.from_truth_nodes(pos, h, whole, prev)
-        npos, aff, dist, normal = _export_all(shards, ps.n, d)
-        CT.check_particle_cdf(f"{tag} end to end", e2e, aff, dist, normal, fails)
-        CT.assert_caps(tag, whole, e2e)
-        for r, s in enumerate(shards):
-            cells, _, ndist, naff, nclosest = MpmData.read_grid(s)
-            blk = cells[:, 0] // bw
-            own = (blk >= ranges[r][0]) & (blk < ranges[r][1])
-            assert own.any()
-            nf = CT.NodeField(cols, d, h, cells[own])
-            CT.check_nodes(f"{tag} slab {r} own nodes", nf, ndist[own], naff[own], nclosest[own], fails)
-            inside = set(map(tuple, cells[own].tolist()))
-            missing = [c for c in whole.cells[(whole.aff != 0) & (whole.cells[:, 0] // bw >= ranges[r][0]) & (whole.cells[:, 0] // bw < ranges[r][1])].tolist()
-                       if tuple(c) not in inside]
-            assert not missing, f"{tag} slab {r}: {len(missing)} collider-affine nodes of its range are not in its grid"
-        crossed.append(bool((whole.voter[:, 1] & (whole.cells[:, 0] >= cut * bw)).any()))
-        pos, prev = npos, aff
+    crossed = check_lockstep_slabs(f"slabs moving ball {d}D", sc, shards, part, 4, fails)
     for s in shards:
         s.close()
     report_margin(f"slabs moving ball {d}D: substeps in which the ball's reach is past the cut", sum(crossed), 1)
@@ -229,17 +178,17 @@ def test_sign_persistence_under_a_thin_plate(hip_libs, d):
     rng = np.random.default_rng(50 + d)
     x0 = np.array([4.13, 6.21, 6.17]) * h
     at = lambda k: Collider.cuboid(CT._v(np.array([0.3, 3.0, 3.0]) * h, d), CT._v(x0 + np.array([0.45 * h * k, 0.0, 0.0]), d),
-                                   rotation=(0.0,) if d == 2 else (0.0, 0.0, 0.0, 1.0))
+                                   rotation=CT.ident(d))
     lo, hi = np.array([3.0, 3.5, 3.5]) * h, np.array([10.0, 9.0, 9.0]) * h
     sc = CT._static(d, h, rng, [at(0)], [(lo, hi)], 3000 if d == 3 else 1500, rim_keep=1.0)
-    data = _new(sc)
+    data = new_data(sc)[1]
     fails = []
     n_kept = 0
     for k in range(8):
         # the host moves the plate (a body in contact that integrates its own velocity is limited to 0.1 h per substep)
         if k:
             data.set_colliders([at(k)])
-        _, pf, _ = _checked_substep(f"thin plate {d}D substep {k}", sc, data, fails, first=k == 0, colliders=[at(k)])
+        pf = checked_substep(f"thin plate {d}D substep {k}", sc, data, fails, first=k == 0, colliders=[at(k)]).particles
         n_kept += int(pf.fresh_sign_differs.sum())
     report_margin(f"thin plate {d}D: decided particles whose sign differs from their fresh vote", n_kept, 10)
     assert not fails, "\n".join(fails)
@@ -249,9 +198,9 @@ def test_sign_persistence_under_a_thin_plate(hip_libs, d):
 def test_det_edge(hip_libs):
     """3D, h = 0.1: decided particles on both sides of det = 1e-8 carry exactly the truth's affinity word (0 below)."""
     sc = CT.det_edge()
-    data = _new(sc)
+    data = new_data(sc)[1]
     fails = []
-    _, pf, got = _checked_substep("det edge", sc, data, fails, first=True, part_cap=CT.DET_EDGE_CAP)
+    pf = checked_substep("det edge", sc, data, fails, first=True, part_cap=CT.DET_EDGE_CAP).particles
     dec = pf.reaches & ~pf.undecided
     below, above = int((dec & ~pf.ok).sum()), int((dec & pf.ok).sum())
     report_margin("det edge: decided particles below / above 1e-8, undecided", below, 20, above=above, undecided=int((pf.reaches & pf.undecided).sum()))

@@ -2,7 +2,7 @@
 truth of tests/mesh_truth.py (its bounds are settled on the CPU by tests/test_mesh_truth.py), through k_rigid_transform,
 k_rigid_mark / k_rigid_touch, k_p2g_cdf, the reset of its accumulators in the sort and the merge in k_cdf.
 
-Every checked substep (gpu_common._checked_substep with rigid=True): the positions, previous affinity words and collider
+Every checked substep (gpu_common.checked_substep): the positions, previous affinity words and collider
 poses are those read before it; after it the active cells are exactly the truth's (the blocks the samples add included, and
 none that depends on an undecided sample), every node's affinity / sign bits and closest id are exact outside the undecided
 sets and its distance is within its bound, nodes with no voter hold exactly (1e10, NONE, 0), every particle is checked from
@@ -16,9 +16,8 @@ import pytest
 import cdf_truth as CT
 import mesh_truth as MT
 import transfer_truth as T
-from gpu_common import _checked_substep, _export_all, _native_slabs, check_blocks
+from gpu_common import _native_slabs, blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
 from helpers import debug, new_data, pipeline, report_margin, run_oracle
-from wgsparkl_amd import MpmData
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
@@ -26,23 +25,15 @@ pytestmark = pytest.mark.gpu
 CASES = MT.CASES
 
 
-def _new(sc):
-    return new_data(sc)[1]
-
-
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_mesh_shapes_one_substep(hip_libs, name, d, h):
     i = CASES.index((name, d, h))
     sc = MT.SCENES[name](d, h, uniform=i % 2 == 1)          # (the two layouts alternate)
-    data = _new(sc)
+    data = new_data(sc)[1]
     fails = []
-    nf, pf, got, rg = _checked_substep(f"mesh {name} {d}D h={h}", sc, data, fails, first=True, rigid=True)
+    checked_substep(f"mesh {name} {d}D h={h}", sc, data, fails, first=True)
     check_blocks(data, run_oracle(sc, 1, np.float32))
     assert not fails, "\n".join(fails)
-
-
-def _blocks_in_reach(nf, col, d):
-    return set(map(tuple, np.unique(nf.cells[nf.voter[:, col]] // T.bw_of(d), axis=0).tolist()))
 
 
 WIDTH = {3: 3.9, 2: 0.15}     # extent of the moving sheet (2D: of each of its two segments) along its path, in h
@@ -72,7 +63,7 @@ def _moving_mesh_scene(d, h, x0=None, plastic=False):
         ii, jj = np.meshgrid(np.arange(7), np.arange(7), indexing="ij")
         hts = (0.5 * np.sin(0.9 * ii) * np.cos(0.7 * jj)).astype(np.float32)
         fixed = Collider.heightfield(hts, tuple(float(np.float32(v * h)) for v in (6.4 * bw, 0.6, 3.0 * bw)),
-                                     CT._v(np.array([3.0 * bw + 0.13, bw - 0.3, 1.5 * bw + 0.21]) * h, d), rotation=(0.0, 0.0, 0.0, 1.0))
+                                     CT._v(np.array([3.0 * bw + 0.13, bw - 0.3, 1.5 * bw + 0.21]) * h, d), rotation=CT.ident(d))
         L = 2.2 * bw
         v = np.array([[0, 0, 0], [W, 0, 0], [0, 0, L], [W, 0, L]], np.float32) * np.float32(h)
         if x0 is None:
@@ -84,12 +75,12 @@ def _moving_mesh_scene(d, h, x0=None, plastic=False):
         x = np.linspace(-0.2 * bw, 6.2 * bw, 9)
         v = np.stack([x, 0.3 * np.sin(0.9 * np.arange(9))], 1).astype(np.float32) * np.float32(h)
         fixed = Collider.polyline(v, np.stack([np.arange(8), np.arange(1, 9)], 1).astype(np.uint32),
-                                  CT._v(np.array([0.13, bw - 0.3]) * h, d), rotation=(0.0,))
+                                  CT._v(np.array([0.13, bw - 0.3]) * h, d), rotation=CT.ident(d))
         gap = bw + 4.0                                    # between the two segments
         v = np.array([[0, 0], [W, 3.3], [gap, 0], [gap + W, 3.3]], np.float32) * np.float32(h)
         if x0 is None:
             x0 = 4 * bw + 0.5 - 0.35 - gap                # (the back of the front segment leaves block 3 after 0.35 h)
-        sheet = Collider.polyline(v, np.array([[0, 1], [2, 3]], np.uint32), CT._v(np.array([x0, y_sheet]) * h, d), rotation=(0.0,),
+        sheet = Collider.polyline(v, np.array([[0, 1], [2, 3]], np.uint32), CT._v(np.array([x0, y_sheet]) * h, d), rotation=CT.ident(d),
                                   linvel=vel, angvel=(float(np.float32(0.002 / T.DT)),))
         boxes = [(np.array([1.0, bw + 0.5]) * h, np.array([2 * bw - 1.2, top]) * h),
                  (np.array([4 * bw + 1.6, bw + 0.5]) * h, np.array([6 * bw - 1.0, top]) * h)]
@@ -122,12 +113,12 @@ def test_node_field_follows_a_moving_mesh(hip_libs, monkeypatch, path, d):
     h = 0.2
     sc, fixed, sheet = _moving_mesh_scene(d, h, plastic=path == "plastic")
     with debug(monkeypatch, path) if path in ("NO_REBIN", "REBIN_LAUNCH") else contextlib.nullcontext():
-        data = _new(sc)
+        data = new_data(sc)[1]
     fails = []
     entered, left, appeared, gone, reach, only = set(), set(), set(), set(), None, None
     for k in range(12):
-        nf, _, _, rg = _checked_substep(f"moving mesh {path} {d}D substep {k}", sc, data, fails, first=k == 0, rigid=True)
-        now, lone = _blocks_in_reach(nf, 1, d), set(map(tuple, rg.sample_only.tolist()))
+        chk = checked_substep(f"moving mesh {path} {d}D substep {k}", sc, data, fails, first=k == 0)
+        now, lone = blocks_in_reach(chk.nodes, 1, d), set(map(tuple, chk.rigid.sample_only.tolist()))
         if reach is not None:
             entered |= now - reach
             left |= reach - now
@@ -141,7 +132,7 @@ def test_node_field_follows_a_moving_mesh(hip_libs, monkeypatch, path, d):
     moved = [dataclasses.replace(_at_pose(fixed, poses[0], d), translation=CT._v(np.asarray(fixed.translation) + np.array([0.0, 0.37 * h, 0.0])[:d], d)),
              _at_pose(sheet, poses[1], d)]
     data.set_colliders(moved)
-    _checked_substep(f"moving mesh {path} {d}D after the fixed mesh moved", sc, data, fails, first=False, colliders=moved, rigid=True)
+    checked_substep(f"moving mesh {path} {d}D after the fixed mesh moved", sc, data, fails, first=False, colliders=moved)
     assert not fails, "\n".join(fails)
     assert min(len(entered), len(left), len(appeared), len(gone)) >= 2, (len(entered), len(left), len(appeared), len(gone))
 
@@ -151,7 +142,6 @@ def test_lockstep_slabs_with_a_mesh_across_the_cut(hip_libs, d):
     """The moving-mesh scene as two lockstep slabs, 4 substeps: the sheet's reach starts short of the cut and crosses it.
     Every particle against the truth of the whole domain; the nodes of each slab's own blocks against the truth restricted
     to them; no collider-affine node of a slab's range is missing."""
-    from wgsparkl_amd.sharded import native_lockstep
     h = 0.2
     bw = T.bw_of(d)
     sc, _, _ = _moving_mesh_scene(d, h)
@@ -169,37 +159,8 @@ def test_lockstep_slabs_with_a_mesh_across_the_cut(hip_libs, d):
     sc, fixed, sheet = _moving_mesh_scene(d, h, x0=x0)
     assert np.array_equal(sc["particles"].pos, ps.pos)
     shards, part = _native_slabs(sc, 2, pipe)
-    ranges = [part.block_range(r) for r in range(2)]
     fails = []
-    pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
-    crossed = []
-    for k in range(4):
-        poses = shards[0].read_body_poses()
-        native_lockstep(pipe, shards, 1)
-        for s in shards:
-            s.sync()
-        cols = CT.colliders_of(sc["colliders"], d, poses)
-        tag = f"slabs moving mesh {d}D substep {k}"
-        rg = MT.rigid_of(sc, poses)
-        whole = CT.NodeField(cols, d, h, CT.active_cells(pos, h, d, rigid=rg), rigid=rg)
-        assert not rg.und_blocks
-        e2e = CT.from_truth_nodes(pos, h, whole, prev)
-        npos, aff, dist, normal = _export_all(shards, ps.n, d)
-        CT.check_particle_cdf(f"{tag} end to end", e2e, aff, dist, normal, fails)
-        CT.assert_caps(tag, whole, e2e)
-        for r, s in enumerate(shards):
-            cells, _, ndist, naff, nclosest = MpmData.read_grid(s)
-            blk = cells[:, 0] // bw
-            own = (blk >= ranges[r][0]) & (blk < ranges[r][1])
-            assert own.any()
-            nf = CT.NodeField(cols, d, h, cells[own], rigid=rg)       # (the samples' own blocks: those of the whole domain)
-            CT.check_nodes(f"{tag} slab {r} own nodes", nf, ndist[own], naff[own], nclosest[own], fails)
-            inside = set(map(tuple, cells[own].tolist()))
-            missing = [c for c in whole.cells[(whole.aff != 0) & (whole.cells[:, 0] // bw >= ranges[r][0]) & (whole.cells[:, 0] // bw < ranges[r][1])].tolist()
-                       if tuple(c) not in inside]
-            assert not missing, f"{tag} slab {r}: {len(missing)} collider-affine nodes of its range are not in its grid"
-        crossed.append(bool((whole.voter[:, 1] & (whole.cells[:, 0] >= cut * bw)).any()))
-        pos, prev = npos, aff
+    crossed = check_lockstep_slabs(f"slabs moving mesh {d}D", sc, shards, part, 4, fails)
     for s in shards:
         s.close()
     report_margin(f"slabs moving mesh {d}D: substeps in which the sheet's reach is past the cut", sum(crossed), 1)

@@ -10,89 +10,35 @@
 - perturbed truths (strict edges, the sign of the closest vote, validity ignored, the true point-to-primitive distance, a
   2^D stencil, the cell by floor, the own-block rule ignored, + neighbours added, the highest id on ties, the pose or the
   scale not applied, end points valid in 2D, the normal reversed) are caught on the scenes that exercise them;
-- without `rigid` a NodeField and active_cells are what they were: a mesh collider leaves no trace."""
+- without `rigid` a NodeField and active_cells are what they were: a mesh collider leaves no trace; with the `rigid` of a
+  mesh out of every particle's reach they are the same again."""
 import numpy as np
 import pytest
 
 import cdf_truth as CT
 import mesh_truth as MT
 import transfer_truth as T
-from helpers import oracle, report_margin
+from helpers import report_margin
 
 CASES = MT.CASES
-REL = 1.0e-10
 MIN_INSTANCES = 20
-_CACHE = {}
 
 
-def _prev(sc, seed=11):
-    """previous affinity words: a third of the particles carried collider 0 with a positive sign, a third with a negative one"""
-    rng = np.random.default_rng(seed)
-    return rng.choice(np.array([0, 0x1, 0x10001], np.uint32), sc["particles"].n)
-
-
-def _oracle_fields(sc, dtype, prev):
-    ps = sc["particles"]
-    st = oracle(ps.dim, dtype).new_state(ps, sc["params"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], 0)
-    st.arr["cdf_affinity"][:] = prev
-    st.update_rigid_particles()
-    st.sort_rigid()
-    assert not st.overflow
-    st.grid_update_cdf()
-    st.p2g_cdf()
-    st.g2p_cdf()
-    cells, _, dist, aff, closest = st.grid_records()
-    return dict(cells=cells, dist=dist, aff=aff, closest=closest, paff=st.arr["cdf_affinity"].copy(),
-                pdist=st.arr["cdf_dist"].copy(), pnormal=st.arr["cdf_normal"].copy())
-
-
-def _case(name, d, h):
-    key = (name, d, h)
-    if key not in _CACHE:
-        sc = MT.SCENES[name](d, h)
-        prev = _prev(sc)
-        rg, nf, pf = MT.truth_of(sc, prev_aff=prev)
-        _CACHE[key] = (sc, prev, rg, nf, pf)
-    return _CACHE[key]
+def _scene(name, d, h):
+    """the cdf_truth.Case of MT.SCENES[name], from the cache test_cdf_truth.py shares"""
+    return CT._case(MT.SCENES[name], d, h)
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_truth_matches_the_fp64_oracle(oracle_libs, name, d, h):
-    sc, prev, rg, nf, pf = _case(name, d, h)
+    sc, prev, truth = _scene(name, d, h)
     assert sc["particles"].n <= (3000 if d == 3 else 1500)
-    o = _oracle_fields(sc, np.float64, prev)
-    assert np.array_equal(o["cells"], nf.cells), "the truth's active cells are not the oracle's"
-    assert not ((o["aff"] ^ nf.aff) & ~nf.und_bits).any(), "decided node bits differ"
-    sure = ~nf.und_dist
-    idc = sure & ~nf.und_tie
-    assert np.array_equal(o["closest"][idc], nf.closest[idc])
-    assert np.all(np.abs(o["dist"][sure] - nf.dist[sure]) <= REL * np.maximum(np.abs(nf.dist[sure]), h)), \
-        float(np.max(np.abs(o["dist"][sure] - nf.dist[sure])))
-    # particle field from the oracle's own nodes (isolated) and end to end
-    iso = CT.ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
-    for tag, p in (("isolated", iso), ("end to end", pf)):
-        dec = ~p.undecided
-        assert np.array_equal(o["paff"][dec], p.aff[dec]), f"{tag}: decided particle affinity words differ"
-        tol = REL * np.maximum(1.0, p.cond)               # (the fp64 solves themselves differ by cond(G) 2^-53)
-        assert np.all(np.abs(o["pdist"] - p.dist)[dec] <= (tol * np.maximum(np.abs(p.dist), h))[dec]), tag
-        big = dec & (p.grad_len > 1e-3)
-        assert np.all(np.linalg.norm(o["pnormal"] - p.normal, axis=1)[big] <= (tol / np.maximum(p.grad_len, 1e-3))[big]), tag
+    CT.assert_matches_fp64_oracle(sc, prev, truth)
 
 
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_fp32_oracle_fits_the_bounds_and_the_caps_hold(oracle_libs, name, d, h):
-    sc, prev, rg, nf, pf = _case(name, d, h)
-    tag = f"mesh {name} {d}D h={h} fp32 oracle"
-    CT.assert_caps(f"mesh {name} {d}D h={h} truth", nf, pf)
-    assert not rg.und_blocks, f"blocks whose membership depends on an undecided sample: {rg.und_blocks}"
-    o = _oracle_fields(sc, np.float32, prev)
-    assert np.array_equal(o["cells"], nf.cells)
-    fails = []
-    CT.check_nodes(tag, nf, o["dist"], o["aff"], o["closest"], fails)
-    iso = CT.ParticleField(sc["particles"].pos, h, o["cells"], o["dist"], o["aff"], prev)
-    CT.check_particle_cdf(f"{tag} isolated", iso, o["paff"], o["pdist"], o["pnormal"], fails)
-    CT.check_particle_cdf(f"{tag} end to end", pf, o["paff"], o["pdist"], o["pnormal"], fails)
-    assert not fails, "\n".join(fails)
+    CT.assert_fp32_oracle_fits_and_caps_hold(name, *_scene(name, d, h))
 
 
 # what every scene must hold MIN_INSTANCES decided instances of (mesh_truth.counts)
@@ -111,7 +57,8 @@ NAMED = {
 
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_the_scenes_reach_the_edges_they_are_named_for(name, d, h):
-    sc, prev, rg, nf, pf = _case(name, d, h)
+    truth = _scene(name, d, h).truth
+    rg, nf = truth.rigid, truth.nodes
     c = MT.counts(rg, nf)
     for k in NAMED[name]:
         report_margin(f"mesh {name} {d}D h={h}: decided instances of {k}", c[k], MIN_INSTANCES)
@@ -149,7 +96,8 @@ MESH_VARIANTS = {
 @pytest.mark.parametrize("name,d,h", CASES)
 def test_perturbations_are_caught(monkeypatch, name, d, h):
     monkeypatch.setattr(T, "report_margin", lambda *a, **k: None)     # (perturbed fields are no measured margins)
-    sc, prev, rg, nf, pf = _case(name, d, h)
+    sc, _, truth = _scene(name, d, h)
+    nf = truth.nodes
     pos = sc["particles"].pos
     cols = CT.colliders_of(sc["colliders"], d)
     # control: the unperturbed truth, rebuilt and rounded to fp32 like every perturbed field below, passes the same checks
@@ -182,3 +130,22 @@ def test_without_rigid_a_mesh_collider_leaves_no_trace(d):
     assert len(cells) == 64 * len(np.unique((blk[:, None, :] + np.unique(T.shifts_of(d) % 2, axis=0)[None, :, :]).reshape(-1, d), axis=0))
     nf = CT.NodeField(cols, d, h, cells)
     assert not nf.aff.any() and not nf.und_bits.any() and (nf.closest == CT.NONE).all() and (nf.dist == CT.NO_VOTER).all()
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_a_mesh_out_of_reach_gives_the_truth_without_rigid(d):
+    """The scene of test_gpu_cdf.py's k_cdf path: a small mesh more than four blocks from every particle. Its Rigid adds no
+    block, every sample is ignored, and the node field is the one built without `rigid`, element for element."""
+    h = 0.5
+    sc = MT.far_mesh(CT.two_equal(d, h))
+    pos = sc["particles"].pos
+    rg = MT.rigid_of(sc)
+    cells = CT.active_cells(pos, h, d)
+    assert np.array_equal(CT.active_cells(pos, h, d, rigid=rg), cells)
+    assert rg.n > 0 and len(rg.sample_only) == 0 and rg.ignored.all() and not rg.und_blocks
+    cols = CT.colliders_of(sc["colliders"], d)
+    bare, full = CT.NodeField(cols, d, h, cells), CT.NodeField(cols, d, h, cells, rigid=rg)
+    for f in ("dist", "aff", "closest", "und_bits", "und_dist", "und_tie", "b_dist"):
+        assert np.array_equal(getattr(bare, f), getattr(full, f)), f
+    both = CT.truth_of(sc)
+    assert both.rigid is not None and np.array_equal(both.nodes.cells, cells) and np.array_equal(both.nodes.aff, bare.aff)
