@@ -216,7 +216,8 @@ const char *wgs_build_info(void);
  * wgs_set_fluid_eos were added without touching a struct, an enum value or a signature — a binding that must run against older
  * libraries of version 7 detects wgs_set_fluid_eos by symbol lookup. Still 7: WGS_MODEL_PER_PARTICLE, wgs_set_particle_models and
  * wgs_read_particle_models were added the same way (new symbols and a macro only; wgs_diagnostics.model may now read 3) — detect
- * wgs_set_particle_models by symbol lookup. */
+ * wgs_set_particle_models by symbol lookup. Still 7: wgs_grid_sample, wgs_sample_grid[_device] and wgs_read_grid_window[_device] were
+ * added the same way (one new struct and four new symbols) — detect wgs_sample_grid by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -543,6 +544,46 @@ typedef struct {
 } wgs_diagnostics;
 wgs_status wgs_read_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *out);
 wgs_status wgs_enqueue_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *device_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Eulerian field output. NEW: the reference has no counterpart (its grid never leaves the device, src/grid/grid.rs; wgs_read_grid above
+ * is this library's own host dump of every node). What draws or couples a fluid is a field: here the grid is sampled at arbitrary
+ * points, or a dense box of its nodes is copied out, on the device, without a dump of every node over PCIe.
+ *
+ * The grid is the one wgs_read_grid reports: the nodes of the blocks active in the last executed substep, velocity after the grid update
+ * and node mass. EVERY OTHER node counts as velocity 0, mass 0: blocks still in the table but not active in that substep, evicted
+ * blocks, blocks outside the packed key range, and everything before the first substep.
+ *
+ * A sample at x uses the step's own stencil: per axis cell = round(x / h) - 1 (src/solver/particle3d.wgsl:41-49, bit for bit),
+ * ref = cell * h - x, the quadratic B-spline weights w of -ref / h (src/grid/kernel.wgsl:60-66), x_i - x = ref + shift * h over the 3^D
+ * nodes cell + shift, inv_d = 4 / h^2. velocity and velocity_gradient are what G2P gives a particle at x (src/solver/g2p.wgsl:150-218)
+ * before the speed cap and before any CPIC projection: colliders play no part in a sample. One thread sums one sample in one fixed
+ * order — the tensor-product order of the step's G2P, x, then y, then z —, so a record depends on its point and the grid only: not on n,
+ * not on the order of the points, not on the launch shape.
+ * A point with a non-finite coordinate, or whose stencil reaches a block outside the packed key range (src/grid/grid.wgsl:88-95), gives
+ * an all-zero record with active_nodes = 0; no input makes a kernel read outside its arrays.
+ *
+ * n == 0 is WGS_OK and writes nothing. Sharded data (wgs_data_create_sharded) -> WGS_ERR_UNSUPPORTED, like wgs_get_device_ptrs.
+ * wgs_sample_grid and wgs_read_grid_window block, like wgs_read_grid; the _device forms take DEVICE pointers, are stream-ordered on the
+ * data's stream and return at once, like wgs_prep_vertex_buffer_device. None of the four writes simulation state: a step that never
+ * calls them launches exactly what it launched before.
+ *
+ * A window: `out` holds dims[0] * ... * dims[DIM-1] nodes of DIM + 1 floats each — velocity, then mass; in 3D one float4 —, node
+ * (i, j[, k]) of the window = world cell lo + (i, j[, k]) at index i + dims[0] * (j + dims[1] * k). The values are the raw node values of
+ * wgs_read_grid, bit for bit; nodes outside the active blocks are +0. Every dims[k] >= 1 and the product of dims below 2^31, else
+ * WGS_ERR_INVALID_ARGUMENT and nothing is written. A window partly or wholly outside the key range is allowed and reads zeros there. */
+typedef struct {
+    float velocity[WGS_DIM];                     /* sum_i w_i v_i */
+    float velocity_gradient[WGS_DIM * WGS_DIM];  /* inv_d * sum_i w_i v_i (x_i - x)^T, column-major like `affine` */
+    float density;                               /* sum_i w_i m_i / h^DIM */
+    uint32_t active_nodes;                       /* stencil nodes that lie in an active block, 0 .. 3^DIM */
+} wgs_grid_sample;                               /* 14 words in 3D, 8 in 2D */
+/* points: n * DIM floats; out: n records. */
+wgs_status wgs_sample_grid(wgs_data *data, const float *points, size_t n, wgs_grid_sample *out);
+wgs_status wgs_sample_grid_device(wgs_data *data, const float *device_points, size_t n, wgs_grid_sample *device_out);
+/* lo: DIM cell coordinates; dims: DIM extents. */
+wgs_status wgs_read_grid_window(wgs_data *data, const int32_t *lo, const uint32_t *dims, float *out);
+wgs_status wgs_read_grid_window_device(wgs_data *data, const int32_t *lo, const uint32_t *dims, float *device_out);
 
 #ifdef __cplusplus
 }

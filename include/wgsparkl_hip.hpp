@@ -180,6 +180,27 @@ class MpmData {
         check(wgs_read_diagnostics(h_, what, &r));
         return r;
     }
+    // Eulerian field output (no reference counterpart): the grid of the last substep sampled at points (n * WGS_DIM floats) and a
+    // dense window of its nodes (WGS_DIM + 1 floats per node, x fastest). The host forms block; the _device forms take DEVICE pointers,
+    // are stream-ordered on the data's stream and return at once.
+    std::vector<wgs_grid_sample> sample_grid(const std::vector<float> &points) {
+        std::vector<wgs_grid_sample> out(points.size() / WGS_DIM);
+        check(wgs_sample_grid(h_, points.data(), out.size(), out.data()));
+        return out;
+    }
+    void sample_grid_device(const float *device_points, size_t n, wgs_grid_sample *device_out) {
+        check(wgs_sample_grid_device(h_, device_points, n, device_out));
+    }
+    std::vector<float> grid_window(const int32_t (&lo)[WGS_DIM], const uint32_t (&dims)[WGS_DIM]) {
+        unsigned long long total = 1;
+        for (int k = 0; k < WGS_DIM; k++) total = total < (1ull << 31) ? total * dims[k] : total;
+        std::vector<float> out(total != 0 && total < (1ull << 31) ? (size_t)total * (WGS_DIM + 1) : 1);   // (a refused call writes nothing)
+        check(wgs_read_grid_window(h_, lo, dims, out.data()));
+        return out;
+    }
+    void grid_window_device(const int32_t (&lo)[WGS_DIM], const uint32_t (&dims)[WGS_DIM], float *device_out) {
+        check(wgs_read_grid_window_device(h_, lo, dims, device_out));
+    }
     size_t num_particles() const { return n_; }
     wgs_data *handle() const { return h_; }
 

@@ -197,6 +197,16 @@ pub struct wgs_diagnostics {
     pub model: u32,
 }
 
+/// One sample of the grid at a point (include/wgsparkl_hip.h "Eulerian field output"): 14 words in 3D, 8 in 2D.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_grid_sample {
+    pub velocity: [f32; DIM],
+    pub velocity_gradient: [f32; DIM * DIM], // column-major like `affine`
+    pub density: f32,
+    pub active_nodes: u32,
+}
+
 #[repr(C)]
 pub struct wgs_comm {
     _private: [u8; 0],
@@ -256,6 +266,12 @@ extern "C" {
     /// reproducible sums, bounds and state digest, reduced on the device; blocking / stream-ordered into DEVICE memory
     pub fn wgs_read_diagnostics(d: *mut wgs_data, what: u32, out: *mut wgs_diagnostics) -> wgs_status;
     pub fn wgs_enqueue_diagnostics(d: *mut wgs_data, what: u32, device_out: *mut wgs_diagnostics) -> wgs_status;
+    /// the grid of the last substep sampled at `n` points (n * DIM floats) / a dense window of its nodes (DIM + 1 floats per node);
+    /// the _device forms take DEVICE pointers, are stream-ordered and return at once. Detect by symbol lookup on older libraries.
+    pub fn wgs_sample_grid(d: *mut wgs_data, points: *const f32, n: usize, out: *mut wgs_grid_sample) -> wgs_status;
+    pub fn wgs_sample_grid_device(d: *mut wgs_data, device_points: *const f32, n: usize, device_out: *mut wgs_grid_sample) -> wgs_status;
+    pub fn wgs_read_grid_window(d: *mut wgs_data, lo: *const i32, dims: *const u32, out: *mut f32) -> wgs_status;
+    pub fn wgs_read_grid_window_device(d: *mut wgs_data, lo: *const i32, dims: *const u32, device_out: *mut f32) -> wgs_status;
     /// test hook: the device scan on caller data (prefix_sum.rs:183-229 vectors)
     pub fn wgs_debug_scan(p: *mut wgs_pipeline, values: *const u32, n: u32, out: *mut u32, total: *mut u32) -> wgs_status;
 

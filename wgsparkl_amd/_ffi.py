@@ -91,9 +91,13 @@ def make_types(D: int):
                     ("cell_changers", C.c_uint64), ("table_rebuilds", C.c_uint64),
                     ("block_ids", u), ("block_ids_free", u), ("table_marks", u), ("table_refreshes", u)]
 
+    class GridSample(C.Structure):
+        _fields_ = [("velocity", f * D), ("velocity_gradient", f * (D * D)), ("density", f), ("active_nodes", u)]
+
     ns = dict(SimParams=SimParams, Elastic=Elastic, DruckerPrager=DruckerPrager, PlasticState=PlasticState,
               Phase=Phase, Cdf=Cdf, Dynamics=Dynamics, Particle=Particle, Pose=Pose, Velocity=Velocity,
-              Collider=Collider, MassProperties=MassProperties, NodeRecord=NodeRecord, BlockRecord=BlockRecord, Stats=Stats)
+              Collider=Collider, MassProperties=MassProperties, NodeRecord=NodeRecord, BlockRecord=BlockRecord, Stats=Stats,
+              GridSample=GridSample)
     return type("Types", (), ns)
 
 
@@ -180,6 +184,11 @@ def prototypes(T):
         # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
         "wgs_read_diagnostics": (st, [vp, u32, P(Diagnostics)]),
         "wgs_enqueue_diagnostics": (st, [vp, u32, vp]),
+        # Eulerian field output (the grid sampled at points, a dense window of its nodes; no reference counterpart)
+        "wgs_sample_grid": (st, [vp, fp, size, P(T.GridSample)]),
+        "wgs_sample_grid_device": (st, [vp, vp, size, vp]),
+        "wgs_read_grid_window": (st, [vp, P(i32), u32p, fp]),
+        "wgs_read_grid_window_device": (st, [vp, P(i32), u32p, vp]),
     }
 
 

@@ -47,3 +47,5 @@ using namespace wgs;
 #include "capi_debug.inc"        // extern "C": diagnostics, test hooks, WGS_ABLATE profile readers
 #include "kernels_fluid.h"       // WGS_MODEL_FLUID: the kernel of the model switch (last: nothing that existed changes its place)
 #include "kernels_models.h"      // per-particle models: the kernels of wgs_set_particle_models / wgs_read_particle_models (behind it, likewise)
+#include "kernels_probe.h"       // Eulerian field output: the sampler and the window scatter (behind them, likewise) ...
+#include "capi_probe.inc"        // ... extern "C": wgs_sample_grid[_device], wgs_read_grid_window[_device]

@@ -163,6 +163,10 @@ struct wgs_data {
     // diagnostics (kernels_diag.h): accumulators and the result on the device (allocated by the first call, freed with `mem`), pinned host copy
     DiagAcc *diag_acc = nullptr;
     wgs_diagnostics *diag_out = nullptr, *diag_host = nullptr;
+    // Eulerian field output (capi_probe.inc): the sampler's scratch word per block id (allocated by the first call, freed with `mem`),
+    // the capacity it was sized for, and the ticket of the last call
+    uint32_t *probe_mark = nullptr;
+    uint32_t probe_mark_cap = 0, probe_ticket = 0;
 
     // ---- allocation: every device buffer above and in `dev` (dev_alloc; wgs_data_destroy releases them all)
     DeviceMemory mem;

@@ -73,6 +73,24 @@ class Diagnostics:
         return float(cfl_target / per_dt) if per_dt > 0 else float(dt)
 
 
+@dataclass
+class GridSamples:
+    """`wgs_grid_sample` records as numpy (include/wgsparkl_hip.h "Eulerian field output"), one row per point."""
+    velocity: np.ndarray            # [n, D]
+    velocity_gradient: np.ndarray   # [n, D, D] (row, col)
+    density: np.ndarray             # [n]
+    active_nodes: np.ndarray        # [n] uint32: stencil nodes that lie in an active block
+    raw: np.ndarray                 # [n, D + D*D + 2] uint32: the records themselves
+
+
+def grid_samples_from_words(words: np.ndarray, dim: int) -> GridSamples:
+    """`words`: [n, D + D*D + 2] uint32, the records as the library wrote them (the gradient is column-major there)."""
+    D = dim
+    fl = words.view(F32)
+    return GridSamples(velocity=fl[:, :D].copy(), velocity_gradient=fl[:, D:D + D * D].reshape(-1, D, D).transpose(0, 2, 1).copy(),
+                       density=fl[:, D + D * D].copy(), active_nodes=words[:, D + D * D + 1].copy(), raw=words)
+
+
 def diagnostics_from_struct(r, dim: int) -> Diagnostics:
     ncomp = dict(momentum=dim, mass_moment=dim, grid_momentum=dim, angular=1 if dim == 2 else 3, grid_angular=1 if dim == 2 else 3)
     sums = {}
@@ -482,6 +500,48 @@ class MpmData(DataHandle):
         order = np.lexsort(vid.T[::-1]) if m else np.zeros(0, np.int64)
         u = raw.view(np.uint32)
         return vid[order], u[:, D][order].copy(), u[:, D + 1][order].copy(), ids[:self.n]
+
+    # -- Eulerian field output: the grid of the last substep at arbitrary points, and a dense window of its nodes
+    def sample_grid(self, points) -> GridSamples:
+        """`wgs_sample_grid`: velocity, velocity gradient, density and the number of active stencil nodes at every row of `points`
+        [n, D], with the step's own stencil on the grid `read_grid` reports. Blocking."""
+        D = self.dim
+        pts = np.ascontiguousarray(points, F32).reshape(-1, D)
+        n = pts.shape[0]
+        words = np.zeros((n, C.sizeof(self.T.GridSample) // 4), np.uint32)
+        _ffi.check(self.lib, self.lib.wgs_sample_grid(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                      words.ctypes.data_as(C.POINTER(self.T.GridSample))))
+        return grid_samples_from_words(words, D)
+
+    def sample_grid_device(self, points_ptr: int, n: int, out_ptr: int):
+        """`wgs_sample_grid_device`: the same on DEVICE memory (`points_ptr`: n * D floats, `out_ptr`: n records of
+        `ctypes.sizeof(T.GridSample)` bytes), stream-ordered on the data's stream. Returns at once."""
+        _ffi.check(self.lib, self.lib.wgs_sample_grid_device(self._h, C.c_void_p(int(points_ptr)), int(n), C.c_void_p(int(out_ptr))))
+
+    def _window_args(self, lo, dims):
+        D = self.dim
+        lo = np.ascontiguousarray(lo, np.int32).reshape(D)
+        dims = np.ascontiguousarray(dims, np.uint32).reshape(D)
+        return lo, dims, lo.ctypes.data_as(C.POINTER(C.c_int32)), dims.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def grid_window(self, lo, dims):
+        """`wgs_read_grid_window`: (velocity[dims..., D], mass[dims...]) of the world cells lo + (i, j[, k]), the x index first; the raw
+        node values of `read_grid`, +0 outside the active blocks. Blocking."""
+        D = self.dim
+        lo, dims, plo, pdims = self._window_args(lo, dims)
+        total = int(np.prod(dims.astype(np.uint64)))
+        ok = bool(np.all(dims >= 1)) and total < 2 ** 31
+        out = np.zeros((total if ok else 1) * (D + 1), F32)    # (a refused call writes nothing)
+        _ffi.check(self.lib, self.lib.wgs_read_grid_window(self._h, plo, pdims, out.ctypes.data_as(C.POINTER(C.c_float))))
+        nodes = out.reshape(tuple(int(x) for x in dims[::-1]) + (D + 1,))          # stored with x fastest
+        nodes = nodes.transpose(tuple(range(D - 1, -1, -1)) + (D,))
+        return nodes[..., :D].copy(), nodes[..., D].copy()
+
+    def grid_window_device(self, lo, dims, out_ptr: int):
+        """`wgs_read_grid_window_device`: the same into DEVICE memory (prod(dims) * (D + 1) floats, x fastest), stream-ordered on the
+        data's stream. Returns at once."""
+        lo, dims, plo, pdims = self._window_args(lo, dims)
+        _ffi.check(self.lib, self.lib.wgs_read_grid_window_device(self._h, plo, pdims, C.c_void_p(int(out_ptr))))
 
     def read_timings(self):
         ms = (C.c_float * _ffi.WGS_NUM_PASSES)()
