@@ -1,7 +1,8 @@
 // capi_io.inc — entry points that write simulation inputs and read state back: sim params, colliders, bodies, rigid
 // (mesh) particles, plastic state; particles, positions, grid, blocks, body poses, the vertex buffer, device pointers,
 // timings and stats. Every reader that needs a staging buffer takes a Scratch and ends in download(); the kernels they
-// launch are in kernels_readback.h / kernels_shard.h.
+// launch are in kernels_readback.h / kernels_shard.h. In front: the host rules several entry points share (fill_sim_params,
+// cdf_live, "this collider moves": colliders_move), create_impl of capi_lifecycle.inc among their users.
 
 namespace {
 __global__ void k_fluid_collapse(Dev d, int side);   // kernels_fluid.h (defined behind every other kernel: capi.hip on placement)
@@ -19,6 +20,46 @@ wgs_status drop_particle_models(wgs_data *d) {
         d->dev.pmodel[s] = nullptr;
     }
     return WGS_OK;
+}
+
+void fill_sim_params(SimParamsDev &sp, const wgs_sim_params *params) {
+    for (int k = 0; k < D; k++) sp.gravity[k] = params->gravity[k];
+    sp.dt = params->dt;
+}
+
+// After a step with zero colliders every particle cdf is default_cdf()
+// (g2p_cdf.wgsl:246-249 runs unconditionally); before any step the input is echoed.
+bool cdf_live(const wgs_data *d) { return d->cpic || d->substeps == 0; }
+
+// "This collider moves", by the two kinds of evidence: a velocity among the first n colliders the host wrote, a mass
+// property of any. Both end in colliders_move.
+uint32_t moving_by_velocity(const wgs_data *d, size_t n) {
+    uint32_t mask = 0u;
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++)
+            if (d->host_colliders[i].linvel[k] != 0.f || d->host_colliders[i].angvel[k] != 0.f) mask |= 1u << i;
+    return mask;
+}
+uint32_t moving_by_mass(const wgs_data *d) {
+    uint32_t mask = 0u;
+    for (size_t i = 0; i < d->dev.n_colliders; i++) {
+        const BodyDev &b = d->host_bodies[i];
+        for (int k = 0; k < 3; k++) if (b.inv_mass[k] != 0.f) mask |= 1u << i;
+        for (int k = 0; k < 9; k++) if (b.inv_inertia_local[k] != 0.f) mask |= 1u << i;
+    }
+    return mask;
+}
+// (both sticky; says whether the set of moving colliders changed. create_impl stops here: new data has no cached node cdfs,
+// and it enables the impulses behind its last launch, under its own error text)
+bool note_moving(wgs_data *d, uint32_t mask) {
+    const uint32_t moving_before = d->moving_mask;
+    d->moving_mask |= mask;
+    d->bodies_move = d->bodies_move || mask != 0u;
+    return d->moving_mask != moving_before;
+}
+wgs_status colliders_move(wgs_data *d, uint32_t mask) {
+    if (note_moving(d, mask)) d->cdf_generation++;   // (what keeps of a block's node cdfs depends on which colliders move)
+    return d->bodies_move ? enable_impulses(d) : WGS_OK;
 }
 }
 
@@ -118,8 +159,7 @@ wgs_status wgs_set_fluid_eos(wgs_data *d, float gamma) {
 
 wgs_status wgs_set_sim_params(wgs_data *d, const wgs_sim_params *params) {
     WGS_TRY(enter(d, params != nullptr));
-    for (int k = 0; k < D; k++) d->host_sp.gravity[k] = params->gravity[k];
-    d->host_sp.dt = params->dt;
+    fill_sim_params(d->host_sp, params);
     // pageable memcpyAsync returns after staging, so host_sp may be reused at once
     HIP_TRY(hipMemcpyAsync(d->sp, &d->host_sp, sizeof(SimParamsDev), hipMemcpyHostToDevice, d->stream));
     return WGS_OK;
@@ -161,44 +201,25 @@ wgs_status wgs_set_collider_poses(wgs_data *d, const wgs_pose *poses, const floa
 wgs_status wgs_set_body_velocities(wgs_data *d, const wgs_velocity *vels, size_t n) {
     WGS_TRY(enter(d, vels || !n));
     if (n > d->dev.n_colliders) return fail(WGS_ERR_INVALID_ARGUMENT, "more velocities than colliders");
-    const uint32_t moving_before = d->moving_mask;
     for (size_t i = 0; i < n; i++) {
         ColliderDev &c = d->host_colliders[i];
         for (int k = 0; k < 3; k++) c.linvel[k] = vels[i].linear[k];
         for (int k = 0; k < 3; k++) c.angvel[k] = vels[i].angular[k];
-        for (int k = 0; k < 3; k++)
-            if (c.linvel[k] != 0.f || c.angvel[k] != 0.f) {
-                d->bodies_move = true;
-                d->moving_mask |= 1u << i;
-            }
     }
-    if (d->moving_mask != moving_before) d->cdf_generation++;   // (what keeps of a block's node cdfs depends on which colliders move)
+    WGS_TRY(colliders_move(d, moving_by_velocity(d, n)));
     static_assert(offsetof(ColliderDev, angvel) - offsetof(ColliderDev, linvel) == 12, "linvel|angvel contiguous");
-    if (d->bodies_move) WGS_TRY(enable_impulses(d));
     return upload_collider_field(d, offsetof(ColliderDev, linvel), sizeof(float) * 6, n);
 }
 
 wgs_status wgs_set_body_mass_properties(wgs_data *d, const wgs_mass_properties *mp, size_t n) {
     WGS_TRY(enter(d, mp || !n));
     if (n > d->dev.n_colliders) return fail(WGS_ERR_INVALID_ARGUMENT, "more mass properties than colliders");
-    bool dynamic = false;
-    const uint32_t moving_before = d->moving_mask;
     for (size_t i = 0; i < n; i++) {
         BodyDev &b = d->host_bodies[i];
         for (int k = 0; k < 3; k++) b.inv_mass[k] = mp[i].inv_mass[k];
         for (int k = 0; k < 9; k++) b.inv_inertia_local[k] = mp[i].inv_inertia_local[k];
     }
-    for (size_t i = 0; i < d->dev.n_colliders; i++) {
-        const BodyDev &b = d->host_bodies[i];
-        bool dyn = false;
-        for (int k = 0; k < 3; k++) dyn = dyn || b.inv_mass[k] != 0.f;
-        for (int k = 0; k < 9; k++) dyn = dyn || b.inv_inertia_local[k] != 0.f;
-        if (dyn) d->moving_mask |= 1u << i;
-        dynamic = dynamic || dyn;
-    }
-    if (d->moving_mask != moving_before) d->cdf_generation++;   // (what keeps of a block's node cdfs depends on which colliders move)
-    d->bodies_move = d->bodies_move || dynamic;
-    if (d->bodies_move) WGS_TRY(enable_impulses(d));
+    WGS_TRY(colliders_move(d, moving_by_mass(d)));
     // inv_mass | inv_inertia_local are the first 12 floats of BodyDev; local_com / world inertia stay device-owned
     static_assert(offsetof(BodyDev, local_com) == sizeof(float) * 12, "BodyDev layout");
     if (n)
@@ -318,11 +339,8 @@ wgs_status wgs_read_particles(wgs_data *d, wgs_particle *out, wgs_plastic_state 
     Scratch<float> ptmp;   // (stays null unless asked for: the kernel then skips it)
     WGS_TRY(tmp.alloc(n));
     if (plastic_out) WGS_TRY(ptmp.alloc((size_t)3 * n));
-    // After a step with zero colliders every particle cdf is default_cdf()
-    // (g2p_cdf.wgsl:246-249 runs unconditionally); before any step the input is echoed.
-    const bool cdf_live = d->cpic || d->substeps == 0;
     hipLaunchKernelGGL(k_export_particles, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side, o, d->plastic,
-                       cdf_live, (uint32_t)d->substeps, d->static_radius, d->static_dp, d->static_phase, d->static_flags,
+                       cdf_live(d), (uint32_t)d->substeps, d->static_radius, d->static_dp, d->static_phase, d->static_flags,
                        reinterpret_cast<float *>(tmp.ptr), ptmp.ptr);
     if (plastic_out) HIP_TRY(hipMemcpyAsync(plastic_out, ptmp.ptr, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, d->stream));
     return download(d, out, tmp.ptr, sizeof(wgs_particle) * (size_t)n);   // (one wait for both copies)
@@ -331,9 +349,8 @@ wgs_status wgs_read_particles(wgs_data *d, wgs_particle *out, wgs_plastic_state 
 wgs_status wgs_prep_vertex_buffer_device(wgs_data *d, uint32_t mode, wgs_instance *device_instances) {
     WGS_TRY(enter(d, device_instances != nullptr));
     if (mode > WGS_RENDER_CDF_SIGNS) return fail(WGS_ERR_INVALID_ARGUMENT, "unknown render mode");
-    const bool cdf_live = d->cpic || d->substeps == 0;
     if (d->dev.n)
-        hipLaunchKernelGGL(k_prep_instances, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side, mode, cdf_live,
+        hipLaunchKernelGGL(k_prep_instances, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side, mode, cdf_live(d),
                            (uint32_t)d->substeps, reinterpret_cast<float *>(device_instances));
     HIP_TRY(hipGetLastError());
     return WGS_OK;
@@ -401,11 +418,7 @@ wgs_status wgs_read_blocks(wgs_data *d, wgs_block_record *out, size_t capacity, 
 wgs_status wgs_shard_export(wgs_data *d, void *device_buf, uint32_t capacity_records, uint32_t *count) {
     WGS_TRY(enter(d, device_buf && count));
     if (!d->dev.sharded) return fail(WGS_ERR_INVALID_ARGUMENT, "not a sharded wgs_data");
-    d->dev.ctr_set = (uint32_t)(d->substeps & 1u);
-    if (d->sub.needs_compact) {
-        hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, d->stream, d->dev);
-        d->sub.needs_compact = false;
-    }
+    catch_up_counters(d);
     hipLaunchKernelGGL(k_clear_headers, dim3(1), dim3(64), 0, d->stream, static_cast<uint32_t *>(device_buf), (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_export_records<D>, dim3(grid_for(d, 4)), dim3(256), 0, d->stream, d->dev, d->side, static_cast<float *>(device_buf), capacity_records);
     WGS_TRY(download(d, count, device_buf, sizeof(uint32_t)));

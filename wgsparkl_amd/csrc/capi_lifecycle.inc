@@ -235,8 +235,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
     WGS_TRY(h2d(d->static_phase, s_phase.data(), s_phase.size() * sizeof(float)));
     WGS_TRY(h2d(d->static_flags, s_flags.data(), s_flags.size() * sizeof(uint32_t)));
     d->host_sp = SimParamsDev{};
-    for (int k = 0; k < D; k++) d->host_sp.gravity[k] = params->gravity[k];
-    d->host_sp.dt = params->dt;
+    fill_sim_params(d->host_sp, params);
     WGS_TRY(h2d(d->sp, &d->host_sp, sizeof(SimParamsDev)));
     if (sharded) {
         // counts live on the device; the host-side n / nv become the launch bound (allocated capacity)
@@ -251,13 +250,7 @@ static wgs_status create_impl(wgs_pipeline *pipeline, const wgs_sim_params *para
     for (size_t i = 0; i < num_colliders; i++) fill_collider(d->host_colliders[i], colliders[i]);
     WGS_TRY(h2d(d->colliders, d->host_colliders.data(), sizeof(ColliderDev) * WGS_MAX_COLLIDERS));
     d->host_bodies.assign(WGS_MAX_COLLIDERS, BodyDev{});
-    d->bodies_move = false;
-    for (size_t i = 0; i < num_colliders; i++)
-        for (int k = 0; k < 3; k++)
-            if (colliders[i].velocity.linear[k] != 0.f || colliders[i].velocity.angular[k] != 0.f) {
-                d->bodies_move = true;
-                d->moving_mask |= 1u << i;
-            }
+    note_moving(d, moving_by_velocity(d, num_colliders));
     if (num_colliders)  // local centres of mass from the world ones (update_world_mass_properties' inverse)
         hipLaunchKernelGGL(k_bodies_refresh<D>, dim3(1), dim3(16), 0, d->stream, dev, 0xffffu);
     if (d->bodies_move && enable_impulses(d) != WGS_OK) return fail(WGS_ERR_HIP, "out of device memory for the impulse accumulators");
@@ -334,23 +327,19 @@ wgs_status wgs_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_substeps, 
     }
     WGS_TRY(maintain_grid(d));
     auto flush_bodies = [&]() {   // the last substep's integrate_bodies: every other entry point finds the bodies integrated
-        if (d->sub.bodies_pending) {
-            hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, d->stream, d->dev);
-            d->sub.bodies_pending = false;
-        }
+        if (d->sub.bodies_pending) launch_bodies_integrate(d);
+        d->sub.bodies_pending = false;
     };
     for (uint32_t i = 0; i < num_substeps; i++) {
         wgs_status st = WGS_OK;
         if (i > 0 && i % 64u == 0u) {  // long calls: keep an eye on the table inside the call too (bounded run-ahead)
             if ((st = watch_counters(d)) == WGS_OK) st = maintain_grid(d);
         }
+        // (a whole substep: the four stages of host_substep.inc; the first substeps of a timestamped call record their marks)
         if (st == WGS_OK) {
-            if (timestamps && d->timing.events.used < Events::MAX_SUBSTEPS) {
-                st = enqueue_substep<true>(d, d->timing.events.used, 0);
-                d->timing.events.used++;
-            } else {
-                st = enqueue_substep<false>(d, 0, 0);
-            }
+            const int ts_slot = timestamps && d->timing.events.used < Events::MAX_SUBSTEPS ? d->timing.events.used++ : -1;
+            if ((st = begin_substep(d, false, ts_slot)) == WGS_OK && (st = enqueue_sort<D>(d)) == WGS_OK && (st = enqueue_p2g<D>(d, P2gLayers::all)) == WGS_OK)
+                st = enqueue_finish<D>(d);
         }
         if (st != WGS_OK) {   // (the substeps enqueued so far stand: a pose read-back after a failed call sees their bodies integrated)
             flush_bodies();

@@ -1,5 +1,5 @@
 // host_grid.inc — the arrays sized by the block capacity and the host's care for them: alloc_grid (the ONE list of those
-// arrays), enable_impulses, grow_grid, and the host's looks at the device counters that decide about growth and table
+// arrays), enable_impulses, clear_table, grow_grid, and the host's looks at the device counters that decide about growth and table
 // rebuilds (maintain_grid on the pinned watch, fetch_counters at a synchronisation), with sticky_status and resolve_timings
 // as the other two things a synchronising caller asks for. Host code only: nothing here launches a kernel.
 
@@ -76,6 +76,17 @@ wgs_status enable_impulses(wgs_data *d) {
     return st;
 }
 
+// Every slot of the table of block ids empty, on the data's stream; `ids_too`: and the ids handed out anew (reset_hmap, device_math.h).
+wgs_status clear_table(wgs_data *d, bool ids_too) {
+    const Dev &dev = d->dev;
+    HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), d->stream));
+    HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), d->stream));
+    if (!ids_too) return WGS_OK;
+    HIP_TRY(hipMemsetAsync(dev.counters + CTR_NPHYS, 0, sizeof(uint32_t), d->stream));
+    HIP_TRY(hipMemsetAsync(dev.counters + CTR_NFREE, 0, 3 * sizeof(uint32_t), d->stream));   // (free list, insertion count, marks: layout.h)
+    return WGS_OK;
+}
+
 // SURVEY 8f4, second half — the reference's resize loop is a stub (src/grid/grid.rs:43-45,116-117: "TODO: resize the
 // hashmap and retry"). Here the block capacity doubles BEFORE the table fills: a new zeroed set of grid arrays replaces
 // the old one and the next substep rebuilds the table from the particles (the same full pass a table rebuild runs).
@@ -98,10 +109,7 @@ wgs_status grow_grid(wgs_data *d, uint32_t new_cap) {
         return WGS_OK;
     }
     d->mem.release_group(MemGroup::old_grid);
-    HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), d->stream));
-    HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), d->stream));
-    HIP_TRY(hipMemsetAsync(dev.counters + CTR_NPHYS, 0, sizeof(uint32_t), d->stream));
-    HIP_TRY(hipMemsetAsync(dev.counters + CTR_NFREE, 0, 3 * sizeof(uint32_t), d->stream));   // (free list, insertion count, marks)
+    WGS_TRY(clear_table(d, true));
     d->sub.prev_sorted = false;      // block ids start over: the next substep bins every particle through the hash map
     d->sub.prebinned = false;        // (what the last G2P binned went with the old arrays)
     d->cdf_generation++;

@@ -1,5 +1,6 @@
 // host_sharded.inc — the multi-GPU substep behind the entry points of capi_sharded.inc: the run-time binding of RCCL, the two
-// phases of a sharded substep around its one exchange, and the two transports of that exchange.
+// phases of a sharded substep around its one exchange (each a run of the stages of host_substep.inc), and the two transports
+// of that exchange.
 //
 // NEW DESIGN: the reference is single-GPU (one wgpu::Device, src/pipeline.rs:176-193). A caller that replays the
 // reference contract — one call per frame, src_testbed/step.rs:122-128 — gets the x-slab decomposition of
@@ -104,25 +105,22 @@ wgs_status allreduce_impulses(wgs_data *d) {
 // the only slabs the outgoing messages are gathered from — with the pack waves behind it, then P2G of every other block with
 // the interior's grid update behind it. Same kernels, same sums in the same order as the unsplit form: bit-identical (tested).
 wgs_status shard_phase_begin_split(wgs_data *d) {
-    d->sub.in_sharded_step = true;
-    wgs_status st = enqueue_substep<false>(d, 0, 1, 1);                    // the sort
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 2);            // boundary layers + pack waves
-    if (st == WGS_OK) st = enqueue_substep<false>(d, 0, 1, 3);            // everything else + the interior's grid update
-    d->sub.in_sharded_step = false;
-    return st;
+    WGS_TRY(begin_substep(d, true));
+    WGS_TRY(enqueue_sort<D>(d));
+    WGS_TRY(enqueue_p2g<D>(d, P2gLayers::boundary));   // + pack waves
+    return enqueue_p2g<D>(d, P2gLayers::others);       // + the interior's grid update
 }
 
 // phase A: sort .. P2G, then the interface node sums and the guests packed into the outgoing messages
 wgs_status shard_phase_begin(wgs_pipeline *p, wgs_data *d) {
     if ((d->dev.dbg & DBG_SHARD_SPLIT_LAYERS) && d->link && (d->link->has_lower || d->link->has_upper) && !(d->dev.dbg & DBG_GU_OWN_LAUNCH))
         return shard_phase_begin_split(d);
-    d->sub.in_sharded_step = true;
-    wgs_status st = enqueue_substep<false>(d, 0, 1);
-    d->sub.in_sharded_step = false;
-    if (st != WGS_OK) return st;
+    WGS_TRY(begin_substep(d, true));
+    WGS_TRY(enqueue_sort<D>(d));
+    WGS_TRY(enqueue_p2g<D>(d, P2gLayers::all));
     ShardLink &L = *d->link;
     if (!L.has_lower && !L.has_upper) return WGS_OK;
-    if (d->sub.shard_fused) return WGS_OK;   // the pack waves rode in the P2G launch (host_substep.inc plan_p2g)
+    if (d->sub.shard_fused) return WGS_OK;   // the pack waves rode in the P2G launch (host_substep.inc begin_substep, plan_p2g)
     const PackWaves pw = pack_waves(d);   // (workgroups of one wave)
     hipLaunchKernelGGL(k_pack_face<D>, dim3(pw.blocks + pw.guests), dim3(64), 0, d->stream, d->dev, d->side, (uint32_t)(d->substeps + 1), pw.blocks);
     HIP_TRY(hipGetLastError());
@@ -131,12 +129,7 @@ wgs_status shard_phase_begin(wgs_pipeline *p, wgs_data *d) {
 
 // phase B: grid update (which adds the neighbours' partial sums from the inbound messages) + fused G2P + the arrivals' G2P
 // (bodies deferred when the caller reduces the impulses itself)
-wgs_status shard_phase_end(wgs_pipeline *p, wgs_data *d) {
-    d->sub.in_sharded_step = true;
-    const wgs_status st = enqueue_substep<false>(d, 0, 2);
-    d->sub.in_sharded_step = false;
-    return st;
-}
+wgs_status shard_phase_end(wgs_pipeline *p, wgs_data *d) { return enqueue_finish<D>(d); }
 
 // one grouped send + receive per neighbour on the data's stream (the two neighbours are distinct peers: each message
 // rides its own xGMI link; a rank that is its own neighbour — the one-GPU proxy — matches its sends in order)

@@ -190,15 +190,24 @@ struct wgs_data {
         bool force_refresh = false;    // the marks of evicted blocks crowd the table: the next substep re-inserts the live blocks into a cleared table (k_table_refresh)
     } seen;
 
-    // ---- the substep being enqueued, and what the last one left behind: written by enqueue_substep and its plans
+    // ---- the substep being enqueued, and what the last one left behind (host_substep.inc)
     struct Substep {
+        // what the last substep left behind: written by enqueue_finish (and grow_grid), consumed by the next substep
         bool prev_sorted = false;   // the current buffer is the sorted output of the previous substep (perm_cell, links valid)
         bool needs_compact = false; // sharded: the last substep ran without its neighbours (wgs_step): the counters of its buffer are still to be set
-        bool in_sharded_step = false;  // the substep being enqueued belongs to wgs_sharded_step[_lockstep]: guests are dropped, arrivals advanced
         bool prebinned = false;     // the last fused G2P binned its output for the coming substep (Dev::bin_next): no k_rebin launch then
         bool bodies_pending = false;   // integrate_bodies of the last substep has not run yet (it rides in the next sort launch)
-        bool gu_fused = false;      // this substep's grid update rode in its P2G launch
-        bool shard_fused = false;   // sharded substep: the pack waves and the interior blocks' grid update rode in the P2G launch
+        // the substep being enqueued: decided ONCE by begin_substep, read by the stages behind it
+        bool in_sharded_step = false;  // it belongs to wgs_sharded_step[_lockstep]: guests are dropped, the grid update adds the neighbours' sums
+        int ts_slot = -1;           // the row of timing events its marks are recorded in (a timestamped wgs_step), -1: none
+        uint32_t epoch = 0;
+        bool rehash = false;        // it rebuilds the table of block ids
+        bool use_rebin = false;     // its sort bins the particles relative to their old block (k_rebin, or the last G2P did: `binned`)
+        bool binned = false;
+        bool fused_cdf = false;     // node cdfs and block classes ride in launch 2 of its sort
+        bool gu_fused = false;      // its grid update rides in its P2G launch
+        bool shard_fused = false;   // sharded substep: the pack waves and the interior blocks' grid update ride in its P2G launch
+        bool arrivals = false;      // sharded substep: the particles that arrive with its messages are advanced (k_g2p_arrivals)
     } sub;
 
     // ---- statistics (wgs_stats): only ever counted up

@@ -1,11 +1,13 @@
 // host_substep.inc — one substep on the data's stream: the tunables of the launch shapes, the launch ladders (which
-// instantiation a decided shape means), the launch plans (which shape a substep takes: plan_p2g, plan_g2p) and
-// enqueue_substep, which strings them together. Everything that decides WHAT is launched lives here; entry points only
-// call enqueue_substep / enqueue_bodies.
+// instantiation a decided shape means), the launch plans (which shape a substep takes: plan_sort, plan_p2g, plan_g2p) and
+// the stages that string them together: begin_substep decides, once, everything the substep's launches share; enqueue_sort,
+// enqueue_p2g and enqueue_finish launch. Everything that decides WHAT is launched lives here; entry points only run the
+// stages (wgs_step all four, the phases of host_sharded.inc begin + sort + P2G | finish) or call enqueue_bodies.
 
 namespace {
 
 wgs_status allreduce_impulses(wgs_data *d);  // host_sharded.inc
+void launch_bodies_integrate(wgs_data *d);   // behind the stages
 
 #ifndef WGS_PCDF_WAVES_MAX_VISITS
 #define WGS_PCDF_WAVES_MAX_VISITS 256
@@ -26,9 +28,9 @@ constexpr uint32_t P2G_SMALL_BUDGET_MIN_PARTICLES = 600000;  // one-way CPIC P2G
 #endif
 constexpr uint32_t P2G_PAIR_MIN_BLOCKS = 8;  // near-collider blocks from which P2G runs both bodies in one launch
 
-// ---- launch ladders of enqueue_substep: each takes the shape enqueue_substep decided and lists exactly the instantiations
-// that exist. (Templates on the dimension: they are instantiated where enqueue_substep reaches them, which keeps the kernels
-// in the code object in the order of their first use — placement alone moves a kernel by a few percent, DESIGN 9.7.)
+// ---- launch ladders of the stages: each takes the shape a plan decided and lists exactly the instantiations that exist.
+// (Templates on the dimension, like the stages themselves: they are instantiated where wgs_step reaches them, which keeps the
+// kernels in the code object in the order of their first use — placement alone moves a kernel by a few percent, DESIGN 9.7.)
 
 // pack waves of a slab with neighbours: one per interface block as the host last saw the grid (a face holds a fraction of the
 // active blocks), plus a few for the guests
@@ -172,60 +174,99 @@ void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, c
     else launch_g2p_shape<DIM, MODEL, PL, 1>(dev, s, side, epoch, p, mark);
 }
 
+// The G2P variant of the data, in the order of the ladders below (which is the order of their kernels in the code object).
+// (the fluid exists without plastic state only — wgs_set_constitutive_model refuses it on such data — and comes last: the
+// instantiations of the other models keep their places in the code object)
+// (a table of per-particle models — Dev::pmodel, likewise without plastic state and on single-domain data only — behind the fluid)
+enum class G2pVariant { corotated, corotated_plastic, neo_hookean, neo_hookean_plastic, fluid, per_particle };
+G2pVariant g2p_variant(const Dev &dev, bool plastic) {
+    if (dev.pmodel[0]) return G2pVariant::per_particle;
+    if (dev.model == WGS_MODEL_FLUID) return G2pVariant::fluid;
+    if (dev.model == WGS_MODEL_NEO_HOOKEAN) return plastic ? G2pVariant::neo_hookean_plastic : G2pVariant::neo_hookean;
+    return plastic ? G2pVariant::corotated_plastic : G2pVariant::corotated;
+}
+
 // the fused G2P; `mark(6)` between the two launches of that shape
 template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
-    // (the fluid exists without plastic state only — wgs_set_constitutive_model refuses it on such data — and comes last: the
-    // instantiations of the other models keep their places in the code object)
-    // (a table of per-particle models — Dev::pmodel, likewise without plastic state and on single-domain data only — behind the fluid)
-    switch (dev.pmodel[0] ? 5 : dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
-        case 0: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
-        case 1: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
-        case 2: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
-        case 3: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
-        case 4: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
-        default: launch_g2p_model<DIM, 3, false>(dev, s, side, epoch, p, mark); break;
+    switch (g2p_variant(dev, plastic)) {
+        case G2pVariant::corotated: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::corotated_plastic: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::neo_hookean: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::neo_hookean_plastic: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::fluid: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::per_particle: launch_g2p_model<DIM, 3, false>(dev, s, side, epoch, p, mark); break;
     }
 }
 
+// (a slab has no per-particle models — wgs_set_particle_models refuses it —: no arrivals' kernel of that variant)
 template <int DIM> void launch_arrivals(const Dev &dev, hipStream_t s, dim3 g, int side, uint32_t epoch, bool plastic) {
-    switch (dev.model == WGS_MODEL_FLUID ? 4 : ((dev.model == WGS_MODEL_NEO_HOOKEAN ? 2 : 0) | (plastic ? 1 : 0))) {
-        case 0: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, false>), g, dim3(256), 0, s, dev, side, epoch); break;
-        case 1: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, true>), g, dim3(256), 0, s, dev, side, epoch); break;
-        case 2: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, false>), g, dim3(256), 0, s, dev, side, epoch); break;
-        case 3: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+    switch (g2p_variant(dev, plastic)) {
+        case G2pVariant::corotated: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case G2pVariant::corotated_plastic: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 0, true>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case G2pVariant::neo_hookean: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, false>), g, dim3(256), 0, s, dev, side, epoch); break;
+        case G2pVariant::neo_hookean_plastic: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 1, true>), g, dim3(256), 0, s, dev, side, epoch); break;
         default: hipLaunchKernelGGL((k_g2p_arrivals<DIM, 2, false>), g, dim3(256), 0, s, dev, side, epoch); break;
     }
 }
 
-// The shape of this substep's P2G (`part`, `p2g_sel`: enqueue_substep). Sets what the grid update that follows needs to know.
-P2gLaunch plan_p2g(wgs_data *d, int part, int p2g_sel) {
+// ---- the launch plans: which shape a substep's launches take (what begin_substep decided is in d->sub and d->dev)
+
+enum class SortBin { full, rebin, by_last_g2p };   // launch 1: k_bin | k_rebin | it ran inside the previous substep's fused G2P
+struct SortLaunch {
+    bool refresh, reset_table;   // k_table_refresh in front of the sort | reset_hmap, amortised (device_math.h)
+    SortBin bin;
+    uint32_t do_bodies;          // a pending integrate_bodies of the previous substep rides in workgroup 0 of launch 1
+    uint32_t nscan, nreg;        // launch 2: scan and regroup workgroups; have_old, cdf, summ: launch_regroup
+    int have_old;
+    bool cdf, summ;
+    uint32_t refresh_wgs, mesh_wgs, p2g_cdf_wgs;   // k_table_refresh; k_rigid_transform / _mark / _touch; k_p2g_cdf
+};
+SortLaunch plan_sort(const wgs_data *d) {
+    const Dev &dev = d->dev;
+    SortLaunch p{};
+    // the marks of evicted blocks crowd the table (the host's last look): clear it and insert the live blocks again under
+    // their own ids — no particle is touched, the steady-state sort goes on (kernels_sort.h k_table_refresh)
+    p.refresh = d->seen.force_refresh && !d->sub.rehash && dev.free_ids != nullptr;
+    p.refresh_wgs = std::max(1u, std::min((dev.cap + 255u) / 256u, (uint32_t)grid_for(d, 4)));
+    p.reset_table = d->sub.rehash;
+    // (sharded runs: k_rebin also bins the particles that arrived in the last substep, behind the residents)
+    p.bin = d->sub.binned ? SortBin::by_last_g2p : d->sub.use_rebin ? SortBin::rebin : SortBin::full;
+    p.do_bodies = d->sub.bodies_pending ? 1u : 0u;
+    p.mesh_wgs = (uint32_t)grid_for(d, 1);
+    p.nscan = (dev.cap + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    // one resident round: 4 workgroups per CU (127 VGPRs, 36 KB of LDS), the scan workgroups among them
+    p.nreg = std::max(1u, std::min((dev.cap + 3u) / 4u, WGS_REGROUP_ROUNDS * ((uint32_t)grid_for(d, 4) - std::min(p.nscan, (uint32_t)grid_for(d, 2)))));
+    p.have_old = d->sub.use_rebin ? 1 : 0;
+    p.cdf = d->sub.fused_cdf;
+    // (summ: every block within reach of a collider is evaluated substep after substep — each evaluates its own nodes and
+    // tells its neighbours, kernels_sort.h block_cdf_summ; with colliders at rest: the instantiation without)
+    p.summ = (dev.cdf_moving != 0u || dev.cdf_gen == 0u) && !(dev.dbg & DBG_NO_CDF_SUMM);
+    p.p2g_cdf_wgs = std::min((dev.n_rigid * 32u + 255u) / 256u, (uint32_t)grid_for(d, 32));
+    return p;
+}
+
+// which blocks a P2G launch takes (kernels_transfer.h layer_sel): all of them, or — the split form of a slab's phase A,
+// host_sharded.inc — the boundary layers with the pack waves behind them, then all other blocks with the interior's grid update
+enum class P2gLayers { all, boundary, others };
+
+// The shape of this substep's P2G.
+P2gLaunch plan_p2g(const wgs_data *d, P2gLayers layers) {
     const Dev &dev = d->dev;
     const uint32_t n = dev.n;
     const uint32_t NW = (uint32_t)P2GCfg<D>::NW;
     P2gLaunch p{};
     p.two_way = d->two_way;
-    p.layer_sel = p2g_sel == 2 ? 1u : p2g_sel == 3 ? 2u : 0u;   // (kernels_transfer.h: boundary layers / the others)
+    p.layer_sel = layers == P2gLayers::boundary ? 1u : layers == P2gLayers::others ? 2u : 0u;
     // Workgroups per body: about one per two entries of the block list (as the host last saw it), between 8 and
     // 32 per CU. A workgroup strides over the list, and the dispatcher balances better than a fixed stride does:
     // blocks differ in cost, and with 5 per CU — one resident round and a quarter — the quarter started when the
     // first workgroups retired (C5, 16 M particles: P2G 472 -> 346 us; C2: 35.6 -> 31.8 us). Same results for
     // any grid: a block's slab is the work of one workgroup.
     p.wgs = std::min((uint32_t)grid_for(d, 32), std::max((uint32_t)grid_for(d, 8), (d->seen.nblocks / 2u + 255u) & ~255u));
-    // Single-domain simulations: the grid update rides in the (last) P2G launch as workgroups of its own
-    // behind the P2G workgroups (kernels_transfer.h gu_waves; GU = 2), one wave per active block as the host last saw
-    // them; a P2G launch before it hands its slabs over the same way (GU = 1). Same results as the launch of its own
-    // (DBG_GU_OWN_LAUNCH): the same sums in the same order.
-    const bool fuse_gu = part == 0 && !dev.sharded && !(dev.dbg & DBG_GU_OWN_LAUNCH);
-    // Inside wgs_sharded_step (part 1 of a slab's substep): behind the P2G workgroups ride the waves that pack the
-    // outgoing messages (no k_pack_face launch) and the grid update of the INTERIOR blocks — everything that does
-    // not wait for the exchange; the interface layers are updated after it (GU = 3).
-    const bool fuse_shard = part == 1 && d->sub.in_sharded_step && d->link && d->link->attached && !(dev.dbg & DBG_GU_OWN_LAUNCH);
-    p.gu = fuse_gu ? 2 : fuse_shard ? 3 : 0;
-    d->sub.gu_fused = fuse_gu;
-    d->sub.shard_fused = fuse_shard;
+    p.gu = d->sub.gu_fused ? 2 : d->sub.shard_fused ? 3 : 0;   // (begin_substep)
     // (8, 16, 32 or 64 workgroups per CU at most: the same times at C2 / C3 / C5)
-    const uint32_t gu_wgs = (p.gu == 0 || p2g_sel == 2) ? 0u : std::min((uint32_t)grid_for(d, 8), std::max((uint32_t)grid_for(d, 1), ((d->seen.nblocks + NW - 1u) / NW + 7u) & ~7u));
-    if (fuse_shard && (d->link->has_lower || d->link->has_upper) && p2g_sel != 3) {   // (they ride behind the boundary layers' P2G)
+    const uint32_t gu_wgs = (p.gu == 0 || layers == P2gLayers::boundary) ? 0u : std::min((uint32_t)grid_for(d, 8), std::max((uint32_t)grid_for(d, 1), ((d->seen.nblocks + NW - 1u) / NW + 7u) & ~7u));
+    if (d->sub.shard_fused && (d->link->has_lower || d->link->has_upper) && layers != P2gLayers::others) {   // (they ride behind the boundary layers' P2G)
         const PackWaves pw = pack_waves(d);
         p.npack_blk = pw.blocks;
         p.npack = (pw.blocks + pw.guests + NW - 1u) / NW;
@@ -292,32 +333,46 @@ G2pLaunch plan_g2p(const wgs_data *d) {
     return p;
 }
 
-// One substep = pipeline.rs:201-280 (MPM passes), enqueued on the data's stream.
-// part 0 = the whole substep (single GPU, or a slab stepped without its neighbours); the sharded step splits it around
-// its one neighbour exchange: part 1 = sort .. P2G, part 2 = grid update + fused G2P (+ the arrivals' G2P) + bodies.
-// `p2g_sel` splits part 1 further (DBG_SHARD_SPLIT_LAYERS on lockstep slabs): 0 = all of it; 1 = the sort only; 2 = P2G of the
-// boundary layers with the pack waves behind it; 3 = P2G of all other blocks with the interior's grid update.
-template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part, int p2g_sel = 0) {
-    Dev &dev = d->dev;
-    hipStream_t s = d->stream;
-    const bool first = part != 2 && p2g_sel <= 1;   // the first call of this substep
-    const int side = d->side;
-    const uint32_t n = dev.n;
-    const int pgrid = (int)((n + SORT_THREADS - 1) / SORT_THREADS);
-    static const bool trace = getenv("WGS_TRACE") != nullptr;   // developer aid: drain the stream at every pass boundary and say so
-    auto mark = [&](int m) {
-        if (TS) hipEventRecord(d->timing.events.ev[ts_slot][m], s);
+// ---- the stages. One substep = pipeline.rs:201-280 (MPM passes), enqueued on the data's stream: begin_substep, enqueue_sort,
+// enqueue_p2g, enqueue_finish. wgs_step runs them back to back (single-domain data, or a slab stepped without its neighbours);
+// the sharded step puts its one neighbour exchange in front of enqueue_finish (host_sharded.inc, also on the split form of P2G).
+
+// The timing marks of the substep being enqueued (Substep::ts_slot; resolve_timings names them) and the developer's trace.
+struct Mark {
+    wgs_data *d;
+    void operator()(int m) const {
+        static const bool trace = getenv("WGS_TRACE") != nullptr;   // developer aid: drain the stream at every pass boundary and say so
+        if (d->sub.ts_slot >= 0) hipEventRecord(d->timing.events.ev[d->sub.ts_slot][m], d->stream);
         if (trace) {
-            const hipError_t te = hipStreamSynchronize(s);
-            fprintf(stderr, "[wgs trace] substep %llu part %d mark %d: %s\n", (unsigned long long)d->substeps, part, m, hipGetErrorString(te));
+            const hipError_t te = hipStreamSynchronize(d->stream);
+            fprintf(stderr, "[wgs trace] substep %llu mark %d: %s\n", (unsigned long long)d->substeps, m, hipGetErrorString(te));
         }
-    };
-    const uint32_t epoch = (uint32_t)(d->substeps + 1);
-    d->sub.gu_fused = false;
-    if (first) d->sub.shard_fused = false;   // (part 2 of a sharded substep consumes what its part 1 decided)
-    dev.ctr_set = (uint32_t)(d->substeps & 1u);  // sharded runs: the set of particle counters this substep reads (layout.h)
+    }
+};
+
+// A slab's counter catch-up: the set of particle counters the coming launches read (layout.h), and the counters of a buffer that
+// a substep without neighbours left unset (Substep::needs_compact: only ever set on a slab).
+void catch_up_counters(wgs_data *d) {
+    d->dev.ctr_set = (uint32_t)(d->substeps & 1u);
+    if (!d->sub.needs_compact) return;
+    hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, d->stream, d->dev);
+    d->sub.needs_compact = false;
+}
+
+// Every decision the launches of one substep share, made once, in front of its first launch: into d->sub what the stages read,
+// into d->dev the per-substep kernel arguments. "(same in every stage: ...)" says why a stage that used to compute the value
+// itself got this one: no entry point runs between the stages of a substep — a sharded step puts only its exchange and the
+// other slabs' stages there (maintain_grid and watch_counters run in front of a substep, fetch_counters in entry points of its own).
+wgs_status begin_substep(wgs_data *d, bool in_sharded_step, int ts_slot = -1) {
+    Dev &dev = d->dev;
+    wgs_data::Substep &sub = d->sub;
+    hipStream_t s = d->stream;
+    sub.in_sharded_step = in_sharded_step;
+    sub.ts_slot = ts_slot;
+    sub.epoch = (uint32_t)(d->substeps + 1);   // (same in every stage: `substeps` moves at the end of enqueue_finish only)
     // chunks of 64 sorted particles per wave of the fused G2P (kernels_transfer.h); the sort files the visit list by it
     // (2D: the body keeps no state of the chunk after the next one — at most two chunks per wave)
+    // (same in every stage: seen.nv_hint is written by maintain_grid and fetch_counters, dev.nv by enqueue_finish)
     const uint32_t nv_now = dev.sharded && d->seen.nv_hint != 0u ? std::min(d->seen.nv_hint, dev.nv) : dev.nv;   // (a slab launches for its capacity)
     dev.g2p_npass = (D == 3 && nv_now >= G2P_MANY_PASS_MIN_PARTICLES) ? (uint32_t)G2P_MANY_PASSES
                     : (nv_now >= G2P_TWO_PASS_MIN_PARTICLES || (dev.dbg & DBG_G2P_TWO_PASSES)) ? 2u : 1u;
@@ -325,159 +380,172 @@ template <bool TS> wgs_status enqueue_substep(wgs_data *d, int ts_slot, int part
     // (perm_cell) and neighbour links are still valid, so the particles are re-binned RELATIVE to their old
     // block (k_rebin: no hash lookups except for the few particles that changed block). The full k_bin runs
     // on the first substep, on table-rebuild substeps and in sharded runs (particles arrive from neighbours).
-    const bool rehash = d->substeps == 0 || (d->rehash_period != 0u && d->substeps % d->rehash_period == 0) || (d->seen.force_rehash && first);
-    if (rehash && first) {
+    // (read by the sort only: a later stage used to compute it again without the consumed force_rehash, for nobody)
+    sub.rehash = d->substeps == 0 || (d->rehash_period != 0u && d->substeps % d->rehash_period == 0) || d->seen.force_rehash;
+    if (sub.rehash) {
         d->stats.table_rebuilds++;
         d->seen.force_rehash = false;
         d->cdf_generation++;   // block ids are handed out anew
     }
     // node cdfs / block classes are reused from one substep to the next while no collider can move
+    // (same in every stage: cdf_generation and moving_mask move here and in setters, which are entry points)
     dev.cdf_gen = d->cpic ? d->cdf_generation : 0u;
     dev.cdf_moving = d->moving_mask;
-    const bool fused_cdf = d->cpic && dev.n_rigid == 0;  // (mesh cdfs are only complete after k_p2g_cdf)
-    if (first) dev.listed_in_perm = fused_cdf ? 1u : 0u;  // (part 2 of a sharded substep consumes what its part 1 wrote)
-    const bool use_rebin = d->sub.prev_sorted && !rehash && !(dev.dbg & DBG_NO_REBIN);
+    sub.fused_cdf = d->cpic && dev.n_rigid == 0;  // (mesh cdfs are only complete after k_p2g_cdf)
+    dev.listed_in_perm = sub.fused_cdf ? 1u : 0u;  // (written once per substep as before: enqueue_finish consumes what the sort wrote)
+    sub.use_rebin = sub.prev_sorted && !sub.rehash && !(dev.dbg & DBG_NO_REBIN);   // (read by the sort only, like `binned`)
     // The fused G2P of this substep also bins its output for the next one (g2p_body.inc, Dev::bin_next; slabs too), unless
     // that substep rebuilds the table anyway (DBG_REBIN_LAUNCH brings launch 1 of the sort, k_rebin, back: same results, tested).
     // `prebinned`: the previous substep's G2P did so for this one.
-    const bool binned = use_rebin && d->sub.prebinned;
-    if (first && d->sub.prebinned && !binned) {
+    sub.binned = sub.use_rebin && sub.prebinned;
+    if (sub.prebinned && !sub.binned) {
         // (a table rebuild nobody could foresee — ids three quarters handed out, seen by the host in between: what the G2P
         // accumulated for the old ids is dropped; the stamps it left mean nothing once the ids are handed out anew)
         HIP_TRY(hipMemsetAsync(dev.block_acc, 0, sizeof(uint32_t) * (size_t)dev.cap, s));
         HIP_TRY(hipMemsetAsync(dev.cell_head, 0, sizeof(uint32_t) * (size_t)dev.cap * NPB, s));
         HIP_TRY(hipMemsetAsync(dev.blk_narr, 0, sizeof(uint32_t) * (size_t)dev.cap, s));
     }
-    if (first) d->sub.prebinned = false;
+    sub.prebinned = false;
     // (not the plastic variants: their fused G2P is compiled without the binning — kernels_transfer.h: the code alone, beyond the
     // instruction cache, cost a third of the launch — and launch 1 of the sort, k_rebin, stays)
     // (a slab: its fused G2P bins the residents — the guests it drops leave their block's total —, k_g2p_arrivals the particles that
-    // arrive; both parts of a sharded substep see the same value)
+    // arrive. Same in every stage: the data's plasticity, switches and rebuild period are fixed, `substeps` as for the epoch)
     dev.bin_next = (!d->plastic && !(dev.dbg & (DBG_NO_REBIN | DBG_REBIN_LAUNCH)) && (d->rehash_period == 0u || (d->substeps + 1) % d->rehash_period != 0)) ? 1u : 0u;
     // the fused G2P drops the guests only inside the sharded step (kernels_shard.h); wgs_step on a slab advances what it holds
-    dev.skip_guests = (d->sub.in_sharded_step && dev.sharded) ? 1u : 0u;
-    if (dev.sharded && d->sub.needs_compact && first) {
-        hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, s, dev);
-        d->sub.needs_compact = false;
+    dev.skip_guests = (in_sharded_step && dev.sharded) ? 1u : 0u;
+    // Single-domain simulations: the grid update rides in the (last) P2G launch as workgroups of its own
+    // behind the P2G workgroups (kernels_transfer.h gu_waves; GU = 2), one wave per active block as the host last saw
+    // them; a P2G launch before it hands its slabs over the same way (GU = 1). Same results as the launch of its own
+    // (DBG_GU_OWN_LAUNCH): the same sums in the same order.
+    sub.gu_fused = !in_sharded_step && !dev.sharded && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    // Inside wgs_sharded_step: behind the P2G workgroups ride the waves that pack the outgoing messages (no k_pack_face launch)
+    // and the grid update of the INTERIOR blocks — everything that does not wait for the exchange; the interface layers are updated
+    // after it (GU = 3). (an empty slab launches no P2G for them to ride in. Same in every stage: attaching a slab is an entry point)
+    const bool attached = in_sharded_step && d->link && d->link->attached;
+    sub.shard_fused = attached && dev.n > 0 && !(dev.dbg & DBG_GU_OWN_LAUNCH);
+    sub.arrivals = attached;
+    catch_up_counters(d);   // (a slab last stepped by wgs_step: k_shard_compacted at the head of this substep)
+    return WGS_OK;
+}
+
+// marks 0..3 — "grid sort" (grid.rs:30-207), then the node and particle cdfs of mesh colliders
+template <int DIM> wgs_status enqueue_sort(wgs_data *d) {
+    Dev &dev = d->dev;
+    hipStream_t s = d->stream;
+    const Mark mark{d};
+    const int side = d->side;
+    const uint32_t n = dev.n, epoch = d->sub.epoch;
+    const int pgrid = (int)((n + SORT_THREADS - 1) / SORT_THREADS);
+    const SortLaunch p = plan_sort(d);
+    if (d->sub.ts_slot >= 0) {  // two adjacent marks: their distance is what every interval below pays for its closing mark
+        mark(9);
+        mark(10);
     }
-    if (first) {
-        if (TS) {  // two adjacent marks: their distance is what every interval below pays for its closing mark
-            mark(9);
-            mark(10);
-        }
-        mark(0);
-        // ---- "grid sort" (grid.rs:30-207)
-        if (d->seen.force_refresh && !rehash && dev.free_ids != nullptr) {
-            // the marks of evicted blocks crowd the table (the host's last look): clear it and insert the live blocks again under
-            // their own ids — no particle is touched, the steady-state sort goes on (kernels_sort.h k_table_refresh)
-            HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
-            HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
-            hipLaunchKernelGGL(k_table_refresh, dim3(std::max(1u, std::min((dev.cap + 255u) / 256u, (uint32_t)grid_for(d, 4)))), dim3(256), 0, s, dev);
-            d->stats.table_refreshes++;
-        }
-        if (first) d->seen.force_refresh = false;
-        if (rehash) {  // reset_hmap, amortised (device_math.h)
-            HIP_TRY(hipMemsetAsync(dev.hkeys, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
-            HIP_TRY(hipMemsetAsync(dev.hvals, 0xff, sizeof(uint32_t) * ((size_t)dev.hmask + 1), s));
-            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NPHYS, 0, sizeof(uint32_t), s));
-            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NFREE, 0, 3 * sizeof(uint32_t), s));   // (free list, insertion count, marks: layout.h)
-        }
-        // ---- "update rigid particles" (rigid_particle_update.wgsl): samples and vertices of the mesh colliders
-        if (dev.n_rigid > 0)
-            hipLaunchKernelGGL(k_rigid_transform<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev);
-        if (n > 0) {
-            // (sharded runs: k_rebin also bins the particles that arrived in the last substep, behind the residents)
-            // (a pending integrate_bodies of the previous substep rides in workgroup 0 of this launch)
-            const uint32_t do_bodies = d->sub.bodies_pending ? 1u : 0u;
-            d->sub.bodies_pending = false;
-            if (binned) {   // launch 1 ran inside the previous substep's fused G2P
-                if (do_bodies) hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, s, dev);
-            } else if (use_rebin) hipLaunchKernelGGL(k_rebin<D>, dim3((pgrid + REBIN_K - 1) / REBIN_K), dim3(SORT_THREADS), 0, s, dev, side, epoch, do_bodies);
-            else hipLaunchKernelGGL(k_bin<D>, dim3(pgrid), dim3(SORT_THREADS), 0, s, dev, side, epoch, do_bodies);
-            if (dev.n_rigid > 0) {  // blocks a mesh sample reaches must exist (sort.wgsl:38-86)
-                hipLaunchKernelGGL(k_rigid_mark<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev, epoch);
-                hipLaunchKernelGGL(k_rigid_touch<D>, dim3(grid_for(d, 1)), dim3(256), 0, s, dev, epoch);
-            }
-            // launch 2: chunked scan (active list, first_particle) + per-block setup and regrouping in canonical order.
-            // Collider simulations without mesh colliders: node cdf + block classes ride in this launch, the particle
-            // cdf in the CPIC P2G launch (no CDF launch at all)
-            {
-                const uint32_t nscan = (dev.cap + SCAN_CHUNK - 1) / SCAN_CHUNK;
-                // one resident round: 4 workgroups per CU (127 VGPRs, 36 KB of LDS), the scan workgroups among them
-                const uint32_t nreg = std::max(1u, std::min((dev.cap + 3u) / 4u, WGS_REGROUP_ROUNDS * ((uint32_t)grid_for(d, 4) - std::min(nscan, (uint32_t)grid_for(d, 2)))));
-                const dim3 g(nscan + nreg);
-                const int have_old = use_rebin ? 1 : 0;
-                // (summ: every block within reach of a collider is evaluated substep after substep — each evaluates its own nodes and
-                // tells its neighbours, kernels_sort.h block_cdf_summ; with colliders at rest: the instantiation without)
-                const bool summ = (dev.cdf_moving != 0u || dev.cdf_gen == 0u) && !(dev.dbg & DBG_NO_CDF_SUMM);
-                launch_regroup<D>(dev, s, g, side, epoch, nscan, have_old, fused_cdf, summ);
-            }
-        } else {
-            HIP_TRY(hipMemsetAsync(dev.counters + CTR_NBLOCKS, 0, sizeof(uint32_t), s));
-        }
-        mark(1);
-        // ---- "grid_update_cdf" + "g2p_cdf" (collide.wgsl, grid_update_cdf.wgsl, g2p_cdf.wgsl): one launch
-        // (kernels_cdf.h); the reference's two pass names share its time in wgs_read_timings
-        if (dev.n_rigid > 0 && n > 0)  // "p2g_cdf": mesh primitives -> node cdf accumulators
-            hipLaunchKernelGGL(k_p2g_cdf<D>, dim3(std::min((dev.n_rigid * 32u + 255u) / 256u, (uint32_t)grid_for(d, 32))), dim3(256), 0, s, dev, epoch);
-        if (d->cpic && n > 0 && !fused_cdf)
-            hipLaunchKernelGGL(k_cdf<D>, dim3(grid_for(d, 16)), dim3(CDF_THREADS), 0, s, dev, side, epoch);
-        mark(2);
-        mark(3);
+    mark(0);
+    if (p.refresh) {
+        WGS_TRY(clear_table(d, false));
+        hipLaunchKernelGGL(k_table_refresh, dim3(p.refresh_wgs), dim3(256), 0, s, dev);
+        d->stats.table_refreshes++;
     }
-    if (part != 2 && p2g_sel != 1) {
-        if (n > 0) launch_p2g<D>(dev, s, side, epoch, plan_p2g(d, part, p2g_sel));   // ---- "p2g"
-        mark(4);
-    }
-    if (part != 1) {
-        // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
-        if (n > 0 && !(part == 0 && d->sub.gu_fused))
-            launch_grid_update<D>(dev, s, dim3(grid_for(d, WGS_GU_WG_PER_CU)), epoch, part != 0, d->two_way, d->sub.shard_fused ? 1u : 0u);
-        mark(5);
-        // ---- "g2p" + "particles_update", fused (mark 6: between the two launches of a collider simulation's G2P)
-        const G2pLaunch g2p = plan_g2p(d);
-        if (dev.nv > 0) launch_g2p<D>(dev, s, side, epoch, d->plastic, g2p, mark);
-        if (!(dev.nv > 0 && g2p.shape == G2pShape::two_launches)) mark(6);
-        // sharded step: the particles that arrived with this substep's messages are advanced too (kernels_arrivals.h), by a
-        // launch of their own behind the fused G2P. (As extra workgroups INSIDE that launch — first or last in its grid — they
-        // made it 7-10 us longer at a 1 M slab for the 5 us launch they saved: measured twice in round 3, not kept.)
-        // (the arrivals' body also does the bookkeeping of the migration round, so it runs even when nobody can arrive)
-        const bool arrivals = part == 2 && d->sub.in_sharded_step && d->link && d->link->attached;
-        if (arrivals) {
-            const uint32_t arr_most = ((d->link->has_lower ? 1u : 0u) + (d->link->has_upper ? 1u : 0u)) * d->link->mig_cap;
-            launch_arrivals<D>(dev, s, dim3(std::max(1u, std::min((arr_most + ARR_PER_WG - 1u) / ARR_PER_WG, 1024u))), side, epoch, d->plastic);
+    d->seen.force_refresh = false;
+    if (p.reset_table) WGS_TRY(clear_table(d, true));
+    // ---- "update rigid particles" (rigid_particle_update.wgsl): samples and vertices of the mesh colliders
+    if (dev.n_rigid > 0)
+        hipLaunchKernelGGL(k_rigid_transform<DIM>, dim3(p.mesh_wgs), dim3(256), 0, s, dev);
+    if (n > 0) {
+        d->sub.bodies_pending = false;   // (p.do_bodies)
+        switch (p.bin) {
+            case SortBin::by_last_g2p: if (p.do_bodies) launch_bodies_integrate(d); break;
+            case SortBin::rebin: hipLaunchKernelGGL(k_rebin<DIM>, dim3((pgrid + REBIN_K - 1) / REBIN_K), dim3(SORT_THREADS), 0, s, dev, side, epoch, p.do_bodies); break;
+            case SortBin::full: hipLaunchKernelGGL(k_bin<DIM>, dim3(pgrid), dim3(SORT_THREADS), 0, s, dev, side, epoch, p.do_bodies); break;
         }
-        mark(7);
-        // ---- "integrate_bodies" (rigid_impulses.wgsl:95-136) + the world mass properties of the next substep
-        // (pipeline.rs:204-205). Skipped while no body has a velocity or a mass: it would be the identity.
-        if (d->bodies_move && dev.n_colliders > 0 && !(part == 2 && d->reduce_impulses == 2)) {
-            if (part == 2 && d->reduce_impulses == 1) {
-                wgs_status rst = allreduce_impulses(d);
-                if (rst != WGS_OK) return rst;
-            }
-            // Single-domain simulations without mesh colliders: left to the first launch of the next substep (or to the end of
-            // this wgs_step call, flush_bodies) — a 16-thread launch of its own costs a dependent launch, ~5 us, per substep.
-            // (not when this substep's G2P binned for the next one: that substep has no launch in front of the node cdfs of its sort)
-            if (part == 0 && !dev.sharded && dev.n_rigid == 0 && n > 0 && !(dev.dbg & DBG_BODIES_OWN_LAUNCH) && !dev.bin_next) d->sub.bodies_pending = true;
-            else hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, s, dev);
+        if (dev.n_rigid > 0) {  // blocks a mesh sample reaches must exist (sort.wgsl:38-86)
+            hipLaunchKernelGGL(k_rigid_mark<DIM>, dim3(p.mesh_wgs), dim3(256), 0, s, dev, epoch);
+            hipLaunchKernelGGL(k_rigid_touch<DIM>, dim3(p.mesh_wgs), dim3(256), 0, s, dev, epoch);
         }
-        mark(8);
-        d->side ^= 1;
-        d->substeps++;
-        d->sub.prev_sorted = true;
-        d->sub.prebinned = dev.bin_next != 0u && dev.nv > 0;
-        dev.n = dev.nv;  // the buffer just written holds the valid particles only, in sorted order
-        // sharded: the counters of the new buffer (CTR_N / CTR_NPREV / CTR_NV) are set by k_g2p_arrivals; a slab stepped
-        // without its neighbours (wgs_step) sets them at the head of its next substep (k_shard_compacted)
-        if (dev.sharded && !arrivals) d->sub.needs_compact = true;
+        // launch 2: chunked scan (active list, first_particle) + per-block setup and regrouping in canonical order.
+        // Collider simulations without mesh colliders: node cdf + block classes ride in this launch, the particle
+        // cdf in the CPIC P2G launch (no CDF launch at all)
+        launch_regroup<DIM>(dev, s, dim3(p.nscan + p.nreg), side, epoch, p.nscan, p.have_old, p.cdf, p.summ);
+    } else {
+        HIP_TRY(hipMemsetAsync(dev.counters + CTR_NBLOCKS, 0, sizeof(uint32_t), s));
     }
+    mark(1);
+    // ---- "grid_update_cdf" + "g2p_cdf" (collide.wgsl, grid_update_cdf.wgsl, g2p_cdf.wgsl): one launch
+    // (kernels_cdf.h); the reference's two pass names share its time in wgs_read_timings
+    if (dev.n_rigid > 0 && n > 0)  // "p2g_cdf": mesh primitives -> node cdf accumulators
+        hipLaunchKernelGGL(k_p2g_cdf<DIM>, dim3(p.p2g_cdf_wgs), dim3(256), 0, s, dev, epoch);
+    if (d->cpic && n > 0 && !p.cdf)
+        hipLaunchKernelGGL(k_cdf<DIM>, dim3(grid_for(d, 16)), dim3(CDF_THREADS), 0, s, dev, side, epoch);
+    mark(2);
+    mark(3);
     HIP_TRY(hipGetLastError());
     return WGS_OK;
 }
 
+// mark 4 — "p2g", with what rides behind its workgroups (plan_p2g)
+template <int DIM> wgs_status enqueue_p2g(wgs_data *d, P2gLayers layers) {
+    if (d->dev.n > 0) launch_p2g<DIM>(d->dev, d->stream, d->side, d->sub.epoch, plan_p2g(d, layers));
+    Mark{d}(4);
+    HIP_TRY(hipGetLastError());
+    return WGS_OK;
+}
+
+// marks 5..8 — grid update, fused G2P, a slab's arrivals, bodies; then the substep is over
+template <int DIM> wgs_status enqueue_finish(wgs_data *d) {
+    Dev &dev = d->dev;
+    const wgs_data::Substep &sub = d->sub;
+    hipStream_t s = d->stream;
+    const Mark mark{d};
+    const int side = d->side;
+    const uint32_t n = dev.n, epoch = sub.epoch;
+    // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
+    if (n > 0 && !sub.gu_fused)
+        launch_grid_update<DIM>(dev, s, dim3(grid_for(d, WGS_GU_WG_PER_CU)), epoch, sub.in_sharded_step, d->two_way, sub.shard_fused ? 1u : 0u);
+    mark(5);
+    // ---- "g2p" + "particles_update", fused (mark 6: between the two launches of a collider simulation's G2P)
+    const G2pLaunch g2p = plan_g2p(d);
+    if (dev.nv > 0) launch_g2p<DIM>(dev, s, side, epoch, d->plastic, g2p, mark);
+    if (!(dev.nv > 0 && g2p.shape == G2pShape::two_launches)) mark(6);
+    // sharded step: the particles that arrived with this substep's messages are advanced too (kernels_arrivals.h), by a
+    // launch of their own behind the fused G2P. (As extra workgroups INSIDE that launch — first or last in its grid — they
+    // made it 7-10 us longer at a 1 M slab for the 5 us launch they saved: measured twice in round 3, not kept.)
+    // (the arrivals' body also does the bookkeeping of the migration round, so it runs even when nobody can arrive)
+    if (sub.arrivals) {
+        const uint32_t arr_most = ((d->link->has_lower ? 1u : 0u) + (d->link->has_upper ? 1u : 0u)) * d->link->mig_cap;
+        launch_arrivals<DIM>(dev, s, dim3(std::max(1u, std::min((arr_most + ARR_PER_WG - 1u) / ARR_PER_WG, 1024u))), side, epoch, d->plastic);
+    }
+    mark(7);
+    // ---- "integrate_bodies" (rigid_impulses.wgsl:95-136) + the world mass properties of the next substep
+    // (pipeline.rs:204-205). Skipped while no body has a velocity or a mass: it would be the identity.
+    // (reduce_impulses is read HERE, not in begin_substep: the lockstep step sets it between a slab's two phases; 2 = the group sums and integrates)
+    if (d->bodies_move && dev.n_colliders > 0 && !(sub.in_sharded_step && d->reduce_impulses == 2)) {
+        if (sub.in_sharded_step && d->reduce_impulses == 1) WGS_TRY(allreduce_impulses(d));
+        // Single-domain simulations without mesh colliders: left to the first launch of the next substep (or to the end of
+        // this wgs_step call, flush_bodies) — a 16-thread launch of its own costs a dependent launch, ~5 us, per substep.
+        // (not when this substep's G2P binned for the next one: that substep has no launch in front of the node cdfs of its sort)
+        if (!sub.in_sharded_step && !dev.sharded && dev.n_rigid == 0 && n > 0 && !(dev.dbg & DBG_BODIES_OWN_LAUNCH) && !dev.bin_next) d->sub.bodies_pending = true;
+        else launch_bodies_integrate(d);
+    }
+    mark(8);
+    d->side ^= 1;
+    d->substeps++;
+    d->sub.prev_sorted = true;
+    d->sub.prebinned = dev.bin_next != 0u && dev.nv > 0;
+    dev.n = dev.nv;  // the buffer just written holds the valid particles only, in sorted order
+    // sharded: the counters of the new buffer (CTR_N / CTR_NPREV / CTR_NV) are set by k_g2p_arrivals; a slab stepped
+    // without its neighbours (wgs_step) sets them at the head of its next substep (k_shard_compacted)
+    if (dev.sharded && !sub.arrivals) d->sub.needs_compact = true;
+    HIP_TRY(hipGetLastError());
+    return WGS_OK;
+}
+
+// integrate_bodies in a launch of its own: where no sort launch carries it
+void launch_bodies_integrate(wgs_data *d) { hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, d->stream, d->dev); }
+
 // integrate_bodies of a lockstep group (the group summed the impulses of its slabs after every slab's grid update)
 wgs_status enqueue_bodies(wgs_data *d) {
-    if (d->bodies_move && d->dev.n_colliders > 0) hipLaunchKernelGGL(k_bodies_integrate<D>, dim3(1), dim3(16), 0, d->stream, d->dev);
+    if (d->bodies_move && d->dev.n_colliders > 0) launch_bodies_integrate(d);
     HIP_TRY(hipGetLastError());
     return WGS_OK;
 }

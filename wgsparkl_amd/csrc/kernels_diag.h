@@ -476,13 +476,7 @@ wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     if (what & WGS_DIAG_ENERGY) what |= WGS_DIAG_PARTICLES;
     if (!d->diag_acc) WGS_TRY(dev_alloc(d, &d->diag_acc, 1));
     DiagAcc *acc = d->diag_acc;
-    if (d->dev.sharded) {   // (the particle counters of a slab live on the device, in the set of the substep's parity: wgs_shard_export)
-        d->dev.ctr_set = (uint32_t)(d->substeps & 1u);
-        if (d->sub.needs_compact) {
-            hipLaunchKernelGGL(k_shard_compacted, dim3(1), dim3(64), 0, d->stream, d->dev);
-            d->sub.needs_compact = false;
-        }
-    }
+    if (d->dev.sharded) catch_up_counters(d);   // (the particle counters of a slab live on the device, in the set of the substep's parity)
     const bool part = what & WGS_DIAG_PARTICLES, energy = what & WGS_DIAG_ENERGY, digest = what & WGS_DIAG_DIGEST, grid = what & WGS_DIAG_GRID;
     const dim3 blocks(grid_for(d, 4)), threads(256);
     const float *phase = (d->plastic || d->dev.sharded) ? nullptr : d->static_phase;
