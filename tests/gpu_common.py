@@ -9,6 +9,7 @@ from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrag
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
 import cdf_truth as CT
+import cpic_truth as CP
 import mesh_truth as MT
 import transfer_truth as T
 from helpers import (assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, pipeline, rel_rms, report_margin, run_gpu,
@@ -60,17 +61,17 @@ class Checked(NamedTuple):
     rigid: object                  # the mesh_truth.Rigid of the substep (None without a mesh collider)
 
 
-def checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None):
+def checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders=None, before=None):
     """one substep of `data`, checked against the fp64 truth of the collider distance fields; `first`: the uploaded state is
-    the state before it (else it is read back). Where the scene has mesh colliders the truth includes the blocks and the
-    votes of their samples (tests/mesh_truth.py); without one mesh_truth.rigid_of gives None and every step below is the
-    analytic one."""
+    the state before it (else it is `before`, or read back). Where the scene has mesh colliders the truth includes the
+    blocks and the votes of their samples (tests/mesh_truth.py); without one mesh_truth.rigid_of gives None and every step
+    below is the analytic one."""
     ps = sc["particles"]
     d, h = ps.dim, sc["cell_width"]
     if first:
-        pos, prev = ps.pos, np.zeros(ps.n, np.uint32)
+        pos, prev = ps.pos, ps.cdf_affinity
     else:
-        before = data.read_particles()
+        before = data.read_particles() if before is None else before
         pos, prev = before.pos, before.cdf_affinity
     poses = data.read_body_poses()
     pipeline(d).step(data, 1)
@@ -89,6 +90,38 @@ def checked_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, colliders
     CT.check_particle_cdf(f"{tag} end to end", e2e, got.cdf_affinity, got.cdf_dist, got.cdf_normal, fails)
     CT.assert_caps(tag, nf, e2e, part_cap)
     return Checked(nf, e2e, got, rg)
+
+
+class CheckedCpic(NamedTuple):
+    """what checked_cpic_substep returns"""
+    cdf: Checked                   # the distance-field check of the substep
+    end_to_end: CP.Result          # the CPIC truth from the kernel's own decisions
+    before: object                 # the particles before the substep
+    got: object                    # ... and after it
+
+
+def checked_cpic_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, extra_levels=0.0):
+    """one substep of `data` checked twice: the collider distance fields (checked_substep), and the CPIC transfer from the
+    kernel's own read-back decisions (tests/cpic_truth.py): the particles' cdf fields, the nodes' affinities and closest
+    ids, the bodies' velocities and centres of mass before the step. Every node's mass and velocity; every particle's x,
+    v, F and C' from the kernel's own grid and end to end with the node bounds propagated."""
+    ps = sc["particles"]
+    d, h = ps.dim, sc["cell_width"]
+    before = ps if first else data.read_particles()
+    poses = data.read_body_poses()
+    ck = checked_substep(tag, sc, data, fails, first, part_cap, before=before)
+    cells, vm, _, aff, closest = data.read_grid()
+    got = ck.got
+    f = CP.Fields(got.cdf_affinity, got.cdf_normal.astype(np.float64), got.cdf_dist.astype(np.float64), cells, aff, closest)
+    mo = CP.Motion.of(sc["colliders"], d, poses)
+    inp = T.Inputs.of(before)
+    prm = sc["params"]
+    e2e = CP.substep(inp, h, prm.dt, prm.gravity, f, mo, extra_levels=extra_levels)
+    near_n, nn, near_p = CP.check_result(f"{tag} cpic end to end", e2e, cells, vm, got, sc["model"], fails, extra_levels=extra_levels)
+    iso = CP.substep(inp, h, prm.dt, prm.gravity, f, mo, own_grid=(cells, vm[:, :d]))
+    CP.check_result(f"{tag} cpic isolated G2P", iso, None, None, got, sc["model"], fails)
+    CP.assert_near(f"{tag} cpic", near_n, nn, near_p, inp.n)
+    return CheckedCpic(ck, e2e, before, got)
 
 
 def blocks_in_reach(nf, col, d):
@@ -178,9 +211,9 @@ def _native_slabs(sc, world, pipe, **kw):
     return shards, part
 
 
-def _export_cdf(shard):
-    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds: the exchange
-    records carry every quad of the particle and the substep its cdf was computed in"""
+def _export_records(shard):
+    """the exchange records of the particles a slab holds [count, floats per record]: every quad of the particle, its global id
+    and the substep its cdf was computed in"""
     import ctypes as C
     import torch
     from wgsparkl_amd import _ffi
@@ -189,7 +222,13 @@ def _export_cdf(shard):
     torch.cuda.current_stream(buf.device).synchronize()
     cnt = C.c_uint32(0)
     _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
-    rec = buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
+    return buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
+
+
+def _export_cdf(shard, rec=None):
+    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds"""
+    D = shard.dim
+    rec = _export_records(shard) if rec is None else rec
     ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
     q = lambda k: rec[:, 4 * k:4 * k + 4]
     if D == 3:
@@ -197,15 +236,28 @@ def _export_cdf(shard):
     return ids, q(0)[:, :2].copy(), q(7)[:, 3].copy().view(np.uint32), q(7)[:, 2].copy(), q(7)[:, :2].copy(), stamp
 
 
-def _export_all(shards, n, d):
+def _export_all(shards, n, d, recs=None):
     """the particles of all slabs in the order of their global ids; a cdf whose stamp is not the newest is the default one"""
-    parts = [_export_cdf(s) for s in shards]
+    parts = [_export_cdf(s, None if recs is None else recs[r]) for r, s in enumerate(shards)]
     ids = np.concatenate([p[0] for p in parts]).astype(np.int64)
     assert np.array_equal(np.sort(ids), np.arange(n)), "every particle exactly once"
     order = np.argsort(ids)
     pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
     live = stamp == stamp.max()
     return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)
+
+
+def export_state_and_cdf(shards, n, d):
+    """one export per slab, read twice: ({pos, vel, def_grad, affine, mass} in the order of the global ids, the rank that holds
+    each particle, cdf_affinity, cdf_dist, cdf_normal)"""
+    from wgsparkl_amd.sharded import unpack_records
+    recs = [_export_records(s) for s in shards]
+    outs = [unpack_records(rec, d, s.uniform_material if d == 3 else None) for rec, s in zip(recs, shards)]
+    ids = np.concatenate([o["ids"] for o in outs]).astype(np.int64)
+    order = np.argsort(ids)
+    held = np.concatenate([np.full(len(o["ids"]), r) for r, o in enumerate(outs)])[order]
+    _, aff, dist, normal = _export_all(shards, n, d, recs)          # (asserts that every particle is there exactly once)
+    return {f: np.concatenate([o[f] for o in outs])[order] for f in ("pos", "vel", "def_grad", "affine", "mass")}, held, aff, dist, normal
 
 
 def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):

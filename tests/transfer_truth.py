@@ -91,9 +91,12 @@ class Stencil:
 class Grid:
     """fp64 P2G + grid update. Node arrays are over the unique stencil nodes (`cells`, sorted by key)."""
 
-    def __init__(self, inp: Inputs, st: Stencil, dt, gravity, variant=()):
+    def __init__(self, inp: Inputs, st: Stencil, dt, gravity, variant=(), gate=None):
+        """`gate` [n, S] bool (CPIC, tests/cpic_truth.py): the (particle, node) pairs that transfer; the others add nothing to a
+        node, and are not among its contributors. None: every pair transfers."""
         d = inp.d
         h = st.h
+        sw = st.w if gate is None else np.where(gate, st.w, 0.0)
         g = np.zeros(d)
         g[:] = np.asarray(gravity, np.float64)[:d]
         if "gravity_g1_on_every_axis" in variant:
@@ -109,18 +112,18 @@ class Grid:
         cd = np.einsum("nrc,nsc->nsr", inp.C, st.dpt)                     # [n, S, d]
         mom = cd + mv[:, None, :]
         idx = self.inv.reshape(-1)
-        wm = (inp.m[:, None] * st.w).reshape(-1)
+        wm = (inp.m[:, None] * sw).reshape(-1)
         self.mass = np.bincount(idx, wm, M)
-        self.mom = np.stack([np.bincount(idx, (mom[..., k] * st.w).reshape(-1), M) for k in range(d)], 1)
-        self.count = np.bincount(idx, None, M)
+        self.mom = np.stack([np.bincount(idx, (mom[..., k] * sw).reshape(-1), M) for k in range(d)], 1)
+        self.count = np.bincount(idx, None if gate is None else gate.reshape(-1).astype(np.float64), M)
         # scales: sum w m, sum w |m v + C dpt| (as |m v| + |C| |dpt|: what the kernel rounds), and the weight-error sums
         cn = np.linalg.norm(inp.C, axis=(1, 2))
         amom = np.linalg.norm(mv, axis=1)[:, None] + cn[:, None] * np.linalg.norm(st.dpt, axis=2)
         self.s_m = self.mass.copy()
-        self.s_p = np.bincount(idx, (st.w * amom).reshape(-1), M)
-        ew = st.weight_error[:, None] * np.ones_like(st.w)
+        self.s_p = np.bincount(idx, (sw * amom).reshape(-1), M)
+        ew = st.weight_error[:, None] * (np.ones_like(st.w) if gate is None else gate.astype(np.float64))
         self.e_m = np.bincount(idx, (ew * inp.m[:, None]).reshape(-1), M)
-        self.e_p = np.bincount(idx, (ew * amom + st.w * (cn * st.dpt_error)[:, None]).reshape(-1), M)
+        self.e_p = np.bincount(idx, (ew * amom + sw * (cn * st.dpt_error)[:, None]).reshape(-1), M)
         with np.errstate(divide="ignore", invalid="ignore"):
             inv_m = np.where(self.mass > 0, 1.0 / self.mass, 0.0)
         self.vel_u = (self.mom + self.mass[:, None] * g[None, :] * self.dt) * inv_m[:, None]
@@ -162,7 +165,10 @@ class Particles:
     `node_vel` [n, S, d]: the velocity of every stencil node of every particle (fp64 truth grid, or a kernel's own grid:
     the isolated G2P truth). `node_bound` [n, S]: the bound of those node velocities (0 for a kernel's own grid)."""
 
-    def __init__(self, inp: Inputs, st: Stencil, node_vel, dt, node_bound=None, u=U32, variant=()):
+    def __init__(self, inp: Inputs, st: Stencil, node_vel, dt, node_bound=None, u=U32, variant=(), contact=None):
+        """`contact` (CPIC, a cpic_truth.Contact): project(vel_g, b_vel_g, u) -> (velocity, bound) of the penetrating particles'
+        projection before the speed cap, penalty(dt, u) -> (dv, bound) of the impulse added after the advection; its
+        variants "cap_before_projection" and "advect_after_penalty" reorder the update. None: no collider."""
         d, h, dt = inp.d, st.h, float(dt)
         self.d, self.h, self.dt, self.u = d, h, dt, u
         self.lim = h / dt
@@ -171,12 +177,6 @@ class Particles:
         self.invd = 4.0 if "invd_4" in variant else 4.0 / (h * h)
         self.vel_g = np.einsum("ns,nsr->nr", w, node_vel)
         self.grad = self.invd * np.einsum("ns,nsr,nsc->nrc", w, node_vel, st.dpt)
-        speed = np.linalg.norm(self.vel_g, axis=1)
-        cap = speed > self.lim
-        self.vel = self.vel_g.copy()
-        self.vel[cap] *= (self.lim / speed[cap])[:, None]
-        self.x = inp.x + self.vel * dt
-        self.F = inp.F + (self.grad * dt) @ inp.F
         # ---- bounds (normwise per particle)
         anv = np.linalg.norm(node_vel, axis=2)                            # [n, S]
         s_v = np.einsum("ns,ns->n", w, anv)
@@ -188,12 +188,34 @@ class Particles:
         if node_bound is not None:
             b_vel = b_vel + np.einsum("ns,ns->n", w, node_bound)
             b_grad = b_grad + self.invd * np.einsum("ns,ns,ns->n", w, node_bound, dn)
-        self.near_cap = (np.abs(speed - self.lim) <= b_vel + NEAR_CLAMP * self.lim) & (b_vel < LOOSE * self.lim)
         self.b_vel_g = b_vel
+        cvar = () if contact is None else contact.variant
+        pre = self.vel_g
+        if "cap_before_projection" in cvar:
+            s0 = np.linalg.norm(pre, axis=1)
+            pre = np.where((s0 > self.lim)[:, None], pre * (self.lim / np.maximum(s0, 1e-300))[:, None], pre)
+        if contact is not None:
+            pre, b_vel = contact.project(pre, b_vel, u)
+        self.vel_c = pre
+        speed = np.linalg.norm(pre, axis=1)
+        cap = (speed > self.lim) & ("cap_before_projection" not in cvar)
+        self.vel = pre.copy()
+        self.vel[cap] *= (self.lim / speed[cap])[:, None]
+        self.near_cap = (np.abs(speed - self.lim) <= b_vel + NEAR_CLAMP * self.lim) & (b_vel < LOOSE * self.lim)
         self.b_vel = b_vel + C_UPD * u * np.linalg.norm(self.vel, axis=1) + np.where(speed >= self.lim * (1 - NEAR_CLAMP), 4 * u * self.lim, 0.0)
         self.b_grad = b_grad
         vn = np.linalg.norm(self.vel, axis=1)
-        self.b_x = dt * self.b_vel + C_UPD * u * (np.linalg.norm(inp.x, axis=1) + dt * vn)
+        self.vel_adv = self.vel
+        b_adv = self.b_vel
+        if contact is not None:
+            dv, b_dv = contact.penalty(dt, u)
+            self.vel = self.vel + dv
+            self.b_vel = self.b_vel + b_dv
+            if "advect_after_penalty" in cvar:
+                self.vel_adv = self.vel
+        self.x = inp.x + self.vel_adv * dt
+        self.F = inp.F + (self.grad * dt) @ inp.F
+        self.b_x = dt * b_adv + C_UPD * u * (np.linalg.norm(inp.x, axis=1) + dt * vn)
         fn = np.linalg.norm(inp.F, axis=(1, 2))
         gn = np.linalg.norm(self.grad, axis=(1, 2))
         self.b_F = dt * b_grad * fn + C_UPD * u * d * (fn + dt * gn * fn)
