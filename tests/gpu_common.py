@@ -53,6 +53,37 @@ def check_blocks(data, st):
     assert sorted(ids.tolist()) == list(range(st.n))
 
 
+def assert_runs_canonical(vid, first, num, ids, pos_before, dim, h):
+    """The order the whole sort rests on, from read_blocks()'s arrays and the positions the sort saw: `ids` holds every
+    particle once, and every block's run ids[first : first + num] goes by in-block cell (t0 + (t1 << BSHIFT) +
+    (t2 << 2 BSHIFT), the cell being the one the cells-exact comparisons use: oracle.np_oracle.assoc_cell), the cells lying
+    in the block, and by strictly ascending particle id inside a cell."""
+    ids = np.asarray(ids, np.int64)
+    n = len(pos_before)
+    assert np.array_equal(np.sort(ids), np.arange(n)), "the sorted ids are not a permutation of the particles"
+    assert int(np.asarray(num, np.int64).sum()) == n, "the runs do not hold every particle"
+    bw = T.bw_of(dim)
+    bshift = bw.bit_length() - 1
+    cell = CT.assoc_cell(np.asarray(pos_before, np.float32), h)
+    for b in range(len(vid)):
+        run = ids[int(first[b]):int(first[b]) + int(num[b])]
+        c = cell[run]
+        assert np.array_equal(c // bw, np.broadcast_to(np.asarray(vid[b], np.int64), c.shape)), f"block {tuple(vid[b])}: a particle of its run is in another block"
+        t = c % bw
+        key = sum(t[:, k] << (bshift * k) for k in range(dim))
+        step = np.diff(key)
+        assert (step >= 0).all(), f"block {tuple(vid[b])}: the cells of its run do not ascend"
+        assert (np.diff(run)[step == 0] > 0).all(), f"block {tuple(vid[b])}: ids do not ascend strictly inside a cell"
+
+
+def assert_canonical_order(data, pos_before, dim, h):
+    """assert_runs_canonical of what `data` holds after a substep; `pos_before`: the positions read BEFORE that substep (the
+    sort of substep n orders the state substep n - 1 left)."""
+    vid, first, num, ids = data.read_blocks()
+    assert_runs_canonical(vid, first, num, ids, pos_before, dim, h)
+    return vid, first, num, ids
+
+
 class Checked(NamedTuple):
     """what checked_substep returns"""
     nodes: CT.NodeField            # the node truth of the substep

@@ -38,7 +38,7 @@ using namespace wgs;
 #include "host_state.h"          // error reporting, the handle structs, who owns device memory
 #include "host_grid.inc"         // the arrays sized by the block capacity, growth, the host's looks at the counters
 #include "kernels_readback.h"    // device code of the readers and of the checkpoint / render hand-off
-#include "host_substep.inc"      // launch ladders, launch plans, enqueue_substep
+#include "host_substep.inc"      // launch ladders, launch plans, the stages of a substep (begin_substep ... enqueue_finish)
 #include "capi_io.inc"           // extern "C": setters and readers (in front of wgs_step: k_export_records keeps its place)
 #include "capi_lifecycle.inc"    // extern "C": create / destroy, wgs_step, wgs_sync
 #include "host_sharded.inc"      // RCCL binding and the phases of a sharded substep

@@ -420,6 +420,36 @@ __device__ inline void block_prefix(const Dev &d, uint32_t epoch, uint32_t id, i
     start = wait_tagged(&d.group_b[grp], epoch) + psum;
 }
 
+// A word of the output stage: the in-block cell from bit OUT_CELL_SHIFT up, below it (OUT_SRC_MASK) where the member comes from — a slot
+// of the buffer, or in the wave-parallel form an index v into the staged ids.
+constexpr uint32_t OUT_CELL_SHIFT = 26, OUT_SRC_MASK = 0x03ffffffu;
+
+constexpr int ARRC = 4;                      // arrivals of a cell kept in registers with their ids (the lane-by-lane form)
+constexpr int PAR_R = (RUNCAP + 63) / 64;    // rounds of 64 entries over a staged run
+// The three LDS stages of a regrouping wave, RUNCAP words each, and the arrays that live in them for a part of a block's regrouping.
+struct WaveStage {
+    uint32_t *s_in;    // the raw cell-id entries of the block's previous run: valid from the staging until pass 1 has read them
+    uint32_t *s_out;   // the block's new run (words of OUT_CELL_SHIFT / OUT_SRC_MASK): valid from the first place taken (pass 2) until perm / perm_cell are written
+    uint32_t *s_pid;   // the particle ids of the previous run, in the wave-parallel form the array arrivals' behind them at [runlen + lane]:
+                       // valid from the staging until the cells are in order
+    // -- wave-parallel form, per cell: members that stayed / that came. Valid from pass 1's zeroing until pass 1 has read them back
+    // (the output stage is not written before the counters are consumed)
+    __device__ uint32_t *cnt_stay() const { return s_out + RUNCAP - 64; }
+    __device__ uint32_t *cnt_new() const { return s_out + RUNCAP - 128; }
+    // -- wave-parallel form, per cell: first place of the stayers / of the newcomers; per lane: the slot of its array arrival. Valid from
+    // the places of pass 2 (the staged cell ids are consumed by then) until perm is written
+    __device__ uint32_t *place_stay() const { return s_in; }
+    __device__ uint32_t *arr_slot() const { return s_in + 64; }
+    __device__ uint32_t *place_new() const { return s_in + 128; }
+    // -- lane-by-lane form, per cell: a counter and ARRC (slot, id) pairs handed over by other cells' lanes. Valid from pass 1's zeroing
+    // until pass 1 has read them into registers (before pass 2 writes s_out)
+    __device__ uint32_t *hand_cnt() const { return s_out; }
+    __device__ uint32_t *hand_slot() const { return s_out + 64; }
+    __device__ uint32_t *hand_pid() const { return s_out + 64 + 64 * ARRC; }
+};
+static_assert(PAR_R % 2 == 0 && RUNCAP <= 1023, "two 16-bit (cell | place << 6) per register; 0xffff = none");
+static_assert(RUNCAP >= 64 + 2 * 64 * ARRC, "the hand-over arrays alias the output stage");
+
 // Per active block, one wave, lane = cell: neighbour links (replaces the per-thread hash lookups of
 // p2g.wgsl:238-275 / g2p.wgsl:72-132), the new cell runs (sort.wgsl:117-127 finalize_particles_sort, in canonical
 // order), reset of the accumulators.
@@ -440,6 +470,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     uint32_t epoch = epoch_of_launch;
     if constexpr (SUMM) asm volatile("" : "+s"(epoch));
     const float *in = d.buf[side];
+    const WaveStage st = {s_in, s_out, s_pid};
     // (the lane's part of every per-block index is pinned once per block: hipcc otherwise hoists array + 4 lane, one 64-bit pair per
     // array, out of the loop over the blocks, keeps the pairs in scratch for want of registers and reloads them — a scratch load and a
     // wait — in front of the block's first loads: the sort is a chain of dependent round trips, and that was one more)
@@ -534,7 +565,6 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     const bool par = old_ok && need_ids && in_lds && __ballot(head != 0u) == 0ull && runlen + narr_in <= (uint32_t)RUNCAP;   // (wave-uniform)
     // (two batches of PAR_R / 2 rounds, every load of a batch in flight before the first LDS store: a round at a time — one wait per
     // round — the staging of a full block was six to eight dependent round trips, 5 us of a dirty block's 16)
-    constexpr int PAR_R = (RUNCAP + 63) / 64;
     if (in_lds && need_ids) {
         const bool want_cells = !clean || par;   // (wave-uniform)
 #pragma unroll
@@ -669,18 +699,38 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
         cdf_cached = cdf_cached && near_moving == 0u;
         own_cached = own_cached && near_moving == 0u;
     }
-    if constexpr (!SUMM) {
-        if (cdf_cached) {
-            const bool any = cdf_class != 0u;
-            if (lane == 0 && any) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
-            listed = any;
-            pc_flag = any ? CELL_LISTED : 0u;
-        } else if (own_cached) {
-            // (nothing to do: its nodes are what they were, it holds no particle)
-        } else if (CDF WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_NO_BLOCK_CDF))) {
+    // The (BW+2)^D tile of a block = its own BW^D nodes + the first two layers of its "+" neighbours' — the same node is in the tiles of
+    // up to 2^D blocks, and a wave that evaluated its whole tile (six rounds of 64 nodes against every collider in reach — 10 us, the
+    // slowest waves of this launch wherever a collider MOVES: the reference's sand3) did 5.4 times the work there is. Every wave
+    // evaluates its OWN nodes, one round, and publishes what its "-" neighbours want to know of them — Dev::block_cdf_summ: per offset o,
+    // "some own node in the first BW+2-BW layers along the axes of o has an affinity" — under this substep's number; a particle-bearing
+    // block then reads its "+" neighbours' words. A word that does not come within a few microseconds (the neighbour's wave is not
+    // resident: more blocks than wave slots) is not waited for any longer: the wave evaluates that neighbour's part of its tile itself,
+    // as before — same loop, same code. The class is the same either way: an affinity bit of a node does not depend on whose reach mask
+    // it was evaluated under (a collider outside the mask gives no node of that tile an affinity).
+    // SUMM is chosen by the host where blocks ARE evaluated substep after substep — a collider moves, or nothing keeps (Dev::cdf_gen 0).
+    // With colliders at rest a block is evaluated once in its life and the words would serve nobody; that instantiation is the
+    // `!SUMM` branch below, which evaluates the whole tile: compiled into one kernel with it, this stage cost the launch 4 us of 57 at
+    // 16 M particles (registers). What the two share — the cached branch and the final note — stands once.
+    constexpr uint32_t SUMM_TAG = 0xffffffu;
+    auto publish_summ = [&](uint32_t bits) {
+        if (lane == 0) __hip_atomic_store(&d.block_cdf_summ[id], ((epoch & SUMM_TAG) << 8) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if (cdf_cached) {
+        const bool any = cdf_class != 0u;
+        if (lane == 0 && any) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
+        listed = any;
+        pc_flag = any ? CELL_LISTED : 0u;
+        if constexpr (SUMM) publish_summ(cdf_summ & 0xffu);   // (its nodes are what they were)
+    } else if (own_cached) {
+        // (nothing to do: its nodes are what they were, it holds no particle)
+        if constexpr (SUMM) publish_summ(cdf_summ & 0xffu);
+    } else if (CDF WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_NO_BLOCK_CDF))) {
+        const uint32_t near = reach_mask(0xffffu);  // bit i: collider i can reach a node of this tile
+        bool any = false;
+        if constexpr (!SUMM) {
             constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE;
             uint32_t mine = 0u;
-            const uint32_t near = reach_mask(0xffffu);  // bit i: collider i can reach a node of this tile
             if (near == 0u) {
                 // no collider in reach of the tile (nearly every block): its own 64 nodes get the "far" cdf — lane = node —
                 // and the rim, which belongs to the neighbours, is theirs to write
@@ -707,46 +757,10 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
                     mine |= c.affinities;
                 }
             }
-            const bool any = __ballot(mine != 0u) != 0ull;
-            if (lane == 0) {
-                d.block_cpic[id] = any ? 1u : 0u;
-                // (kept for the coming substeps only when no collider that moves is in reach)
-                if (d.cdf_gen != 0u) d.block_cdf_gen[id] = (near & d.cdf_moving) == 0u ? (d.cdf_gen | (bcount > 0u ? CDF_FULL : 0u)) : 0u;
-                if (any && bcount > 0u) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
-            }
-            listed = any && bcount > 0u;
-            pc_flag = any ? CELL_LISTED : 0u;
-        }
-    } else {
-        // The (BW+2)^D tile of a block = its own BW^D nodes + the first two layers of its "+" neighbours' — the same node is in the tiles of
-        // up to 2^D blocks, and a wave that evaluated its whole tile (six rounds of 64 nodes against every collider in reach — 10 us, the
-        // slowest waves of this launch wherever a collider MOVES: the reference's sand3) did 5.4 times the work there is. Every wave
-        // evaluates its OWN nodes, one round, and publishes what its "-" neighbours want to know of them — Dev::block_cdf_summ: per offset o,
-        // "some own node in the first BW+2-BW layers along the axes of o has an affinity" — under this substep's number; a particle-bearing
-        // block then reads its "+" neighbours' words. A word that does not come within a few microseconds (the neighbour's wave is not
-        // resident: more blocks than wave slots) is not waited for any longer: the wave evaluates that neighbour's part of its tile itself,
-        // as before — same loop, same code. The class is the same either way: an affinity bit of a node does not depend on whose reach mask
-        // it was evaluated under (a collider outside the mask gives no node of that tile an affinity).
-        // SUMM is chosen by the host where blocks ARE evaluated substep after substep — a collider moves, or nothing keeps (Dev::cdf_gen 0).
-        // With colliders at rest a block is evaluated once in its life and the words would serve nobody; that instantiation is the code
-        // above, untouched: compiled into one kernel with it, this stage cost the launch 4 us of 57 at 16 M particles (registers).
-        constexpr uint32_t SUMM_TAG = 0xffffffu;
-        auto publish_summ = [&](uint32_t bits) {
-            if (lane == 0) __hip_atomic_store(&d.block_cdf_summ[id], ((epoch & SUMM_TAG) << 8) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        if (cdf_cached) {
-            const bool any = cdf_class != 0u;
-            if (lane == 0 && any) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
-            listed = any;
-            pc_flag = any ? CELL_LISTED : 0u;
-            publish_summ(cdf_summ & 0xffu);   // (its nodes are what they were)
-        } else if (own_cached) {
-            publish_summ(cdf_summ & 0xffu);   // (nothing else to do: its nodes are what they were, it holds no particle)
-        } else if (CDF WGS_ABLATE_AND(!(d.dbg & DBG_ABLATE_NO_BLOCK_CDF))) {
+            any = __ballot(mine != 0u) != 0ull;
+        } else {
             constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE;
             constexpr int ROUNDS = (TILE + 63) / 64;
-            const uint32_t near = reach_mask(0xffffu);  // bit i: collider i can reach a node of this tile
-            bool any = false;
             if (near == 0u) {
                 // no collider in reach of the tile (nearly every block): its own 64 nodes get the "far" cdf — lane = node —
                 // and the rim, which belongs to the neighbours, is theirs to write
@@ -809,15 +823,15 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
                 }
                 if (parts != 0u) any = __ballot(mine != 0u) != 0ull;   // (the fallback ran)
             }
-            if (lane == 0) {
-                d.block_cpic[id] = any ? 1u : 0u;
-                // (kept for the coming substeps only when no collider that moves is in reach)
-                if (d.cdf_gen != 0u) d.block_cdf_gen[id] = (near & d.cdf_moving) == 0u ? (d.cdf_gen | (bcount > 0u ? CDF_FULL : 0u)) : 0u;
-                if (any && bcount > 0u) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
-            }
-            listed = any && bcount > 0u;
-            pc_flag = any ? CELL_LISTED : 0u;
         }
+        if (lane == 0) {
+            d.block_cpic[id] = any ? 1u : 0u;
+            // (kept for the coming substeps only when no collider that moves is in reach)
+            if (d.cdf_gen != 0u) d.block_cdf_gen[id] = (near & d.cdf_moving) == 0u ? (d.cdf_gen | (bcount > 0u ? CDF_FULL : 0u)) : 0u;
+            if (any && bcount > 0u) d.cpic_list[(size_t)(id & 7u) * d.cap + atomicAdd(&d.counters[ctr_ncpic(id & 7u, epoch)], 1u)] = id;
+        }
+        listed = any && bcount > 0u;
+        pc_flag = any ? CELL_LISTED : 0u;
     }
     WGS_PROF(3)
     // ---- pass 1: members of the new run = stayers of the previous run + arrivals. Arrivals from OTHER blocks are on the
@@ -825,19 +839,17 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     // its old cell meets it here, in its own range of the previous run, and hands it to its new cell through LDS (a
     // counter and ARRC slots per cell; LDS atomics: the order of the slots is arbitrary, they are sorted by id below).
     // The first ARRC arrivals of a cell are kept in registers with their ids.
-    constexpr int ARRC = 4;
     uint32_t a_slot[ARRC], a_pid[ARRC];
 #pragma unroll
     for (int k = 0; k < ARRC; k++) { a_slot[k] = NONE; a_pid[k] = NONE; }
     uint32_t n_stay = ce_old - cs_old, n_arr = 0, n_in = 0;
     // -- the wave-parallel form: lane = entry of the previous run (strided). Every particle that names a cell of this block takes a
     // place in that cell (an LDS counter per cell: the order of arrival is arbitrary, the ids are put in order further down).
-    static_assert(PAR_R % 2 == 0 && RUNCAP <= 1023, "two 16-bit (cell | place << 6) per register; 0xffff = none");
     uint32_t ckp[PAR_R / 2];  // per entry t = lane + 64 r: new cell | place in it << 6 in half r & 1 of word r / 2, 0xffff = not this block's
     uint32_t a_ck = NONE;     // ... of the lane's entry of the array of arrivals from other blocks
     // (two counters per cell: the particles that did NOT change cell — they come in the order of the cell's previous run, ascending ids —
     // take the first places, the others the places behind them: the ordering pass below then only has the newcomers to move)
-    uint32_t *s_cnt = s_out + RUNCAP - 64, *s_cnt2 = s_out + RUNCAP - 128;   // (the output stage is not written before the counters are consumed)
+    uint32_t *s_cnt = st.cnt_stay(), *s_cnt2 = st.cnt_new();
     uint32_t par_new = 0u;    // bit r: entry lane + 64 r changed cell (its place counts from behind the stayers of its new cell)
     uint32_t par_nst = 0u;    // lane = cell: members of the new run that stayed
     if (par) {
@@ -864,8 +876,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
         n_stay = par_nst + __hip_atomic_load(&s_cnt2[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (all members of the cell's new run)
         n_arr = 0;
     } else {
-        static_assert(RUNCAP >= 64 + 2 * 64 * ARRC, "the hand-over arrays alias the output stage");
-        uint32_t *s_acnt = s_out, *s_aslot = s_out + 64, *s_apid = s_out + 64 + 64 * ARRC;   // (aliases: read into registers before pass 2 writes s_out)
+        uint32_t *s_acnt = st.hand_cnt(), *s_aslot = st.hand_slot(), *s_apid = st.hand_pid();
         auto hand_over = [&](uint32_t c, uint32_t slot, uint32_t pid) {   // to cell c of this block
             const uint32_t k = __hip_atomic_fetch_add(&s_acnt[c & 63u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             if (k < (uint32_t)ARRC) {
@@ -935,10 +946,10 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
         if (out_lds) fetch_bstart();
         keep_perm = bstart == bstart_old && ident == (((epoch - 1u) << 1) | (pc_flag != 0u ? 1u : 0u));
     }
-    uint32_t *s_lst = s_in, *s_av = s_in + 64, *s_new = s_in + 128;   // (wave-parallel form: the staged cell ids are consumed by now)
+    uint32_t *s_lst = st.place_stay(), *s_av = st.arr_slot(), *s_new = st.place_new();
     if (par) {
         // (places) the cell's start + the place taken in it — behind the cell's stayers for a newcomer; an entry of the output stage =
-        // cell << 26 | index v into the ids: v < runlen: entry v of the previous run, else entry v - runlen of the array of arrivals
+        // cell << OUT_CELL_SHIFT | index v into the ids: v < runlen: entry v of the previous run, else entry v - runlen of the array of arrivals
         __hip_atomic_store(&s_lst[lane], lstart, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __hip_atomic_store(&s_new[lane], lstart + par_nst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         if (a_ck != NONE) {
@@ -950,12 +961,12 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             const uint32_t ck = (ckp[r / 2] >> (16 * (r & 1))) & 0xffffu;
             if (ck != 0xffffu) {
                 const uint32_t pos = __hip_atomic_load(((par_new >> r) & 1u) ? &s_new[ck & 63u] : &s_lst[ck & 63u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + (ck >> 6);
-                __hip_atomic_store(&s_out[pos], ((ck & 63u) << 26) | ((uint32_t)lane + 64u * (uint32_t)r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                __hip_atomic_store(&s_out[pos], ((ck & 63u) << OUT_CELL_SHIFT) | ((uint32_t)lane + 64u * (uint32_t)r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
         }
         if (a_ck != NONE) {
             const uint32_t pos = __hip_atomic_load(&s_new[a_ck & 63u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + (a_ck >> 6);
-            __hip_atomic_store(&s_out[pos], ((a_ck & 63u) << 26) | (runlen + (uint32_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_store(&s_out[pos], ((a_ck & 63u) << OUT_CELL_SHIFT) | (runlen + (uint32_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         // (order) lane = cell: its members by ascending (id, v). The stayers hold the first places in the order of the previous run —
         // ascending ids, checked in one pipelined pass —, the newcomers the places behind them. With up to NEWC newcomers (nearly
@@ -966,7 +977,6 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
         // block's 26 us). Any other case — more newcomers, stayers not in order — takes the insertion sort below, which is correct
         // for any order of the places.
         constexpr int NEWC = 4;
-        constexpr uint32_t VM = 0x03ffffffu;
         // (plain LDS accesses in this pass: a lane touches the range of its own cell only — what other lanes wrote there, they wrote with
         // the atomic stores above, which a load of a possibly aliasing address is not moved across —, so the loads of a batch can
         // be issued together)
@@ -976,7 +986,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             uint32_t pk = 0u, pv = 0u;
 #pragma unroll 4
             for (uint32_t m = 0; m < par_nst; m++) {
-                const uint32_t v = lds(&s_out[lstart + m]) & VM, k = lds(&s_pid[v]);
+                const uint32_t v = lds(&s_out[lstart + m]) & OUT_SRC_MASK, k = lds(&s_pid[v]);
                 ordered = ordered && (m == 0u || pk < k || (pk == k && pv < v));
                 pk = k;
                 pv = v;
@@ -991,7 +1001,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             for (int k = 0; k < NEWC; k++) {
                 nk[k] = nv[k] = NONE;   // (empty entries sort last)
                 if ((uint32_t)k < n_new) {
-                    nv[k] = lds(&s_out[lstart + par_nst + (uint32_t)k]) & VM;
+                    nv[k] = lds(&s_out[lstart + par_nst + (uint32_t)k]) & OUT_SRC_MASK;
                     nk[k] = lds(&s_pid[nv[k]]);
                 }
             }
@@ -1014,7 +1024,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
 #pragma unroll
                 for (int k = 0; k < NEWC; k++) {
                     mid[k] = (lo[k] + hi[k]) >> 1;
-                    mv[k] = lo[k] < hi[k] ? (lds(&s_out[lstart + mid[k]]) & VM) : 0u;
+                    mv[k] = lo[k] < hi[k] ? (lds(&s_out[lstart + mid[k]]) & OUT_SRC_MASK) : 0u;
                 }
 #pragma unroll
                 for (int k = 0; k < NEWC; k++) mk[k] = lo[k] < hi[k] ? lds(&s_pid[mv[k]]) : 0u;
@@ -1040,16 +1050,16 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
 #pragma unroll
             for (int k = 0; k < NEWC; k++)
                 if ((uint32_t)k < n_new)
-                    s_out[lstart + rk[k] + (uint32_t)k] = ((uint32_t)lane << 26) | nv[k];
+                    s_out[lstart + rk[k] + (uint32_t)k] = ((uint32_t)lane << OUT_CELL_SHIFT) | nv[k];
         }
         uint32_t kprev = 0u, vprev = 0u;
         if (!quick && total > 1u) {
-            vprev = __hip_atomic_load(&s_out[lstart], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) & 0x03ffffffu;
+            vprev = __hip_atomic_load(&s_out[lstart], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) & OUT_SRC_MASK;
             kprev = __hip_atomic_load(&s_pid[vprev], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         for (uint32_t m = 1; m < (quick ? 0u : total); m++) {   // (the insertion sort: cells the quick form above does not cover)
             const uint32_t e = __hip_atomic_load(&s_out[lstart + m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            const uint32_t ve = e & 0x03ffffffu, ke = __hip_atomic_load(&s_pid[ve], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            const uint32_t ve = e & OUT_SRC_MASK, ke = __hip_atomic_load(&s_pid[ve], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             if (kprev < ke || (kprev == ke && vprev < ve)) {   // in order behind the member before it (which stays the last one so far)
                 kprev = ke;
                 vprev = ve;
@@ -1059,7 +1069,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
             uint32_t j = m;
             while (j > 0u) {
                 const uint32_t q = __hip_atomic_load(&s_out[lstart + j - 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                const uint32_t vq = q & 0x03ffffffu, kq = __hip_atomic_load(&s_pid[vq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                const uint32_t vq = q & OUT_SRC_MASK, kq = __hip_atomic_load(&s_pid[vq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 if (kq < ke || (kq == ke && vq < ve)) break;
                 __hip_atomic_store(&s_out[lstart + j], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 j--;
@@ -1070,7 +1080,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     uint32_t out = lstart;
     auto emit = [&](uint32_t src) {
         if (out_lds) {
-            __hip_atomic_store(&s_out[out], ((uint32_t)lane << 26) | src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_store(&s_out[out], ((uint32_t)lane << OUT_CELL_SHIFT) | src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         } else {
             d.perm[bstart + out] = src;
             d.perm_cell[bstart + out] = idx | pc_flag;
@@ -1191,7 +1201,7 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
         uint32_t rank = 0u;
         for (uint32_t m = 0; m < c_total; m++) rank += __shfl(key, (int)m) < key ? 1u : 0u;
         if ((uint32_t)lane < c_total)
-            __hip_atomic_store(&s_out[c_lstart + rank], ((uint32_t)c << 26) | (uint32_t)key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_store(&s_out[c_lstart + rank], ((uint32_t)c << OUT_CELL_SHIFT) | (uint32_t)key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     WGS_PROF(4)
     if (out_lds && !fast_clean) fetch_bstart();
@@ -1199,10 +1209,10 @@ __device__ __forceinline__ uint32_t regroup_block(const Dev &d, int side, uint32
     if (out_lds && !keep_perm)
         for (uint32_t t = lane; t < btotal; t += 64) {
             const uint32_t v = __hip_atomic_load(&s_out[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            uint32_t src = v & 0x03ffffffu;
+            uint32_t src = v & OUT_SRC_MASK;
             if (par) src = src < runlen ? run0 + src : __hip_atomic_load(&s_av[src - runlen], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             d.perm[bstart + t] = src;
-            d.perm_cell[bstart + t] = (id * NPB + (v >> 26)) | pc_flag;
+            d.perm_cell[bstart + t] = (id * NPB + (v >> OUT_CELL_SHIFT)) | pc_flag;
         }
     // ---- new runs, reset of what this substep consumed
     d.cell_start[idx] = bstart + lstart;
