@@ -217,7 +217,9 @@ const char *wgs_build_info(void);
  * libraries of version 7 detects wgs_set_fluid_eos by symbol lookup. Still 7: WGS_MODEL_PER_PARTICLE, wgs_set_particle_models and
  * wgs_read_particle_models were added the same way (new symbols and a macro only; wgs_diagnostics.model may now read 3) — detect
  * wgs_set_particle_models by symbol lookup. Still 7: wgs_grid_sample, wgs_sample_grid[_device] and wgs_read_grid_window[_device] were
- * added the same way (one new struct and four new symbols) — detect wgs_sample_grid by symbol lookup. */
+ * added the same way (one new struct and four new symbols) — detect wgs_sample_grid by symbol lookup. Still 7: wgs_particle_field and
+ * wgs_read_particle_fields[_device] were added the same way (one new struct and two new symbols) —
+ * detect wgs_read_particle_fields by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -544,6 +546,47 @@ typedef struct {
 } wgs_diagnostics;
 wgs_status wgs_read_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *out);
 wgs_status wgs_enqueue_diagnostics(wgs_data *data, uint32_t what, wgs_diagnostics *device_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Lagrangian field output. NEW: the reference has no counterpart (its host maps `positions` only; stress never leaves
+ * src/solver/particle_update.wgsl). What an MPM user looks at first — the stress a particle carries and how far it is strained — is
+ * evaluated on the device from the particle's stored state, without 188 bytes per particle over PCIe, a host SVD and a restatement of
+ * the constitutive formulae that would not round like the step.
+ *
+ * Same stress as the step. `stress` is what the step's own functions return for the stored def_grad and the particle's own lambda, mu:
+ * a fresh SVD of the stored F, then the corotated (src/models/linear_elasticity.wgsl:14-41) or neo-Hookean
+ * (src/models/neo_hookean_elasticity.wgsl:12-25) Kirchhoff stress, the very device functions the particle update calls. For data
+ * without plastic state it is therefore bit for bit the tau the next substep would apply if the velocity gradient were zero. For
+ * Drucker-Prager data F is the stored (projected) elastic part; the step reuses the SVD its projection maintained, so the two agree to
+ * rounding, not to the bit.
+ * Fluid, pressure part only. The stress of a WGS_MODEL_FLUID particle is the fluid update with a zero gradient, -Jc p I (Jc, p: WGS_MODEL_FLUID
+ * above). The viscous part Jc mu (G + G^T) needs the velocity gradient, which a particle does not store: take it from
+ * wgs_sample_grid at the particle positions (velocity_gradient) where it is wanted.
+ * Kirchhoff, not Cauchy. Cauchy stress is stress / volume_ratio; the division is left to the caller because J may be zero or negative for
+ * an inverted element.
+ * The invariants come from the record: mean_stress and von_mises are fp32 functions of the record's own `stress` in one order — the
+ * diagonal summed k = 0 .. DIM-1 and divided by DIM; the deviator's entries squared and summed in storage order, times 3/2, square root
+ * (the entries are scaled by the power of two of the largest one first and the root scaled back, which is exact: a stress of 1e20 has
+ * no fp32 square).
+ *
+ * No state is written: a step that never calls these launches exactly what it launched before, and no device memory is kept between
+ * calls (wgs_stats.device_bytes does not change). Valid at any time, also before the first substep. Records are in the caller's order
+ * (record i = particle i of wgs_data_create), wgs_stats.num_particles of them. wgs_read_particle_fields blocks, like wgs_read_particles;
+ * the _device form takes a DEVICE pointer aligned to 16 bytes (2D: 8; whatever hipMalloc returns is), is stream-ordered on the data's
+ * stream and returns at once, like wgs_prep_vertex_buffer_device. Sharded data (wgs_data_create_sharded) -> WGS_ERR_UNSUPPORTED, like
+ * wgs_get_device_ptrs. A NULL argument, or a device pointer off that alignment -> WGS_ERR_INVALID_ARGUMENT and nothing is written. */
+typedef struct {
+    float stress[WGS_DIM * WGS_DIM]; /* Kirchhoff stress tau of the particle's stored state, column-major like `affine` */
+    float mean_stress;               /* tr(stress) / DIM */
+    float von_mises;                 /* sqrt(3/2) * |stress - mean_stress * I|_F, in the library's dimension */
+    float volume_ratio;              /* J: mat_det(def_grad) as the step takes it; fluid: def_grad[0] */
+    float stretch[WGS_DIM];          /* signed singular values of def_grad from the step's svd, in the order it returns them;
+                                        fluid: cbrt(J) (2D: sqrt(J)) in every entry, what wgs_prep_vertex_buffer draws */
+    uint32_t model;                  /* the model the stress was evaluated under: 0, 1 or 2 (the particle's own where a table is set) */
+} wgs_particle_field;                /* 16 words in 3D, 10 in 2D */
+/* out: n records, caller's order. */
+wgs_status wgs_read_particle_fields(wgs_data *data, wgs_particle_field *out);
+wgs_status wgs_read_particle_fields_device(wgs_data *data, wgs_particle_field *device_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Eulerian field output. NEW: the reference has no counterpart (its grid never leaves the device, src/grid/grid.rs; wgs_read_grid above

@@ -180,6 +180,15 @@ class MpmData {
         check(wgs_read_diagnostics(h_, what, &r));
         return r;
     }
+    // Lagrangian field output (no reference counterpart): Kirchhoff stress, its invariants, the volume ratio and the stretches of every
+    // particle's stored state, evaluated on the device with the step's own functions; records in the caller's order. The host form
+    // blocks; the _device form takes a DEVICE pointer (16-byte aligned), is stream-ordered on the data's stream and returns at once.
+    std::vector<wgs_particle_field> particle_fields() {
+        std::vector<wgs_particle_field> out(n_);
+        if (n_) check(wgs_read_particle_fields(h_, out.data()));
+        return out;
+    }
+    void particle_fields_device(wgs_particle_field *device_out) { check(wgs_read_particle_fields_device(h_, device_out)); }
     // Eulerian field output (no reference counterpart): the grid of the last substep sampled at points (n * WGS_DIM floats) and a
     // dense window of its nodes (WGS_DIM + 1 floats per node, x fastest). The host forms block; the _device forms take DEVICE pointers,
     // are stream-ordered on the data's stream and return at once.

@@ -207,6 +207,18 @@ pub struct wgs_grid_sample {
     pub active_nodes: u32,
 }
 
+/// Stress and strain of one particle's stored state (include/wgsparkl_hip.h "Lagrangian field output"): 16 words in 3D, 10 in 2D.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_particle_field {
+    pub stress: [f32; DIM * DIM], // Kirchhoff stress, column-major like `affine`
+    pub mean_stress: f32,
+    pub von_mises: f32,
+    pub volume_ratio: f32,
+    pub stretch: [f32; DIM],
+    pub model: u32,
+}
+
 #[repr(C)]
 pub struct wgs_comm {
     _private: [u8; 0],
@@ -266,6 +278,11 @@ extern "C" {
     /// reproducible sums, bounds and state digest, reduced on the device; blocking / stream-ordered into DEVICE memory
     pub fn wgs_read_diagnostics(d: *mut wgs_data, what: u32, out: *mut wgs_diagnostics) -> wgs_status;
     pub fn wgs_enqueue_diagnostics(d: *mut wgs_data, what: u32, device_out: *mut wgs_diagnostics) -> wgs_status;
+    /// per-particle Kirchhoff stress, invariants, volume ratio and stretches of the stored state, num_particles records in the caller's
+    /// order; the _device form takes a DEVICE pointer (16-byte aligned), is stream-ordered and returns at once. Detect by symbol lookup
+    /// on older libraries.
+    pub fn wgs_read_particle_fields(d: *mut wgs_data, out: *mut wgs_particle_field) -> wgs_status;
+    pub fn wgs_read_particle_fields_device(d: *mut wgs_data, device_out: *mut wgs_particle_field) -> wgs_status;
     /// the grid of the last substep sampled at `n` points (n * DIM floats) / a dense window of its nodes (DIM + 1 floats per node);
     /// the _device forms take DEVICE pointers, are stream-ordered and return at once. Detect by symbol lookup on older libraries.
     pub fn wgs_sample_grid(d: *mut wgs_data, points: *const f32, n: usize, out: *mut wgs_grid_sample) -> wgs_status;

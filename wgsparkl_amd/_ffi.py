@@ -94,10 +94,13 @@ def make_types(D: int):
     class GridSample(C.Structure):
         _fields_ = [("velocity", f * D), ("velocity_gradient", f * (D * D)), ("density", f), ("active_nodes", u)]
 
+    class ParticleField(C.Structure):
+        _fields_ = [("stress", f * (D * D)), ("mean_stress", f), ("von_mises", f), ("volume_ratio", f), ("stretch", f * D), ("model", u)]
+
     ns = dict(SimParams=SimParams, Elastic=Elastic, DruckerPrager=DruckerPrager, PlasticState=PlasticState,
               Phase=Phase, Cdf=Cdf, Dynamics=Dynamics, Particle=Particle, Pose=Pose, Velocity=Velocity,
               Collider=Collider, MassProperties=MassProperties, NodeRecord=NodeRecord, BlockRecord=BlockRecord, Stats=Stats,
-              GridSample=GridSample)
+              GridSample=GridSample, ParticleField=ParticleField)
     return type("Types", (), ns)
 
 
@@ -184,6 +187,9 @@ def prototypes(T):
         # device-side diagnostics (reproducible sums, bounds, state digest; no reference counterpart)
         "wgs_read_diagnostics": (st, [vp, u32, P(Diagnostics)]),
         "wgs_enqueue_diagnostics": (st, [vp, u32, vp]),
+        # Lagrangian field output (per-particle stress and strain of the stored state; no reference counterpart)
+        "wgs_read_particle_fields": (st, [vp, P(T.ParticleField)]),
+        "wgs_read_particle_fields_device": (st, [vp, vp]),
         # Eulerian field output (the grid sampled at points, a dense window of its nodes; no reference counterpart)
         "wgs_sample_grid": (st, [vp, fp, size, P(T.GridSample)]),
         "wgs_sample_grid_device": (st, [vp, vp, size, vp]),

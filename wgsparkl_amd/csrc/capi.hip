@@ -49,3 +49,5 @@ using namespace wgs;
 #include "kernels_models.h"      // per-particle models: the kernels of wgs_set_particle_models / wgs_read_particle_models (behind it, likewise)
 #include "kernels_probe.h"       // Eulerian field output: the sampler and the window scatter (behind them, likewise) ...
 #include "capi_probe.inc"        // ... extern "C": wgs_sample_grid[_device], wgs_read_grid_window[_device]
+#include "kernels_fields.h"      // Lagrangian field output: per-particle stress and strain (behind them, likewise) ...
+#include "capi_fields.inc"       // ... extern "C": wgs_read_particle_fields[_device]

@@ -91,6 +91,28 @@ def grid_samples_from_words(words: np.ndarray, dim: int) -> GridSamples:
                        density=fl[:, D + D * D].copy(), active_nodes=words[:, D + D * D + 1].copy(), raw=words)
 
 
+@dataclass
+class ParticleFields:
+    """`wgs_particle_field` records as numpy (include/wgsparkl_hip.h "Lagrangian field output"), one row per particle in the
+    caller's order."""
+    stress: np.ndarray         # [n, D, D] (row, col): Kirchhoff stress of the stored state
+    mean_stress: np.ndarray    # [n]: tr(stress) / D
+    von_mises: np.ndarray      # [n]: sqrt(3/2) |dev stress|_F
+    volume_ratio: np.ndarray   # [n]: J
+    stretch: np.ndarray        # [n, D]: signed singular values of def_grad (fluid: cbrt / sqrt of J)
+    model: np.ndarray          # [n] uint32: the model the stress was evaluated under
+    raw: np.ndarray            # [n, D*D + D + 4] uint32: the records themselves
+
+
+def particle_fields_from_words(words: np.ndarray, dim: int) -> ParticleFields:
+    """`words`: [n, D*D + D + 4] uint32, the records as the library wrote them (the stress is column-major there)."""
+    D, DD = dim, dim * dim
+    fl = words.view(F32)
+    return ParticleFields(stress=fl[:, :DD].reshape(-1, D, D).transpose(0, 2, 1).copy(), mean_stress=fl[:, DD].copy(),
+                          von_mises=fl[:, DD + 1].copy(), volume_ratio=fl[:, DD + 2].copy(), stretch=fl[:, DD + 3:DD + 3 + D].copy(),
+                          model=words[:, DD + 3 + D].copy(), raw=words)
+
+
 def diagnostics_from_struct(r, dim: int) -> Diagnostics:
     ncomp = dict(momentum=dim, mass_moment=dim, grid_momentum=dim, angular=1 if dim == 2 else 3, grid_angular=1 if dim == 2 else 3)
     sums = {}
@@ -500,6 +522,19 @@ class MpmData(DataHandle):
         order = np.lexsort(vid.T[::-1]) if m else np.zeros(0, np.int64)
         u = raw.view(np.uint32)
         return vid[order], u[:, D][order].copy(), u[:, D + 1][order].copy(), ids[:self.n]
+
+    # -- Lagrangian field output: stress and strain of every particle's stored state, evaluated on the device
+    def particle_fields(self) -> ParticleFields:
+        """`wgs_read_particle_fields`: Kirchhoff stress, mean stress, von Mises stress, volume ratio, stretches and model of every
+        particle, in the caller's order, with the step's own constitutive functions. Blocking; writes no state."""
+        words = np.zeros((self.n, C.sizeof(self.T.ParticleField) // 4), np.uint32)
+        _ffi.check(self.lib, self.lib.wgs_read_particle_fields(self._h, words.ctypes.data_as(C.POINTER(self.T.ParticleField))))
+        return particle_fields_from_words(words, self.dim)
+
+    def particle_fields_device(self, out_ptr: int):
+        """`wgs_read_particle_fields_device`: the same into DEVICE memory (`out_ptr`: n records of `ctypes.sizeof(T.ParticleField)`
+        bytes, aligned to 16 bytes), stream-ordered on the data's stream. Returns at once."""
+        _ffi.check(self.lib, self.lib.wgs_read_particle_fields_device(self._h, C.c_void_p(int(out_ptr))))
 
     # -- Eulerian field output: the grid of the last substep at arbitrary points, and a dense window of its nodes
     def sample_grid(self, points) -> GridSamples:
