@@ -258,13 +258,14 @@ def _export_records(shard):
 
 def _export_cdf(shard, rec=None):
     """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds"""
+    from wgsparkl_amd.sharded import record_quad
     D = shard.dim
     rec = _export_records(shard) if rec is None else rec
     ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
-    q = lambda k: rec[:, 4 * k:4 * k + 4]
+    q = lambda name: record_quad(rec, D, name)
     if D == 3:
-        return ids, q(0)[:, :3].copy(), q(11)[:, 3].copy().view(np.uint32), q(10)[:, 3].copy(), q(10)[:, :3].copy(), stamp
-    return ids, q(0)[:, :2].copy(), q(7)[:, 3].copy().view(np.uint32), q(7)[:, 2].copy(), q(7)[:, :2].copy(), stamp
+        return ids, q("XM")[:, :3].copy(), q("CDF1")[:, 3].copy().view(np.uint32), q("CDF0")[:, 3].copy(), q("CDF0")[:, :3].copy(), stamp
+    return ids, q("XM")[:, :2].copy(), q("CDF0")[:, 3].copy().view(np.uint32), q("CDF0")[:, 2].copy(), q("CDF0")[:, :2].copy(), stamp
 
 
 def _export_all(shards, n, d, recs=None):

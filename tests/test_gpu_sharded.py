@@ -463,3 +463,46 @@ def test_single_domain_data_and_a_lone_slab_answer_alike(hip_libs, dim):
     slab.step(2)
     moved = alike("after two substeps")
     assert not np.array_equal(moved["translation"], start["translation"]), "the ball must have moved"
+
+
+def test_a_refused_lockstep_call_leaves_the_slabs_usable(hip_libs):
+    """wgs_sharded_step_lockstep lends every slab slab 0's stream for the length of the call; a call it refuses must hand every
+    slab its own stream back. Two pairs of slabs of one small 2D block under a resting ball: on the first pair only slab 0 is
+    given the ball's mass, so the call is refused (two-way coupling on some slabs); then slab 1 gets the same mass and the pair
+    runs three lockstep substeps. The second pair had the mass on both slabs from the start and runs the same three: the two
+    pairs hold the same particles and bodies, bit for bit."""
+    from wgsparkl_amd._ffi import WgsError
+    from wgsparkl_amd.sharded import native_lockstep
+    from gpu_common import export_state_and_cdf
+    sc = scenes.elastic_block_2d(nx=24, ny=16, with_floor=False)          # 384 particles, cells 7..19 x 7..15
+    ball = Collider.ball(1.5, (13.0, 16.0))                               # at rest, overlapping the block's top: not moving until it has a mass
+    heavy = ball.with_density(500.0, 2)
+    ps = sc["particles"]
+    pipe = pipeline(2)
+    first, _ = _native_slabs({**sc, "colliders": [ball]}, 2, pipe)
+    second, _ = _native_slabs({**sc, "colliders": [heavy]}, 2, pipe)
+    assert min(s.num_particles() for s in first) > 0
+
+    first[0].set_body_mass_properties([heavy])
+    with pytest.raises(WgsError) as e:
+        native_lockstep(pipe, first, 3)
+    assert "two-way coupling must be enabled on every slab or none" in str(e.value)
+    for s in first:
+        s.sync()                                                          # (each on its own stream again)
+    first[1].set_body_mass_properties([heavy])
+
+    for pair in (first, second):
+        native_lockstep(pipe, pair, 3)
+        for s in pair:
+            s.sync()
+    a, b = export_state_and_cdf(first, ps.n, 2), export_state_and_cdf(second, ps.n, 2)
+    for f in a[0]:
+        assert np.array_equal(a[0][f].view(np.uint32), b[0][f].view(np.uint32)), f
+    assert np.array_equal(a[1], b[1]), "the same slab holds each particle"
+    for k, name in ((2, "cdf_affinity"), (3, "cdf_dist"), (4, "cdf_normal")):
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), name
+    for r in range(2):
+        pa, pb = first[r].read_body_poses(), second[r].read_body_poses()
+        for key in pa[0]:
+            assert np.array_equal(pa[0][key], pb[0][key]), (r, key)
+    assert first[0].read_body_poses()[0]["linvel"][1] != 0.0, "the ball has a mass now: gravity and the block move it"

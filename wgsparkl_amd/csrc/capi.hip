@@ -23,6 +23,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernels_bodies.h"
@@ -35,14 +36,14 @@
 
 using namespace wgs;
 
-#include "host_state.h"          // error reporting, the handle structs, who owns device memory
+#include "host_state.h"          // error reporting, the handle structs, the owners of device and pinned memory, events, the stream
 #include "host_grid.inc"         // the arrays sized by the block capacity, growth, the host's looks at the counters
 #include "kernels_readback.h"    // device code of the readers and of the checkpoint / render hand-off
 #include "host_substep.inc"      // launch ladders, launch plans, the stages of a substep (begin_substep ... enqueue_finish)
 #include "capi_io.inc"           // extern "C": setters and readers (in front of wgs_step: k_export_records keeps its place)
-#include "capi_lifecycle.inc"    // extern "C": create / destroy, wgs_step, wgs_sync
+#include "capi_lifecycle.inc"    // the stages of data creation (create_impl drives them); extern "C": create / destroy, wgs_step, wgs_sync
 #include "host_sharded.inc"      // RCCL binding and the phases of a sharded substep
-#include "capi_sharded.inc"      // extern "C": communicators, wgs_shard_attach, the sharded steps
+#include "capi_sharded.inc"      // the loan of a lockstep group's streams; extern "C": communicators, wgs_shard_attach, the sharded steps
 #include "kernels_diag.h"        // device-side diagnostics and their launch sequence
 #include "capi_debug.inc"        // extern "C": diagnostics, test hooks, WGS_ABLATE profile readers
 #include "kernels_fluid.h"       // WGS_MODEL_FLUID: the kernel of the model switch (last: nothing that existed changes its place)

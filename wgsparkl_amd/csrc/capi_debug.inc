@@ -11,10 +11,10 @@ wgs_status wgs_enqueue_diagnostics(wgs_data *d, uint32_t what, wgs_diagnostics *
 wgs_status wgs_read_diagnostics(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     WGS_TRY(enter(d, out != nullptr));
     if (!d->diag_out) WGS_TRY(dev_alloc(d, &d->diag_out, 1));
-    if (!d->diag_host) HIP_TRY(hipHostMalloc((void **)&d->diag_host, sizeof(wgs_diagnostics), hipHostMallocDefault));
+    if (!d->diag_host) WGS_TRY(d->diag_host.alloc(1));
     WGS_TRY(diag_enqueue(d, what, d->diag_out));
-    WGS_TRY(download(d, d->diag_host, d->diag_out, sizeof(wgs_diagnostics)));
-    memcpy(out, d->diag_host, sizeof(wgs_diagnostics));
+    WGS_TRY(download(d, d->diag_host.get(), d->diag_out, sizeof(wgs_diagnostics)));
+    memcpy(out, d->diag_host.get(), sizeof(wgs_diagnostics));
     return WGS_OK;
 }
 

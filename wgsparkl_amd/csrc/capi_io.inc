@@ -2,7 +2,8 @@
 // (mesh) particles, plastic state; particles, positions, grid, blocks, body poses, the vertex buffer, device pointers,
 // timings and stats. Every reader that needs a staging buffer takes a Scratch and ends in download(); the kernels they
 // launch are in kernels_readback.h / kernels_shard.h. In front: the host rules several entry points share (fill_sim_params,
-// cdf_live, "this collider moves": colliders_move), create_impl of capi_lifecycle.inc among their users.
+// cdf_live, "this collider moves": colliders_move; the one list of the rigid-particle buffers: rigid_arrays), the stages of
+// capi_lifecycle.inc's create_impl among their users.
 
 namespace {
 __global__ void k_fluid_collapse(Dev d, int side);   // kernels_fluid.h (defined behind every other kernel: capi.hip on placement)
@@ -15,10 +16,8 @@ wgs_status drop_particle_models(wgs_data *d) {
     if (!d->dev.pmodel[0]) return WGS_OK;
     WGS_TRY(enter(d));
     HIP_TRY(hipStreamSynchronize(d->stream));
-    for (int s = 0; s < 2; s++) {
-        d->mem.release(d->dev.pmodel[s]);
-        d->dev.pmodel[s] = nullptr;
-    }
+    d->mem.release_group(MemGroup::models);
+    d->dev.pmodel[0] = d->dev.pmodel[1] = nullptr;
     return WGS_OK;
 }
 
@@ -56,6 +55,23 @@ bool note_moving(wgs_data *d, uint32_t mask) {
     d->moving_mask |= mask;
     d->bodies_move = d->bodies_move || mask != 0u;
     return d->moving_mask != moving_before;
+}
+// The buffers of the mesh colliders' samples (n) and vertices (nv), MemGroup::rigid — listed HERE AND NOWHERE ELSE. Every
+// pointer is forgotten first (the caller released the group), so 0, 0 leaves the data without them.
+wgs_status rigid_arrays(wgs_data *d, size_t n, size_t nv) {
+    Dev &dev = d->dev;
+    auto rigid_array = [&](auto **ptr, size_t count) {
+        *ptr = nullptr;
+        return count ? dev_alloc(d, ptr, count, MemGroup::rigid) : WGS_OK;
+    };
+    WGS_TRY(rigid_array(&dev.rp_local, n * D));
+    WGS_TRY(rigid_array(&dev.rp_world, n * D));
+    WGS_TRY(rigid_array(&dev.rp_ids, n));
+    WGS_TRY(rigid_array(&dev.rv_local, nv * D));
+    WGS_TRY(rigid_array(&dev.rv_world, nv * D));
+    WGS_TRY(rigid_array(&dev.rv_collider, nv));
+    WGS_TRY(rigid_array(&dev.rp_needs, n));
+    return WGS_OK;
 }
 wgs_status colliders_move(wgs_data *d, uint32_t mask) {
     if (note_moving(d, mask)) d->cdf_generation++;   // (what keeps of a block's node cdfs depends on which colliders move)
@@ -117,12 +133,12 @@ wgs_status wgs_set_particle_models(wgs_data *d, const uint8_t *models) {
             return fail(WGS_ERR_INVALID_ARGUMENT, "wgs_set_particle_models: entry " + std::to_string(i) + " is " + std::to_string((int)models[i]) + ", not a WGS_MODEL_* (0, 1, 2)");
     WGS_TRY(enter(d));
     Dev &dev = d->dev;
-    if (!dev.pmodel[0]) {   // one byte per slot and side, like the pid plane
-        WGS_TRY(dev_alloc(d, &dev.pmodel[0], (size_t)dev.npad));
-        if (dev_alloc(d, &dev.pmodel[1], (size_t)dev.npad) != WGS_OK) {
-            d->mem.release(dev.pmodel[0]);
-            dev.pmodel[0] = nullptr;
-            return WGS_ERR_HIP;
+    if (!dev.pmodel[0]) {   // one byte per slot and side, like the pid plane: both planes or neither
+        if (dev_alloc(d, &dev.pmodel[0], (size_t)dev.npad, MemGroup::models) != WGS_OK ||
+            dev_alloc(d, &dev.pmodel[1], (size_t)dev.npad, MemGroup::models) != WGS_OK) {
+            d->mem.release_group(MemGroup::models);
+            dev.pmodel[0] = dev.pmodel[1] = nullptr;
+            return fail(WGS_ERR_HIP, "wgs_set_particle_models: out of device memory for the model planes");
         }
     }
     if (n) {
@@ -249,19 +265,10 @@ wgs_status wgs_set_rigid_particles(wgs_data *d, const float *local_points, const
     Dev &dev = d->dev;
     dev.n_rigid = 0;
     // buffers of an earlier call are released (the mesh accumulators, sized by the grid capacity, are kept)
-    for (void *p : {(void *)dev.rp_local, (void *)dev.rp_world, (void *)dev.rv_local, (void *)dev.rv_world, (void *)dev.rp_ids, (void *)dev.rv_collider, (void *)dev.rp_needs})
-        d->mem.release(p);
-    dev.rp_local = dev.rp_world = dev.rv_local = dev.rv_world = nullptr;
-    dev.rp_ids = nullptr;
-    dev.rv_collider = dev.rp_needs = nullptr;
+    d->mem.release_group(MemGroup::rigid);
+    WGS_TRY(rigid_arrays(d, 0, 0));
     if (n == 0) return WGS_OK;
-    WGS_TRY(dev_alloc(d, &dev.rp_local, n * D));
-    WGS_TRY(dev_alloc(d, &dev.rp_world, n * D));
-    WGS_TRY(dev_alloc(d, &dev.rp_ids, n));
-    WGS_TRY(dev_alloc(d, &dev.rv_local, nv * D));
-    WGS_TRY(dev_alloc(d, &dev.rv_world, nv * D));
-    WGS_TRY(dev_alloc(d, &dev.rv_collider, nv));
-    WGS_TRY(dev_alloc(d, &dev.rp_needs, n));
+    WGS_TRY(rigid_arrays(d, n, nv));
     d->mesh_cdf = true;   // (the mesh accumulators belong to the grid group: alloc_grid lists them)
     WGS_TRY(alloc_grid(d, true));
     std::vector<uint4> packed(n);
@@ -311,7 +318,7 @@ wgs_status wgs_get_device_ptrs(wgs_data *d, wgs_device_ptrs *out) {
     if (d->dev.sharded) return fail(WGS_ERR_UNSUPPORTED, "sharded wgs_data: use wgs_shard_export");
     const float *buf = d->dev.buf[d->side];
     out->position_quads = buf + (size_t)Pl<D>::XM * 4 * d->dev.npad;
-    out->particle_ids = reinterpret_cast<const uint32_t *>(buf) + (size_t)Pl<D>::NQ * 4 * d->dev.npad;  // (layout.h ldpid)
+    out->particle_ids = pid_plane<D>(buf, d->dev.npad);
     out->count = d->dev.n;
     out->capacity = d->dev.npad;
     out->dim = D;
@@ -408,8 +415,7 @@ wgs_status wgs_read_blocks(wgs_data *d, wgs_block_record *out, size_t capacity, 
     }
     if (sorted_ids && d->dev.n) {
         // The buffer written by the last substep is in sorted order: its pid plane IS sorted_ids.
-        const float *pidp = d->dev.buf[d->side] + (size_t)P::NQ * 4 * d->dev.npad;
-        WGS_TRY(download(d, sorted_ids, pidp, sizeof(uint32_t) * (size_t)d->dev.n));
+        WGS_TRY(download(d, sorted_ids, pid_plane<D>(d->dev.buf[d->side], d->dev.npad), sizeof(uint32_t) * (size_t)d->dev.n));
     }
     return WGS_OK;
 }

@@ -1,6 +1,42 @@
 // capi_sharded.inc — entry points of the multi-GPU decomposition: communicators, wgs_shard_attach, wgs_sharded_step and its
 // one-process twin wgs_sharded_step_lockstep (what they enqueue: host_sharded.inc; wgs_shard_export is a reader: capi_io.inc).
 
+namespace {
+
+// The loan of a lockstep group's streams: from here to the end of the scope every slab works on slab 0's stream (the caller
+// drained the slabs' own streams first). However the scope ends, the slabs get their own streams back. On the way out of a
+// failed call slab 0's stream is drained first: work of every slab may already be queued on it, and a caller that carries
+// on — wgs_sync, a read-back, destroy — must not race it. A call that succeeds does not wait: hand_back_waiting.
+struct StreamLoan {
+    wgs_data **slabs;
+    const uint32_t n;
+    const hipStream_t s;
+    std::vector<hipStream_t> own;
+    bool drain = true;
+    StreamLoan(wgs_data **slabs_, uint32_t n_) : slabs(slabs_), n(n_), s(slabs_[0]->stream), own(n_) {
+        for (uint32_t r = 0; r < n; r++) own[r] = slabs[r]->stream.exchange(s);
+    }
+    StreamLoan(const StreamLoan &) = delete;
+    StreamLoan &operator=(const StreamLoan &) = delete;
+    ~StreamLoan() {
+        if (drain) hipStreamSynchronize(s);
+        for (uint32_t r = 0; r < n; r++) slabs[r]->stream.exchange(own[r]);
+    }
+    // The end of a call that succeeded: each slab's own stream waits for what the group enqueued (an event), nothing is drained.
+    wgs_status hand_back_waiting() {
+        Event done;
+        WGS_TRY(done.create(hipEventDisableTiming));
+        hipError_t e = hipEventRecord(done, s);
+        for (uint32_t r = 0; r < n && e == hipSuccess; r++)
+            if (own[r] != s) e = hipStreamWaitEvent(own[r], done, 0);
+        if (e != hipSuccess) return fail(WGS_ERR_HIP, hipGetErrorString(e));
+        drain = false;
+        return WGS_OK;
+    }
+};
+
+}  // namespace
+
 extern "C" {
 
 uint32_t wgs_shard_halo_record_bytes(void) { return (uint32_t)(HaloCfg<D>::REC_F4 * sizeof(float4)); }
@@ -28,7 +64,7 @@ wgs_status wgs_comm_create(wgs_pipeline *pipeline, const uint8_t id[WGS_COMM_ID_
     HIP_TRY(hipSetDevice(pipeline->device));
     NcclUid u;
     memcpy(u.internal, id, sizeof(u));
-    wgs_comm *c = new wgs_comm();
+    std::unique_ptr<wgs_comm> c(new wgs_comm());
     c->rank = rank;
     c->world = world;
     c->device = pipeline->device;
@@ -36,11 +72,8 @@ wgs_status wgs_comm_create(wgs_pipeline *pipeline, const uint8_t id[WGS_COMM_ID_
     c->upper = rank < world - 1 ? rank + 1 : -1;
     if (flags & WGS_COMM_SELF_NEIGHBOURS) c->lower = c->upper = rank;  // one-GPU proxy of an interior rank (timing only)
     const int rc = r->CommInitRank(&c->comm, world, u, rank);
-    if (rc != 0) {
-        delete c;
-        return fail(WGS_ERR_HIP, std::string("ncclCommInitRank: ") + r->GetErrorString(rc));
-    }
-    *out = c;
+    if (rc != 0) return fail(WGS_ERR_HIP, std::string("ncclCommInitRank: ") + r->GetErrorString(rc));
+    *out = c.release();
     return WGS_OK;
 }
 
@@ -129,92 +162,54 @@ wgs_status wgs_sharded_step_lockstep(wgs_pipeline *pipeline, wgs_data **slabs, u
             return fail(WGS_ERR_INVALID_ARGUMENT, "all slabs of a lockstep group need the same message capacities");
         if (slabs[r]->pipeline->device != pipeline->device) return fail(WGS_ERR_INVALID_ARGUMENT, "lockstep slabs live on one device");
     }
+    bool two_way = false;
+    for (uint32_t r = 0; r < num_slabs; r++) two_way = two_way || slabs[r]->two_way;
+    if (two_way && num_slabs > 1)
+        for (uint32_t r = 0; r < num_slabs; r++)
+            if (!slabs[r]->two_way) return fail(WGS_ERR_INVALID_ARGUMENT, "two-way coupling must be enabled on every slab or none");
     HIP_TRY(hipSetDevice(pipeline->device));
     // One stream orders everything FOR THE DURATION OF THIS CALL: every slab's own stream is drained, its work goes to
     // slab 0's stream, and before returning each slab gets its own stream back, made to wait for the group's work (an
     // event): no slab depends on another slab's lifetime afterwards.
-    hipStream_t s = slabs[0]->stream;
-    std::vector<hipStream_t> own(num_slabs);
-    for (uint32_t r = 0; r < num_slabs; r++) {
-        own[r] = slabs[r]->stream;
-        if (own[r] != s) HIP_TRY(hipStreamSynchronize(own[r]));
-    }
-    // (also on the error paths: work of every slab may already be queued on slab 0's stream, and a caller that carries on —
-    // wgs_sync, a read-back, destroy — must not race it: the stream is drained before the slabs get their own streams back)
-    auto restore = [&]() {
-        hipStreamSynchronize(s);
-        for (uint32_t r = 0; r < num_slabs; r++) slabs[r]->stream = own[r];
-    };
-    for (uint32_t r = 0; r < num_slabs; r++) slabs[r]->stream = s;
-#define LOCKSTEP_TRY(expr)                       \
-    do {                                         \
-        const wgs_status _st = (expr);           \
-        if (_st != WGS_OK) {                     \
-            restore();                           \
-            return _st;                          \
-        }                                        \
-    } while (0)
-#define LOCKSTEP_HIP(expr)                                                                           \
-    do {                                                                                             \
-        const hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) {                                                                      \
-            restore();                                                                               \
-            return fail(WGS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));             \
-        }                                                                                            \
-    } while (0)
-    bool two_way = false;
-    for (uint32_t r = 0; r < num_slabs; r++) two_way = two_way || slabs[r]->two_way;
+    for (uint32_t r = 1; r < num_slabs; r++)
+        if (slabs[r]->stream != slabs[0]->stream) HIP_TRY(hipStreamSynchronize(slabs[r]->stream));
+    StreamLoan loan(slabs, num_slabs);   // (every return below hands the streams back)
+    const hipStream_t s = loan.s;
     int32_t **imp_ptrs = nullptr;
     if (two_way && num_slabs > 1) {
-        for (uint32_t r = 0; r < num_slabs; r++)
-            if (!slabs[r]->two_way) {
-                restore();
-                return fail(WGS_ERR_INVALID_ARGUMENT, "two-way coupling must be enabled on every slab or none");
-            }
         std::vector<int32_t *> host(num_slabs);
         for (uint32_t r = 0; r < num_slabs; r++) host[r] = slabs[r]->dev.impulses;
         wgs_data *d0 = slabs[0];
         if (!d0->lockstep_imp_ptrs || d0->lockstep_imp_n != num_slabs) {
             d0->mem.release(d0->lockstep_imp_ptrs);
             d0->lockstep_imp_ptrs = nullptr;
-            LOCKSTEP_TRY(dev_alloc(d0, &d0->lockstep_imp_ptrs, num_slabs));
+            WGS_TRY(dev_alloc(d0, &d0->lockstep_imp_ptrs, num_slabs));
             d0->lockstep_imp_n = num_slabs;
         }
-        LOCKSTEP_HIP(hipMemcpyAsync(d0->lockstep_imp_ptrs, host.data(), sizeof(int32_t *) * num_slabs, hipMemcpyHostToDevice, s));
-        LOCKSTEP_HIP(hipStreamSynchronize(s));  // (host vector goes out of scope)
+        HIP_TRY(hipMemcpyAsync(d0->lockstep_imp_ptrs, host.data(), sizeof(int32_t *) * num_slabs, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (host vector goes out of scope)
         imp_ptrs = d0->lockstep_imp_ptrs;
     }
-    for (uint32_t r = 0; r < num_slabs; r++) LOCKSTEP_TRY(maintain_grid(slabs[r]));
+    for (uint32_t r = 0; r < num_slabs; r++) WGS_TRY(maintain_grid(slabs[r]));
     for (uint32_t i = 0; i < num_substeps; i++) {
-        for (uint32_t r = 0; r < num_slabs; r++) LOCKSTEP_TRY(shard_phase_begin(pipeline, slabs[r]));
+        for (uint32_t r = 0; r < num_slabs; r++) WGS_TRY(shard_phase_begin(pipeline, slabs[r]));
         for (uint32_t r = 0; r + 1 < num_slabs; r++) {  // face between slab r and r + 1: the transport
             ShardLink &A = *slabs[r]->link, &B = *slabs[r + 1]->link;
-            LOCKSTEP_HIP(hipMemcpyAsync(B.msg_in[0], A.msg_out[1], A.msg_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-            LOCKSTEP_HIP(hipMemcpyAsync(A.msg_in[1], B.msg_out[0], A.msg_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(B.msg_in[0], A.msg_out[1], A.msg_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(A.msg_in[1], B.msg_out[0], A.msg_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
         for (uint32_t r = 0; r < num_slabs; r++) {
             slabs[r]->reduce_impulses = imp_ptrs ? 2 : 0;  // 2: bodies are integrated after the group-wide sum below
-            LOCKSTEP_TRY(shard_phase_end(pipeline, slabs[r]));
+            WGS_TRY(shard_phase_end(pipeline, slabs[r]));
         }
         if (imp_ptrs) {
             hipLaunchKernelGGL(k_impulses_allreduce_local, dim3(1), dim3(128), 0, s, imp_ptrs, (int)num_slabs);
-            for (uint32_t r = 0; r < num_slabs; r++) LOCKSTEP_TRY(enqueue_bodies(slabs[r]));
+            for (uint32_t r = 0; r < num_slabs; r++) WGS_TRY(enqueue_bodies(slabs[r]));
         }
     }
-    LOCKSTEP_HIP(hipGetLastError());
-    for (uint32_t r = 0; r < num_slabs; r++) LOCKSTEP_TRY(watch_counters(slabs[r]));
-    // hand the streams back: each slab's own stream waits for what the group enqueued
-    hipEvent_t done = nullptr;
-    LOCKSTEP_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(done, s);
-    for (uint32_t r = 0; r < num_slabs && e == hipSuccess; r++)
-        if (own[r] != s) e = hipStreamWaitEvent(own[r], done, 0);
-    hipEventDestroy(done);
-    for (uint32_t r = 0; r < num_slabs; r++) slabs[r]->stream = own[r];
-#undef LOCKSTEP_TRY
-#undef LOCKSTEP_HIP
-    if (e != hipSuccess) return fail(WGS_ERR_HIP, hipGetErrorString(e));
-    return WGS_OK;
+    HIP_TRY(hipGetLastError());
+    for (uint32_t r = 0; r < num_slabs; r++) WGS_TRY(watch_counters(slabs[r]));
+    return loan.hand_back_waiting();
 }
 
 }  // extern "C"

@@ -105,7 +105,7 @@ wgs_status grow_grid(wgs_data *d, uint32_t new_cap) {
         d->mem.regroup(MemGroup::old_grid, MemGroup::grid);
         dev = old;
         d->auto_grow = false;
-        hipGetLastError();  // (the failed hipMalloc is not this call's error)
+        hipGetLastError();  // (the failed allocation is not this call's error)
         return WGS_OK;
     }
     d->mem.release_group(MemGroup::old_grid);
@@ -153,11 +153,15 @@ wgs_status maintain_grid(wgs_data *d) {
 
 // leaves a copy of the device counters in pinned host memory for the next call's maintain_grid (asynchronous)
 wgs_status watch_counters(wgs_data *d) {
-    if (!d->seen.watch) {
-        HIP_TRY(hipHostMalloc((void **)&d->seen.watch, sizeof(uint32_t) * CTR_COUNT, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&d->seen.watch_event, hipEventDisableTiming));
+    if (!d->seen.watch) {   // (the watch exists with its event or not at all: a failure leaves nothing behind for the next call)
+        Pinned<uint32_t> watch;
+        Event copied;
+        WGS_TRY(watch.alloc(CTR_COUNT));
+        WGS_TRY(copied.create(hipEventDisableTiming));
+        d->seen.watch = std::move(watch);
+        d->seen.watch_event = std::move(copied);
     }
-    HIP_TRY(hipMemcpyAsync(d->seen.watch, d->dev.counters, sizeof(uint32_t) * CTR_COUNT, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->seen.watch.get(), d->dev.counters, sizeof(uint32_t) * CTR_COUNT, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipEventRecord(d->seen.watch_event, d->stream));
     d->seen.watch_pending = true;
     return WGS_OK;

@@ -1,7 +1,13 @@
 // host_state.h — what every other part of capi.hip builds on: error reporting (fail, HIP_TRY, WGS_TRY), the handle
-// structs behind the C ABI, and the two owners of device memory. hipMalloc / hipFree appear in this file only:
-// DeviceMemory holds what lives as long as a wgs_data (or until it is released by name), Scratch what lives for one call.
-// No kernel and no entry point belongs here.
+// structs behind the C ABI, and the owners of everything the HIP runtime hands out. The calls that make or end a resource
+// appear in this file only:
+//   hipMalloc / hipFree                      DeviceMemory (lives as long as a wgs_data, or until its group is released) and
+//                                            Scratch (lives for one call)
+//   hipHostMalloc / hipHostFree              Pinned
+//   hipEventCreate* / hipEventDestroy        Event, and Events (the block of timing marks: all of them or none)
+//   hipStreamCreate* / hipStreamDestroy      DataStream (the data's stream, its own or the caller's)
+// Each owner ends what it made when it goes out of scope, whichever way that happens; ScopeExit does the same for an
+// action. No kernel and no entry point belongs here.
 #pragma once
 
 namespace {
@@ -33,6 +39,58 @@ wgs_status fail(wgs_status code, const std::string &msg) {
         if (_st != WGS_OK) return _st;         \
     } while (0)
 
+// An action for the end of a scope, whichever way it ends: ScopeExit guard{[&] { ... }};
+template <typename F> struct ScopeExit {
+    F at_exit;
+    ~ScopeExit() { at_exit(); }
+};
+template <typename F> ScopeExit(F) -> ScopeExit<F>;
+
+// Pinned host memory.
+template <typename T> class Pinned {
+    T *ptr = nullptr;
+
+public:
+    Pinned() = default;
+    Pinned(Pinned &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+    Pinned &operator=(Pinned &&o) noexcept {
+        std::swap(ptr, o.ptr);
+        return *this;
+    }
+    ~Pinned() {
+        if (ptr) hipHostFree(ptr);
+    }
+    wgs_status alloc(size_t count) {
+        HIP_TRY(hipHostMalloc((void **)&ptr, sizeof(T) * count, hipHostMallocDefault));
+        return WGS_OK;
+    }
+    T *get() const { return ptr; }
+    T &operator[](size_t i) const { return ptr[i]; }
+    explicit operator bool() const { return ptr != nullptr; }
+};
+
+// One event.
+class Event {
+    hipEvent_t ev = nullptr;
+
+public:
+    Event() = default;
+    Event(Event &&o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    Event &operator=(Event &&o) noexcept {
+        std::swap(ev, o.ev);
+        return *this;
+    }
+    ~Event() {
+        if (ev) hipEventDestroy(ev);
+    }
+    wgs_status create(unsigned flags) {
+        HIP_TRY(hipEventCreateWithFlags(&ev, flags));
+        return WGS_OK;
+    }
+    operator hipEvent_t() const { return ev; }
+};
+
+// The marks of a timestamped wgs_step: created by the first such call, all of them or none.
 struct Events {
     static constexpr int MAX_SUBSTEPS = 64;
     static constexpr int MARKS = 11;  // + 2 calibration marks (9, 10) recorded back to back: the cost of a mark itself
@@ -40,11 +98,64 @@ struct Events {
     hipEvent_t ev[MAX_SUBSTEPS][MARKS];
     int used = 0;
     bool created = false;
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() { destroy(created ? MAX_SUBSTEPS * MARKS : 0); }
+    wgs_status create() {
+        if (created) return WGS_OK;
+        for (int k = 0; k < MAX_SUBSTEPS * MARKS; k++) {
+            const hipError_t e = hipEventCreateWithFlags(&ev[0][0] + k, hipEventDisableSystemFence);  // timing only: no cache writeback per mark
+            if (e != hipSuccess) {
+                destroy(k);
+                return fail(WGS_ERR_HIP, std::string("hipEventCreateWithFlags (timing marks): ") + hipGetErrorString(e));
+            }
+        }
+        created = true;
+        return WGS_OK;
+    }
+
+private:
+    void destroy(int count) {   // (the first `count` in creation order: row by row)
+        for (int k = 0; k < count; k++) hipEventDestroy(*(&ev[0][0] + k));
+        created = false;
+    }
+};
+
+// The stream of one wgs_data: made with it, or the caller's (wgs_set_stream), which is never destroyed here.
+class DataStream {
+    hipStream_t s = nullptr;
+    bool owned = false;
+
+public:
+    DataStream() = default;
+    DataStream(const DataStream &) = delete;
+    DataStream &operator=(const DataStream &) = delete;
+    ~DataStream() {
+        if (s && owned) hipStreamDestroy(s);
+    }
+    wgs_status create() {
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return fail(WGS_ERR_HIP, "hipStreamCreate failed");
+        owned = true;
+        return WGS_OK;
+    }
+    wgs_status borrow(hipStream_t callers) {   // (the caller drained the old one)
+        if (s && owned) HIP_TRY(hipStreamDestroy(s));
+        s = callers;
+        owned = false;
+        return WGS_OK;
+    }
+    // For the length of one call another stream stands in (capi_sharded.inc StreamLoan, which puts the old one back):
+    // whose stream it is does not change.
+    hipStream_t exchange(hipStream_t other) { return std::exchange(s, other); }
+    operator hipStream_t() const { return s; }
 };
 
 // Device memory of one wgs_data. Every allocation belongs to a group: `grid` = the arrays sized by the block capacity
-// (host_grid.inc alloc_grid lists them, grow_grid replaces the whole group), `fixed` = everything else.
-enum class MemGroup : uint8_t { fixed, grid, old_grid };
+// (host_grid.inc alloc_grid lists them, grow_grid replaces the whole group), `rigid` = the samples and vertices of the mesh
+// colliders (capi_io.inc rigid_arrays lists them), `models` = the two planes of per-particle models, `fixed` = everything
+// else. What a later call replaces goes by release_group.
+enum class MemGroup : uint8_t { fixed, grid, old_grid, rigid, models };
 class DeviceMemory {
     struct Block { void *ptr; size_t bytes; MemGroup group; };
     std::vector<Block> blocks;
@@ -127,8 +238,7 @@ struct ShardLink {                // device memory owned by the wgs_data: one me
 struct wgs_data {
     // ---- what the simulation is: set at creation or by a setter
     wgs_pipeline *pipeline = nullptr;
-    hipStream_t stream = nullptr;
-    bool owns_stream = true;
+    DataStream stream;
     Dev dev{};
     int side = 0;
     bool plastic = false;
@@ -162,7 +272,8 @@ struct wgs_data {
     uint32_t lockstep_imp_n = 0;
     // diagnostics (kernels_diag.h): accumulators and the result on the device (allocated by the first call, freed with `mem`), pinned host copy
     DiagAcc *diag_acc = nullptr;
-    wgs_diagnostics *diag_out = nullptr, *diag_host = nullptr;
+    wgs_diagnostics *diag_out = nullptr;
+    Pinned<wgs_diagnostics> diag_host;
     // Eulerian field output (capi_probe.inc): the sampler's scratch word per block id (allocated by the first call, freed with `mem`),
     // the capacity it was sized for, and the ticket of the last call
     uint32_t *probe_mark = nullptr;
@@ -174,8 +285,8 @@ struct wgs_data {
     // ---- the host's last look at the device counters: written by maintain_grid (the pinned watch) and fetch_counters
     // (wgs_sync and the readers), read by the launch plans
     struct Seen {
-        uint32_t *watch = nullptr;     // pinned host copy of the device counters as of the end of the last wgs_step call
-        hipEvent_t watch_event = nullptr;
+        Pinned<uint32_t> watch;        // pinned host copy of the device counters as of the end of the last wgs_step call ...
+        Event watch_event;             // ... and the event behind that copy: made together (watch_counters), both or neither
         bool watch_pending = false;
         uint32_t watch_skips = 0;
         uint32_t errors = 0;           // sticky: CTR_ERRORS of every look

@@ -524,6 +524,14 @@ template <int D> __device__ inline uint32_t ldpid(const float *base, uint32_t np
     asm volatile("" : "+v"(off));
     return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(base) + off);
 }
+// ... which is where this points: the pid plane of a buffer, one u32 per slot (for the host and the readers; the hot kernels
+// address it through ldpid / stpid, by 32-bit byte offsets)
+template <int D> __host__ __device__ inline const uint32_t *pid_plane(const float *base, uint32_t npad) {
+    return reinterpret_cast<const uint32_t *>(base + (size_t)Pl<D>::NQ * 4 * npad);
+}
+template <int D> __host__ __device__ inline uint32_t *pid_plane(float *base, uint32_t npad) {
+    return const_cast<uint32_t *>(pid_plane<D>(static_cast<const float *>(base), npad));
+}
 // Epoch (substep number) at which the particle's CDF quads were last computed. A particle whose block is
 // out of reach of every collider has default_cdf() (g2p_cdf.wgsl:246-249); instead of storing 32 bytes of
 // zeros for ~all particles every substep, the quads are only written for particles near a collider and

@@ -182,23 +182,41 @@ def uniform_material_of(particles: ParticleSet):
     return None
 
 
+# The quads of a particle slot — and of an exchange record, which is a slot's quads followed by its id and the substep of
+# its cdf — per dimension, under the names of Pl<D> in csrc/layout.h (tests/test_quad_table.py holds the two equal).
+QUADS = {
+    3: dict(XM=0, CV0=1, CV1=2, CV2=3, F0=4, F1=5, F2=6, NBASE=7, DP0=7, DP1=8, DP2=9, CDF0=10, CDF1=11, NQ=12),
+    2: dict(XM=0, CV0=1, CV2=2, F0=3, NBASE=4, DP0=4, DP1=5, DP2=6, CDF0=7, CDF1=8, NQ=9),
+}
+
+
+def record_floats(dim: int) -> int:
+    """floats per exchange record (csrc/kernels_shard.h particle_record_floats)"""
+    return QUADS[dim]["NQ"] * 4 + 2
+
+
+def record_quad(rec: np.ndarray, dim: int, name: str) -> np.ndarray:
+    """the four floats of quad `name` of every record [count, 4] (a view)"""
+    k = QUADS[dim][name]
+    return rec[:, 4 * k:4 * k + 4]
+
+
 def unpack_records(rec: np.ndarray, dim: int, uniform_material=None):
     """Particle records (quad layout of csrc/layout.h) -> dict of arrays. In uniform-material mode (3D) the record's
     XM.w slot holds F[8] and the mass is the shared one."""
     ids = rec[:, -2].copy().view(np.uint32)     # [..quads.., pid, cdf epoch]
+    q = lambda name: record_quad(rec, dim, name)
     if dim == 3:
-        q = lambda k: rec[:, 4 * k:4 * k + 4]
-        pos, mass = q(0)[:, :3], q(0)[:, 3]
-        C_ = np.concatenate([q(1), q(2), q(3)[:, :1]], 1)
-        vel = q(3)[:, 1:4]
-        F = np.concatenate([q(4), q(5), q(6)[:, :1]], 1)
+        pos, mass = q("XM")[:, :3], q("XM")[:, 3]
+        C_ = np.concatenate([q("CV0"), q("CV1"), q("CV2")[:, :1]], 1)
+        vel = q("CV2")[:, 1:4]
+        F = np.concatenate([q("F0"), q("F1"), q("F2")[:, :1]], 1)
         if uniform_material is not None:
-            F = np.concatenate([q(4), q(5), q(0)[:, 3:4]], 1)
+            F = np.concatenate([q("F0"), q("F1"), q("XM")[:, 3:4]], 1)
             mass = np.full(len(rec), np.float32(uniform_material[0]), np.float32)
     else:
-        q = lambda k: rec[:, 4 * k:4 * k + 4]
-        pos, mass = q(0)[:, :2], q(0)[:, 2]
-        C_, vel, F = q(1), q(2)[:, :2], q(3)
+        pos, mass = q("XM")[:, :2], q("XM")[:, 2]
+        C_, vel, F = q("CV0"), q("CV2")[:, :2], q("F0")
     return dict(ids=ids, pos=pos.copy(), vel=vel.copy(), def_grad=F.copy(), affine=C_.copy(), mass=mass.copy())
 
 
