@@ -187,7 +187,7 @@ class Contact:
 
 class Result(NamedTuple):
     st: T.Stencil
-    grid: T.Grid                   # gated P2G + grid update; .dimp [M, d]: the momentum not transferred (unchecked here)
+    grid: T.Grid                   # gated P2G + grid update; .dimp [M, d]: the momentum not transferred, .pairs: its pairs (checked by tests/body_truth.py)
     particles: T.Particles
     contact: Contact
     compat: np.ndarray             # [n, S] pairs that transfer
@@ -244,11 +244,13 @@ def substep(inp: T.Inputs, h, dt, gravity, f: Fields, motion: Motion, variant=()
         L = lipschitz(normal[p])
         node_b[p, s] = b_bv + L * (b_bv + u * rn) + C_PROJ * u * L * rn + np.where(ln <= 2.0 * LEN_EPS, 2.0 * LEN_EPS, 0.0) + \
             u * np.linalg.norm(ghost, axis=1)
-        # the momentum a pair does not transfer (the later body check's input)
+        # the momentum a pair does not transfer: what the closest body receives (tests/body_truth.py reads the pairs)
         dimp = (inp.v[p] - ghost) * (st.w[p, s] * inp.m[p])[:, None]
         gr.dimp = np.stack([np.bincount(gr.inv[p, s], dimp[:, k], len(gr.keys)) for k in range(d)], 1)
+        gr.pairs = (p, s, ghost, node_b[p, s])
     else:
         gr.dimp = np.zeros((len(gr.keys), d))
+        gr.pairs = (p, s, np.zeros((0, d)), np.zeros(0))
     takes_grid = compat | ("g2p_incompatible_takes_grid" in variant)
     if own_grid is None:
         _, bv_n, _ = gr.bounds(u, extra_levels)

@@ -20,7 +20,7 @@ import pytest
 import cdf_truth as CT
 import cpic_truth as CP
 import transfer_truth as T
-from gpu_common import _native_slabs, checked_cpic_substep, export_state_and_cdf
+from gpu_common import _bed_scene, _native_slabs, checked_cpic_substep, export_state_and_cdf
 from helpers import debug, new_data, pipeline, report_margin
 from wgsparkl_amd.solver import Collider, SimulationParams
 
@@ -96,31 +96,6 @@ def test_colliders_at_rest_take_the_one_way_p2g(hip_libs, monkeypatch, name, h, 
     assert all(not p["linvel"].any() and not p["angvel"].any() for p in after)
 
 
-def _bed_scene(d, h, n=None, drift=0.0):
-    """a bed of `n` particles 6 blocks long whose lowest half cell lies inside a fixed floor, stirred (a swirl of 0.15 h / dt
-    plus noise, plus `drift` h / dt along x), and a kinematic ball driven into its top at 0.09 h per substep"""
-    bw = T.bw_of(d)
-    rng = np.random.default_rng(60 + d)
-    floor = Collider.cuboid(CT._v(np.array([3.2 * bw, 1.0, 3.0 * bw]) * h, d), CT._v(np.array([3.0 * bw + 0.13, bw - 0.8, 1.5 * bw + 0.21]) * h, d),
-                            rotation=CT.ident(d))
-    lin = np.zeros(3)
-    lin[:d] = (np.array([0.03, -0.08, 0.02]) * h / T.DT)[:d]
-    ball = Collider.ball(float(np.float32(1.5 * h)), CT._v(np.array([3 * bw + 0.4, 2 * bw + 3.6, 1.5 * bw + 0.27]) * h, d),
-                         linvel=tuple(float(v) for v in CT.f32(lin)), angvel=(0.7,) if d == 2 else (0.3, -0.5, 0.4))
-    lo, hi = np.array([1.0, bw - 0.3, bw + 0.5]) * h, np.array([6 * bw - 1.0, 2 * bw + 3.0, 2 * bw + 2.5]) * h
-    sc = CT._static(d, h, rng, [floor, ball], [(lo, hi)], n or (3000 if d == 3 else 1500), rim_keep=1.0)
-    ps = sc["particles"]
-    c = ps.pos.mean(0)
-    vel = np.zeros((ps.n, d))
-    vel[:, 0] = -(ps.pos[:, 1] - c[1])
-    vel[:, 1] = ps.pos[:, 0] - c[0]
-    vel = vel * (0.15 * h / T.DT / (3.0 * bw * h)) + rng.normal(0.0, 0.03 * h / T.DT, (ps.n, d))
-    vel[:, 0] += drift * h / T.DT
-    ps.vel[:] = vel.astype(np.float32)
-    sc["params"] = SimulationParams(gravity=T.GRAVITY[:d], dt=T.DT)
-    return sc
-
-
 def _drive(sc, data, d, h):
     """the host pushes the ball 0.3 h further into the bed (beyond the 0.09 h its own velocity moves it per substep: a body
     in contact is limited to 0.1 h): the particles at its surface keep their sign, and find themselves on the other side"""
@@ -167,7 +142,8 @@ def test_dynamic_body(hip_libs, d):
     """A cuboid of finite mass among the particles. Its P2G is the two-way instantiation every scene with a moving collider
     runs (the kinematic ones too); what sets this case apart is that the impulses the incompatible pairs leave move the body:
     its angular velocity, which nothing else changes, differs after the substep. Grid and particles are checked against the
-    velocities the body had before it; what the body receives is not checked."""
+    velocities the body had before it; what the body receives and how it integrates is checked by tests/test_gpu_bodies.py
+    (gpu_common.checked_body_substep, against tests/body_truth.py)."""
     h = 0.2
     sc = _scene("cuboid", d, h)
     sc["colliders"] = [dataclasses.replace(c.with_density(50.0, d), linvel=c.linvel, angvel=c.angvel) for c in sc["colliders"]]
