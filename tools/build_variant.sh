@@ -1,7 +1,7 @@
-# usage: bash tools/build_variant.sh NAME [extra hipcc flags]  -> tools/tmp_libs/NAME.so (3D library of the current tree)
+# usage: bash tools/build_variant.sh NAME [extra hipcc flags]  -> tools/tmp_libs/NAME/libwgsparkl{2,3}d_hip.so of the current tree
+# (csrc/build.sh with another output directory; run anything with it through WGS_LIB_DIR=tools/tmp_libs/NAME)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
-mkdir -p tools/tmp_libs
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -fno-fast-math -ffp-contract=on -w -DWGS_DIM=3 "$@" wgsparkl_amd/csrc/capi.hip -o tools/tmp_libs/$name.so
-echo built tools/tmp_libs/$name.so
+WGS_OUT_DIR="$PWD/tools/tmp_libs/$name" WGS_EXTRA_FLAGS="$*" bash wgsparkl_amd/csrc/build.sh
+echo built tools/tmp_libs/$name

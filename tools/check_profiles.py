@@ -1,6 +1,6 @@
 """Fails (exit 1) when an evidence file under profiles/ is byte-equal to the same-named file of ANOTHER round: a file called
 rNN_x must come from round NN's own runs (round 4 shipped r04_parity_margins.json as a copy of r03's). Run here, on the CPU:
-`python tools/check_profiles.py`; tools/gpu_round_evidence.sh's summaries are checked by it before they are committed, and
+`python tools/check_profiles.py`; the summaries of the tools/summarize_*.py scripts are checked by it before they are committed, and
 tests/test_profiles_hygiene.py runs it in the CPU suite."""
 import collections, hashlib, os, re, sys
 

@@ -1,9 +1,10 @@
-"""Developer utility: the same scenes stepped with two libraries (LIB_A, LIB_B = paths of libwgsparkl3d_hip.so variants; default: tools/tmp_libs/base.so
-against the in-tree library), results compared bit for bit. A refactor that keeps every particle's arithmetic must print zeros."""
+"""Developer utility: the same scenes stepped with two libraries (LIB_A, LIB_B = directories of library variants, tools/build_variant.sh; default:
+tools/tmp_libs/base against the in-tree libraries), results compared bit for bit. A refactor that keeps every particle's arithmetic must print zeros.
+The children take their library through WGS_LIB_DIR; the in-tree libraries are never touched."""
 import os, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TREE = os.path.join(ROOT, "wgsparkl_amd", "csrc", "libwgsparkl3d_hip.so")
+TREE = os.path.join(ROOT, "wgsparkl_amd", "csrc")
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     from helpers import pipeline
@@ -20,17 +21,14 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     p = data.read_particles()
     np.savez(out, pos=p.pos, vel=p.vel, F=p.def_grad, C=p.affine, dp=p.dp_state, aff=p.cdf_affinity, nrm=p.cdf_normal, dist=p.cdf_dist)
     sys.exit(0)
-lib_a = os.environ.get("LIB_A", os.path.join(ROOT, "tools", "tmp_libs", "base.so"))
-keep = tempfile.mktemp(suffix=".so"); subprocess.run(["cp", TREE, keep], check=True)
-try:
+dirs = [os.path.abspath(os.environ.get("LIB_A", os.path.join(ROOT, "tools", "tmp_libs", "base"))), os.path.abspath(os.environ.get("LIB_B", TREE))]
+with tempfile.TemporaryDirectory() as tmp:
     for name, steps in (("sand3", 150), ("landed", 260), ("c3s", 60), ("cube", 40)):
         outs = []
-        for tag, lib in (("a", lib_a), ("b", keep)):
-            subprocess.run(["cp", lib, TREE], check=True)
-            out = tempfile.mktemp(suffix=".npz")
-            subprocess.run([sys.executable, __file__, "--child", name, out, str(steps)], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        for tag, lib_dir in zip("ab", dirs):     # each child is a fresh process; check=True ends the run at the first one that fails
+            out = os.path.join(tmp, f"{name}_{tag}.npz")
+            subprocess.run(["timeout", "-k", "10", "300", sys.executable, __file__, "--child", name, out, str(steps)], check=True,
+                           env={**os.environ, "WGS_LIB_DIR": lib_dir}, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             outs.append(np.load(out))
         a, b = outs
-        print(name, steps, {k: int((a[k] != b[k]).sum()) for k in a.files}, "max |dpos|", float(np.abs(a["pos"] - b["pos"]).max()))
-finally:
-    subprocess.run(["cp", keep, TREE], check=True)
+        print(name, steps, {k: int((a[k] != b[k]).sum()) for k in a.files}, "max |dpos|", float(np.abs(a["pos"] - b["pos"]).max()), flush=True)

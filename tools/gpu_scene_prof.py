@@ -1,4 +1,4 @@
-"""Developer utility: one reference-sized scene under rocprofv3 (tools/gpu_scene_kstats.sh): settle, sync, then the substeps."""
+"""Developer utility: one reference-sized scene under rocprofv3 (`tools/gpu.py kstats SCENE` / `pmc SCENE`): settle, sync, then the substeps."""
 import sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 from helpers import pipeline
 from wgsparkl_amd import MpmData, scenes

@@ -1,7 +1,10 @@
-"""gpurun_out/<round>_extra, <round>_sharded (tools/gpu_round_evidence.sh) -> profiles/<round>_kernel_stats_{c3,c4,c5,stirred,sand3}.csv,
+"""usage: summarize_extra.py ROUND RAW_DIR. RAW_DIR (tools/README.md: `gpu.py kstats T` / `gpu.py pmc T` for T in c3 c4 c5 stirred sand3,
+`gpu.py kstats native --tag native_c2 -- c2` / `native_c5 -- c5`, all with `--out RAW_DIR`, and RAW_DIR/cost_{c2,c5}.log = the "substeps"
+lines of tools/gpu_native_host_cost.py) -> profiles/<round>_kernel_stats_{c3,c4,c5,stirred,sand3}.csv,
 profiles/<round>_pmc_summary_{c3,c4,c5,sand3,stirred}.json, profiles/<round>_sharded_cost.txt, profiles/<round>_sharded_self_neighbours_{1m,c5}_slab_kernel_stats.csv."""
 import csv, json, os, sys
-R = sys.argv[1] if len(sys.argv) > 1 else "r06"
+if len(sys.argv) != 3: sys.exit(__doc__)
+R, RAW = sys.argv[1], sys.argv[2]
 CMD = {"c3": "rocprofv3 --kernel-trace --stats -- python3 bench.py --config c3 --steps 50 --warmup 10 --no-cpu-baseline --no-extra --no-live-pmc",
        "c4": "rocprofv3 --kernel-trace --stats -- python3 bench.py --config c4 --steps 50 --warmup 10 --no-cpu-baseline --no-extra --no-live-pmc",
        "c5": "rocprofv3 --kernel-trace --stats -- python3 bench.py --config c5 --steps 50 --warmup 10 --no-cpu-baseline --no-extra --no-live-pmc",
@@ -16,13 +19,13 @@ def copy_stats(src, dst, cmd):
     top = sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:5]
     print(os.path.basename(dst)); [print(f"   {r['Name'][:80]:80s} calls {r['Calls']:>5s} avg {float(r['AverageNs'])/1e3:8.1f} us") for r in top]
 for k, cmd in CMD.items():
-    src = f"gpurun_out/{R}_extra/kernel_stats_{k}.csv"
+    src = f"{RAW}/kstats_{k}/kernel_stats.csv"
     if os.path.exists(src): copy_stats(src, f"profiles/{R}_kernel_stats_{k}.csv", cmd)
-NOTE = {"c3": "tools/gpu_pmc_cfg.sh CFG=c3: bench.py --config c3 --steps 12 --warmup 4", "c4": "tools/gpu_pmc_cfg.sh CFG=c4: bench.py --config c4 --steps 12 --warmup 4",
-        "c5": "tools/gpu_pmc_cfg.sh CFG=c5: bench.py --config c5 --steps 12 --warmup 4", "sand3": "tools/gpu_scene_pmc.sh SCENE=sand3: tools/gpu_scene_prof.py sand3 (100 + 200 substeps)",
-        "stirred": "tools/gpu_scene_pmc.sh SCENE=stirred: tools/gpu_scene_prof.py stirred (bench.py's c2_stirred scene, 5 + 50 substeps)"}
+NOTE = {"c3": "tools/gpu.py pmc c3: bench.py --config c3 --steps 12 --warmup 4", "c4": "tools/gpu.py pmc c4: bench.py --config c4 --steps 12 --warmup 4",
+        "c5": "tools/gpu.py pmc c5: bench.py --config c5 --steps 12 --warmup 4", "sand3": "tools/gpu.py pmc sand3: tools/gpu_scene_prof.py sand3 (100 + 200 substeps)",
+        "stirred": "tools/gpu.py pmc stirred: tools/gpu_scene_prof.py stirred (bench.py's c2_stirred scene, 5 + 50 substeps)"}
 for tag, what in NOTE.items():
-    src = f"gpurun_out/{R}_extra/pmc_summary_{tag}.json"
+    src = f"{RAW}/pmc_{tag}/summary.json"
     if not os.path.exists(src): continue
     d = json.load(open(src))
     d["_note"] = (what + "; rocprofv3 --kernel-trace --pmc, one counter set per run (FETCH_SIZE | WRITE_SIZE | two SQ sets); per kernel, mean over the second half of the "
@@ -33,9 +36,9 @@ for tag, what in NOTE.items():
             print(tag, k[:60], "MB/launch", round(e.get("hbm_bytes_per_launch", 0) / 1e6, 1), "wait frac", round(e.get("wait_frac_of_wave_cycles", 0), 3), "VALU insts", int(e.get("SQ_INSTS_VALU", 0)))
 lines = []
 for cfg, name in (("c2", "1m"), ("c5", "c5")):
-    f = f"gpurun_out/{R}_sharded/cost_{cfg}.log"
+    f = f"{RAW}/cost_{cfg}.log"
     if os.path.exists(f): lines += [f"== tools/gpu_native_host_cost.py {cfg}"] + [l.rstrip() for l in open(f)]
-    src = f"gpurun_out/{R}_sharded/kernel_stats_{cfg}.csv"
+    src = f"{RAW}/kstats_native_{cfg}/kernel_stats.csv"
     if os.path.exists(src):
         copy_stats(src, f"profiles/{R}_sharded_self_neighbours_{name}_slab_kernel_stats.csv", f"rocprofv3 --kernel-trace --stats -- python3 tools/gpu_native_host_cost.py {cfg} (one rank as its own two neighbours over RCCL)")
 if lines:

@@ -1,11 +1,12 @@
-"""gpurun_out/<tag>/margins.jsonl (written by the -m gpu suite when WGS_MARGINS_FILE is set, tools/gpu_tests_all.sh)
--> profiles/<round>_parity_margins.json: per check name, how many comparisons, the worst measured value, its bound and
-the test it came from."""
+"""usage: summarize_margins.py ROUND RAW_DIR. RAW_DIR/margins.jsonl (written by the -m gpu suite when WGS_MARGINS_FILE is set:
+`python tools/gpu.py tests` -> build/gpu_out/tests) -> profiles/<round>_parity_margins.json: per check name, how many comparisons,
+the worst measured value, its bound and the test it came from."""
 import collections, json, sys
-tag, rnd = (sys.argv[1] if len(sys.argv) > 1 else "tests"), (sys.argv[2] if len(sys.argv) > 2 else "r03")
+if len(sys.argv) != 3: sys.exit(__doc__)
+rnd, raw = sys.argv[1], sys.argv[2]
 by = collections.OrderedDict()
 total = escapes = 0
-for line in open(f"gpurun_out/{tag}/margins.jsonl"):
+for line in open(f"{raw}/margins.jsonl"):
     r = json.loads(line)
     total += 1
     escapes += 1 if r.get("escape_used") else 0
@@ -16,7 +17,7 @@ for line in open(f"gpurun_out/{tag}/margins.jsonl"):
 import os, re, subprocess
 suite = ""
 try:
-    suite = [l.strip() for l in open(f"gpurun_out/{tag}/pytest.log") if re.search(r"\d+ passed", l)][-1]
+    suite = [l.strip() for l in open(f"{raw}/pytest.log") if re.search(r"\d+ passed", l)][-1]
 except Exception:
     pass
 head = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()

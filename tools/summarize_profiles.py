@@ -1,19 +1,20 @@
-"""Turns $RAW_DIR/<round>/ (default build/profiles/<round>/, made by tools/gpu_round_profile.sh on the GPU box) into the small files
+"""usage: summarize_profiles.py ROUND RAW_DIR. Turns RAW_DIR (tools/README.md: `gpu.py kstats c2 --steps 100` and `gpu.py pmc c2 --steps 20
+--set fetch write sq1` with `--out RAW_DIR`, and RAW_DIR/bench.json = the lines of three `bench.py --full` runs) into the small files
 committed under profiles/: per-kernel rocprofv3 --stats table, PMC byte counters per launch with the
 gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md (x2 for 16-B-per-lane streams), the bench line."""
 import csv, glob, json, os, sys, collections
-R = sys.argv[1] if len(sys.argv) > 1 else "r02"
-src = os.path.join(os.environ.get("RAW_DIR", "build/profiles"), R)
+if len(sys.argv) != 3: sys.exit(__doc__)
+R, src = sys.argv[1], sys.argv[2]
 os.makedirs("profiles", exist_ok=True)
-st = sorted(glob.glob(f"{src}/stats/**/*_kernel_stats.csv", recursive=True), key=os.path.getmtime)[-1]
+st = sorted(glob.glob(f"{src}/kstats_c2/**/*_kernel_stats.csv", recursive=True), key=os.path.getmtime)[-1]
 rows = list(csv.DictReader(open(st)))
 with open(f"profiles/{R}_kernel_stats.csv", "w") as f:
     f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extra (MI355X)\n")
     w = csv.writer(f); w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs"])
     for r in rows: w.writerow([r["Name"], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]])
 pmc = collections.defaultdict(dict)
-for c in ("FETCH_SIZE", "WRITE_SIZE", "SQ"):
-    fs = sorted(glob.glob(f"{src}/pmc_{c}/**/*_counter_collection.csv", recursive=True), key=os.path.getmtime)
+for c in ("fetch", "write", "sq1"):
+    fs = sorted(glob.glob(f"{src}/pmc_c2/{c}/**/*_counter_collection.csv", recursive=True), key=os.path.getmtime)
     if not fs: continue
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(fs[-1])):

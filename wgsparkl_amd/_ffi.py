@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import sys
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 
@@ -24,8 +25,13 @@ class WgsError(RuntimeError):
         self.code = code
 
 
+# Developer override, read once per process like WGS_DEBUG and WGS_REHASH_PERIOD: a directory that holds both libraries of
+# a variant (tools/build_variant.sh). A variant is chosen by path, never by copying it over the tree's libraries.
+_LIB_DIR = os.environ.get("WGS_LIB_DIR") or None
+
+
 def lib_path(dim: int) -> str:
-    return os.path.join(_CSRC, f"libwgsparkl{dim}d_hip.so")
+    return os.path.join(_LIB_DIR or _CSRC, f"libwgsparkl{dim}d_hip.so")
 
 
 def build(force: bool = False) -> None:
@@ -218,6 +224,8 @@ def load(dim: int):
         import torch  # noqa: F401
     except Exception:  # torch is optional for the single-GPU path
         pass
+    if _LIB_DIR:   # nothing produced from a variant is silent about it
+        print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
     for name, (restype, argtypes) in prototypes(T).items():
