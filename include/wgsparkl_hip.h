@@ -219,7 +219,8 @@ const char *wgs_build_info(void);
  * wgs_set_particle_models by symbol lookup. Still 7: wgs_grid_sample, wgs_sample_grid[_device] and wgs_read_grid_window[_device] were
  * added the same way (one new struct and four new symbols) — detect wgs_sample_grid by symbol lookup. Still 7: wgs_particle_field and
  * wgs_read_particle_fields[_device] were added the same way (one new struct and two new symbols) —
- * detect wgs_read_particle_fields by symbol lookup. */
+ * detect wgs_read_particle_fields by symbol lookup. Still 7: wgs_wall and wgs_set_domain_walls / wgs_get_domain_walls were added the
+ * same way (one new struct, one enum and two new symbols) — detect wgs_set_domain_walls by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -374,6 +375,41 @@ wgs_status wgs_set_uniform_material(wgs_data *data, float mass, float init_volum
  * substep rebuilds the table. enabled = 0 restores the fixed capacity; WGS_ERR_GRID_OVERFLOW remains for growth that
  * outruns the check (more than half a capacity of new blocks inside one call). */
 wgs_status wgs_set_grid_growth(wgs_data *data, int32_t enabled);
+/* Domain walls. NEW: the reference builds every container from CPIC collider cuboids; a wall is the cheap form for a boundary that
+ * never moves and is axis-aligned — a boundary condition on the grid, one short launch between the grid update and G2P, no collider
+ * slot. A face is a half-space of grid NODES in world cell coordinates, the integers wgs_read_grid reports in wgs_node_record.cell:
+ * the low face of axis k holds every node with cell[k] <= plane, the high face every node with cell[k] >= plane. Planes are
+ * integers on purpose: membership is exact, independent of the cell width, and the same on host and device.
+ * A node inside a face, after the grid update (velocity v, mass untouched), with vn = the component INTO the wall (-v[k] on a low
+ * face, +v[k] on a high one) and vt = the other components:
+ *   WGS_WALL_STICKY    v = 0 in every component;
+ *   WGS_WALL_SLIP      v[k] = 0, then vt *= max(0, 1 - friction * |vn| / |vt|) — Coulomb friction in velocity form; |vt| == 0
+ *                      leaves vt alone, friction == 0 leaves vt bit for bit;
+ *   WGS_WALL_SEPARATE  like WGS_WALL_SLIP where vn > 0, otherwise the node is left bit for bit.
+ * A node inside several faces (edges, corners) takes them one after the other on the running value, in the order of the array:
+ * axis 0 low, axis 0 high, axis 1 low, axis 1 high[, axis 2 low, axis 2 high].
+ * walls[2*k] = low face of axis k, walls[2*k+1] = its high face, 2 * WGS_DIM entries; walls == NULL removes all walls. Stream-ordered
+ * like the other setters: the substeps enqueued after the call use it. The walls travel as a kernel argument: no device memory
+ * (wgs_stats.device_bytes does not change), no upload; data without walls launches exactly what it launched before.
+ * wgs_read_grid, wgs_sample_grid, wgs_read_grid_window and the WGS_DIAG_GRID sums see the velocities AFTER the walls; the time of
+ * the launch is reported under WGS_PASS_GRID_UPDATE. Colliders and walls may be used together: the walls act on the node values
+ * the CPIC paths read.
+ * Containment: a particle with x[k] < (plane - 0.5) h has its whole stencil inside the low face, so what it gathers from a sticky,
+ * slip or separating face has no velocity into the wall; the speed cap h / dt moves a particle at most h per substep. Every
+ * particle therefore keeps (low.plane - 1.5) h <= x[k] <= (high.plane + 1.5) h — a bound for fast material, not the rest
+ * position. Measured (notes/round_26.md: a column settled for 6 000 substeps in a box of walls, h = 1): the lowest particles rest
+ * 0.06 h (Tait fluid, slip) to 0.38 h (Tait fluid, sticky) and 0.27-0.49 h (neo-Hookean) on the INNER side of the low plane, none
+ * beyond it. So a scene that wants material to rest on a surface puts the plane on it (Wall.low / Wall.high of the Python mirror),
+ * and a scene that must never see a particle beyond a surface — a render box, a sensor — places the plane a cell and a half inside
+ * that surface: the surface it is guaranteed lies a cell and a half outside the plane it sets.
+ * Errors (nothing is changed): type > 3, a friction that is not finite or is negative, both faces of an axis set with
+ * low.plane >= high.plane, NULL data / NULL out -> WGS_ERR_INVALID_ARGUMENT; sharded data (wgs_data_create_sharded) ->
+ * WGS_ERR_UNSUPPORTED, like wgs_sample_grid. */
+enum { WGS_WALL_NONE = 0, WGS_WALL_STICKY = 1, WGS_WALL_SLIP = 2, WGS_WALL_SEPARATE = 3 };
+typedef struct { uint32_t type; float friction; int32_t plane; } wgs_wall;   /* 12 bytes, both dimensions */
+wgs_status wgs_set_domain_walls(wgs_data *data, const wgs_wall *walls /* 2*WGS_DIM, or NULL */);
+/* What wgs_set_domain_walls last took (2 * WGS_DIM entries); all WGS_WALL_NONE when none is set. */
+wgs_status wgs_get_domain_walls(wgs_data *data, wgs_wall *out);
 /* Environment (read once per wgs_data_create; developer switches, none of them changes a result): WGS_DEBUG = bit mask of
  * launch-SHAPE choices (two launches instead of one paired launch, the general binning pass on every substep, the grid
  * update and the message packing as launches of their own instead of workgroups of the P2G launch, ...) and

@@ -133,6 +133,18 @@ class MpmData {
         check(wgs_read_particle_models(h_, out.data()));
         return out;
     }
+    // domain walls (no reference counterpart): 2 * WGS_DIM faces, [2 k] the low face of axis k (nodes with cell[k] <= plane), [2 k + 1]
+    // its high face (cell[k] >= plane); the nodes inside a face have their velocity projected after the grid update (sticky / slip with
+    // Coulomb friction / separating). An empty vector removes all walls. Stream-ordered; no device memory.
+    void set_domain_walls(const std::vector<wgs_wall> &walls) {
+        if (!walls.empty() && walls.size() != 2 * WGS_DIM) throw Error(WGS_ERR_INVALID_ARGUMENT, "set_domain_walls: 2 * WGS_DIM faces");
+        check(wgs_set_domain_walls(h_, walls.empty() ? nullptr : walls.data()));
+    }
+    std::vector<wgs_wall> domain_walls() {
+        std::vector<wgs_wall> out(2 * WGS_DIM);
+        check(wgs_get_domain_walls(h_, out.data()));
+        return out;
+    }
     // device.poll(Maintain::Wait) (src/pipeline.rs:339); also reports device-side sticky errors (grid overflow, key range)
     void sync() { check(wgs_sync(h_)); }
     // the per-frame host -> device writes of src_testbed/step.rs:79-119 and ui.rs:91-104

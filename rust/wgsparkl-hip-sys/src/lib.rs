@@ -219,6 +219,19 @@ pub struct wgs_particle_field {
     pub model: u32,
 }
 
+/// One face of the domain walls (include/wgsparkl_hip.h "Domain walls"): 12 bytes in both dimensions.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_wall {
+    pub type_: u32, // WGS_WALL_*
+    pub friction: f32,
+    pub plane: i32, // world cell coordinate: the low face holds cell[k] <= plane, the high face cell[k] >= plane
+}
+pub const WGS_WALL_NONE: u32 = 0;
+pub const WGS_WALL_STICKY: u32 = 1;
+pub const WGS_WALL_SLIP: u32 = 2;
+pub const WGS_WALL_SEPARATE: u32 = 3;
+
 #[repr(C)]
 pub struct wgs_comm {
     _private: [u8; 0],
@@ -274,6 +287,10 @@ extern "C" {
     /// WGS_ABI_VERSION of the header the library was built from; a binding compares it with `ABI_VERSION` once after loading
     pub fn wgs_abi_version() -> u32;
     pub fn wgs_set_grid_growth(d: *mut wgs_data, enabled: i32) -> wgs_status;
+    /// domain walls: `walls` = 2 * DIM faces ([2 k] low, [2 k + 1] high face of axis k) or null to remove them; stream-ordered, no
+    /// device memory. Detect by symbol lookup on older libraries.
+    pub fn wgs_set_domain_walls(d: *mut wgs_data, walls: *const wgs_wall) -> wgs_status;
+    pub fn wgs_get_domain_walls(d: *mut wgs_data, out: *mut wgs_wall) -> wgs_status;
     pub fn wgs_set_uniform_material(d: *mut wgs_data, mass: f32, init_volume: f32, lambda: f32, mu: f32) -> wgs_status;
     /// reproducible sums, bounds and state digest, reduced on the device; blocking / stream-ordered into DEVICE memory
     pub fn wgs_read_diagnostics(d: *mut wgs_data, what: u32, out: *mut wgs_diagnostics) -> wgs_status;

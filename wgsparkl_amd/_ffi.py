@@ -116,6 +116,14 @@ class DevicePtrs(C.Structure):
                 ("dim", C.c_uint32), ("reserved", C.c_uint32), ("hip_stream", C.c_void_p)]
 
 
+class Wall(C.Structure):
+    """wgs_wall (include/wgsparkl_hip.h "Domain walls"): one face; the same struct in both dimensions."""
+    _fields_ = [("type", C.c_uint32), ("friction", C.c_float), ("plane", C.c_int32)]
+
+
+WALL_NONE, WALL_STICKY, WALL_SLIP, WALL_SEPARATE = 0, 1, 2, 3   # WGS_WALL_*
+
+
 # wgs_diagnostics (include/wgsparkl_hip.h "Device-side diagnostics"): the same struct in both dimensions
 DIAG_PARTICLES, DIAG_ENERGY, DIAG_GRID, DIAG_DIGEST = 1, 2, 4, 8
 DIAG_ALL = DIAG_PARTICLES | DIAG_ENERGY | DIAG_GRID | DIAG_DIGEST
@@ -175,6 +183,8 @@ def prototypes(T):
         "wgs_get_stats": (st, [vp, P(T.Stats)]),
         "wgs_set_uniform_material": (st, [vp, f32, f32, f32, f32]),
         "wgs_set_grid_growth": (st, [vp, i32]),
+        "wgs_set_domain_walls": (st, [vp, P(Wall)]),
+        "wgs_get_domain_walls": (st, [vp, P(Wall)]),
         "wgs_debug_scan": (st, [vp, u32p, u32, u32p, u32p]),
         # multi-GPU (x-slab decomposition; new design, no reference counterpart)
         "wgs_data_create_sharded": (st, [vp, P(T.SimParams), P(T.Particle), size, u32p, P(T.Collider), size, f32, u32, u32,

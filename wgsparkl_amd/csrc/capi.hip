@@ -52,3 +52,5 @@ using namespace wgs;
 #include "capi_probe.inc"        // ... extern "C": wgs_sample_grid[_device], wgs_read_grid_window[_device]
 #include "kernels_fields.h"      // Lagrangian field output: per-particle stress and strain (behind them, likewise) ...
 #include "capi_fields.inc"       // ... extern "C": wgs_read_particle_fields[_device]
+#include "kernels_walls.h"       // domain walls: the projection of the wall nodes' velocities (behind them, likewise) ...
+#include "capi_walls.inc"        // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_domain_walls

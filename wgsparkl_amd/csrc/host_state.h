@@ -278,6 +278,10 @@ struct wgs_data {
     // the capacity it was sized for, and the ticket of the last call
     uint32_t *probe_mark = nullptr;
     uint32_t probe_mark_cap = 0, probe_ticket = 0;
+    // domain walls (capi_walls.inc): what wgs_set_domain_walls last took, face by face; `walls_set`: some face is not WGS_WALL_NONE —
+    // enqueue_finish then launches k_grid_walls behind the grid update, with these as its argument (no device memory)
+    wgs_wall walls[2 * WGS_DIM] = {};
+    bool walls_set = false;
 
     // ---- allocation: every device buffer above and in `dev` (dev_alloc; wgs_data_destroy releases them all)
     DeviceMemory mem;

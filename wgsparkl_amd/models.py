@@ -95,3 +95,31 @@ class ParticlePhase:
     """src/solver/particle_update.rs:35-40"""
     phase: float
     max_stretch: float
+
+
+# Domain walls (include/wgsparkl_hip.h WGS_WALL_*; no reference counterpart: the reference builds its containers from collider cuboids)
+WALL_NONE = 0
+WALL_STICKY = 1      # v = 0
+WALL_SLIP = 2        # normal component 0, Coulomb friction on the rest
+WALL_SEPARATE = 3    # like WALL_SLIP for nodes moving into the wall, free otherwise
+
+
+@dataclass(frozen=True)
+class Wall:
+    """One face of `MpmData.set_domain_walls`: a half-space of grid nodes, `cell[k] <= plane` (a low face) or `cell[k] >= plane` (a high
+    face) — which axis and which side is the entry's place in the list (2 * k: low face of axis k, 2 * k + 1: its high face). Material comes
+    to rest on the inner side of the plane (the lowest particles 0.1 to 0.5 cells inside it), so the plane goes on the surface wanted; no
+    particle ever gets further than 1.5 cells beyond it."""
+    type: int = WALL_SLIP
+    friction: float = 0.0
+    plane: int = 0
+
+    @staticmethod
+    def low(coordinate: float, h: float, type: int = WALL_SLIP, friction: float = 0.0) -> "Wall":
+        """The low face whose last node is the one at or below world coordinate `coordinate`: plane = floor(coordinate / h)."""
+        return Wall(int(type), float(friction), int(math.floor(coordinate / h)))
+
+    @staticmethod
+    def high(coordinate: float, h: float, type: int = WALL_SLIP, friction: float = 0.0) -> "Wall":
+        """The high face whose first node is the one at or above `coordinate`: plane = ceil(coordinate / h)."""
+        return Wall(int(type), float(friction), int(math.ceil(coordinate / h)))

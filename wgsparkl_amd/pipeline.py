@@ -430,7 +430,37 @@ class MpmData(DataHandle):
         """`new` from one of the dicts `wgsparkl_amd.scenes` returns (a missing "model" is MODEL_COROTATED); a keyword replaces the
         scene's entry of that name for this call: `colliders=[]`, `grid_capacity=128`, `particles=snap`."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
-        return cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+        data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+        if sc.get("walls") is not None:
+            data.set_domain_walls(sc["walls"])
+        return data
+
+    def set_domain_walls(self, walls):
+        """`wgs_set_domain_walls`: 2 * dim faces, `walls[2 * k]` the low face of axis k and `walls[2 * k + 1]` its high face, each a
+        `models.Wall` (or a (type, friction, plane) triple) or None for no wall there; `None` for the whole list removes all walls.
+        The nodes inside a face have their velocity projected after the grid update. Stream-ordered; no device memory."""
+        if walls is None:
+            _ffi.check(self.lib, self.lib.wgs_set_domain_walls(self._h, None))
+            return
+        walls = list(walls)
+        if len(walls) != 2 * self.dim:
+            raise ValueError("set_domain_walls: 2 * dim entries (low and high face of every axis)")
+        arr = (_ffi.Wall * (2 * self.dim))()
+        for f, w in enumerate(walls):
+            if w is None:
+                continue
+            t, fr, pl = (w.type, w.friction, w.plane) if hasattr(w, "plane") else w
+            if int(t) < 0 or int(pl) != pl:
+                raise ValueError("set_domain_walls: type is a WALL_* value, plane an integer")
+            arr[f].type, arr[f].friction, arr[f].plane = int(t), float(fr), int(pl)
+        _ffi.check(self.lib, self.lib.wgs_set_domain_walls(self._h, arr))
+
+    def domain_walls(self):
+        """`wgs_get_domain_walls`: the 2 * dim faces as `models.Wall` (type WALL_NONE where there is none)."""
+        from .models import Wall
+        arr = (_ffi.Wall * (2 * self.dim))()
+        _ffi.check(self.lib, self.lib.wgs_get_domain_walls(self._h, arr))
+        return [Wall(int(w.type), float(w.friction), int(w.plane)) for w in arr]
 
     def set_particle_models(self, models):
         """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —

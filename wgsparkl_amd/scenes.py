@@ -9,8 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, DruckerPrager,
-                     ElasticCoefficients, FluidCoefficients, ParticlePhase)
+from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, WALL_SLIP, DruckerPrager,
+                     ElasticCoefficients, FluidCoefficients, ParticlePhase, Wall)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -307,28 +307,43 @@ def tait_fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, ce
     return sc
 
 
-def dam_break(nx=24, ny=40, nz=16, jitter=0.05, cell_width=1.0, density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0):
+def _container(walls):
+    if walls not in ("colliders", "grid"):
+        raise ValueError(f"walls={walls!r}: 'colliders' (CPIC cuboids) or 'grid' (domain walls, MpmData.set_domain_walls)")
+    return walls == "grid"
+
+
+def dam_break(nx=24, ny=40, nz=16, jitter=0.05, cell_width=1.0, density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0,
+              walls="colliders", wall_type=WALL_SLIP, wall_friction=0.0):
     """Small dam break for tests: a column of Tait fluid (MODEL_FLUID) standing on the floor cuboid, one face against a wall
     cuboid, free to collapse along +x. Both colliders are within reach of the column from the first substep, so the
-    near-collider list walk and the CPIC paths of the fused G2P advance fluid particles at once."""
+    near-collider list walk and the CPIC paths of the fused G2P advance fluid particles at once.
+    `walls="grid"`: no cuboids; the same floor and wall as domain walls (scene key "walls"), their planes on the cuboids' faces."""
     h = cell_width
     origin = (8.3 * h, 2.2 * h, 8.0 * h)                       # floor top at y = 2 h, wall face at x = 8 h
     pos = lattice((nx, ny, nz), origin, h, jitter)
     ps = ParticleSet.uniform(pos, h / 4.0, density, FluidCoefficients(bulk_modulus, viscosity), phase=ParticlePhase(1.0, FLT_MAX))
     colliders = [Collider.cuboid((1000.0 * h, 2.0 * h, 1000.0 * h), (0.0, 0.0, 0.0)),
                  Collider.cuboid((2.0 * h, 1000.0 * h, 1000.0 * h), (6.0 * h, 0.0, 0.0))]
-    return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0), dt=1.0 / 1200.0), colliders=colliders,
-                cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma))
+    sc = dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0), dt=1.0 / 1200.0), colliders=colliders,
+              cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma))
+    if _container(walls):
+        sc["colliders"] = []
+        sc["walls"] = [Wall.low(8.0 * h, h, wall_type, wall_friction), None, Wall.low(2.0 * h, h, wall_type, wall_friction), None, None, None]
+    return sc
 
 
 def block_in_fluid(dim=3, tank=(24, 16, 16), block=8, gap=0.5, drop_speed=0.0, solid_model=MODEL_NEO_HOOKEAN, jitter=0.05, cell_width=1.0,
-                   density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, solid_density=2000.0, young_modulus=2.0e5, poisson=0.3):
+                   density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, solid_density=2000.0, young_modulus=2.0e5, poisson=0.3,
+                   walls="colliders", wall_type=WALL_SLIP, wall_friction=0.0):
     """Fluid and solid in one simulation (MpmData.set_particle_models): a tank of Tait fluid — `tank` particles at spacing h/2 standing on
     the floor cuboid between four wall cuboids (two in 2D), like `dam_break` but closed — and an elastic block of `block`^dim particles
     hanging `gap` cells above the middle of its surface, falling at `drop_speed`. The two interact through the grid alone. Returns the
     scene dict with "models" (np.uint8 per particle: MODEL_FLUID for the tank, `solid_model` for the block) and "solid_model";
     "model" (the data's single model, before the table is set) is the solid's: selecting the fluid for the whole data would collapse the
-    block's deformation gradient too. The fluid's particles come first."""
+    block's deformation gradient too. The fluid's particles come first.
+    `walls="grid"`: no cuboids; the same tank as domain walls (scene key "walls": the floor and the side faces, open at the top), their
+    planes on the first node at or beyond the cuboids' faces."""
     h = cell_width
     tank = tuple(tank)[:dim] if dim == 3 else (tank[0], tank[1])
     origin = (8.3 * h, 2.2 * h, 8.3 * h)[:dim]                 # floor top at y = 2 h, wall faces 0.3 h off the fluid
@@ -356,8 +371,32 @@ def block_in_fluid(dim=3, tank=(24, 16, 16), block=8, gap=0.5, drop_speed=0.0, s
                      Collider.cuboid((t, big), (x0 - t, 0.0), rotation=(0.0,)), Collider.cuboid((t, big), (x1 + t, 0.0), rotation=(0.0,))]
     models = np.full(ps.n, MODEL_FLUID, np.uint8)
     models[nf:] = solid_model
-    return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0), colliders=colliders,
-                cell_width=h, grid_capacity=4096, model=int(solid_model), fluid_gamma=float(gamma), models=models, solid_model=int(solid_model))
+    sc = dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0), colliders=colliders,
+              cell_width=h, grid_capacity=4096, model=int(solid_model), fluid_gamma=float(gamma), models=models, solid_model=int(solid_model))
+    if _container(walls):
+        sc["colliders"] = []
+        sc["walls"] = [Wall.low(x0, h, wall_type, wall_friction), Wall.high(x1, h, wall_type, wall_friction),
+                       Wall.low(2.0 * h, h, wall_type, wall_friction), None]
+        if dim == 3:
+            sc["walls"] += [Wall.low(z0, h, wall_type, wall_friction), Wall.high(z1, h, wall_type, wall_friction)]
+    return sc
+
+
+def walled_box(dim=3, n=6000, lo=2, hi=18, wall_type=WALL_SLIP, friction=0.0, cell_width=1.0, speed=1.0, seed=11, with_walls=True,
+               young=2.0e4, density=10.0):
+    """A cloud thrown at all 2 * dim faces of a box of domain walls, no colliders, no gravity: `n` soft elastic particles scattered
+    over the cells (lo + 2 .. hi - 2)^dim, each moving away from the centre of the box at up to `speed` times the grid's cap h / dt. The low planes are `lo`, the high planes `hi` (scene key "walls"; `with_walls=False`: none, the cloud flies apart)."""
+    h = float(cell_width)
+    rng = np.random.default_rng(seed)
+    pos = rng.uniform((lo + 2.0) * h, (hi - 2.0) * h, size=(n, dim)).astype(F32)
+    ps = ParticleSet.uniform(pos, h / 4.0, density, ElasticCoefficients.from_young_modulus(young, 0.3), phase=ParticlePhase(1.0, FLT_MAX))
+    params = SimulationParams(gravity=(0.0,) * dim, dt=1.0 / 1200.0)
+    # (away from the centre: neighbours move alike, so the transfers do not average the motion away as they would random directions)
+    direction = pos.astype(np.float64) - 0.5 * (lo + hi) * h + rng.normal(0.0, 0.05 * h, size=(n, dim))
+    direction /= np.linalg.norm(direction, axis=1, keepdims=True)
+    ps.vel[:] = (direction * rng.uniform(0.5, 1.0, size=(n, 1)) * (speed * h / params.dt)).astype(F32)
+    walls = [Wall(int(wall_type), float(friction), int(lo if f % 2 == 0 else hi)) for f in range(2 * dim)] if with_walls else None
+    return dict(particles=ps, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED, walls=walls)
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):
