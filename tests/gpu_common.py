@@ -283,20 +283,6 @@ def _bed_scene(d, h, n=None, drift=0.0):
     return sc
 
 
-def _native_slabs(sc, world, pipe, part=None, **kw):
-    """The scene cut into `world` x-slabs balanced by particle count (or by the given SlabPartition), each a NativeShard of a lockstep group."""
-    from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, split_scene, uniform_material_of
-    ps = sc["particles"]
-    part = part or SlabPartition.balanced(associated_block_x(ps.pos, sc["cell_width"], ps.dim), world)
-    shards = []
-    for r, (sub, gids) in enumerate(split_scene(ps, part, sc["cell_width"])):
-        lo, hi = part.block_range(r)
-        shards.append(NativeShard(pipe, sc["params"], sub, gids, sc["colliders"], sc["cell_width"], sc["grid_capacity"],
-                                  lo, hi, r > 0, r < world - 1, particle_capacity=ps.n, model=sc["model"],
-                                  uniform_material=uniform_material_of(ps), **kw))
-    return shards, part
-
-
 def _export_records(shard):
     """the exchange records of the particles a slab holds [count, floats per record]: every quad of the particle, its global id
     and the substep its cdf was computed in"""
@@ -348,7 +334,7 @@ def export_state_and_cdf(shards, n, d):
 
 
 def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):
-    """`nsteps` lockstep substeps of the scene's two slabs (_native_slabs), each with the poses read before it: every particle
+    """`nsteps` lockstep substeps of the scene's two slabs (sharded.lockstep_slabs), each with the poses read before it: every particle
     against the truth of the whole domain (the samples of a mesh collider included; without one mesh_truth.rigid_of gives
     None), the nodes of each slab's own blocks against the truth restricted to them, and no collider-affine node of a
     slab's range missing from its grid. Returns, per substep, whether collider 1 votes at a node past the cut."""

@@ -3,8 +3,8 @@ binning inside the fused G2P or as a launch of its own, across a checkpoint / re
 import numpy as np
 import pytest
 
-from wgsparkl_amd import MpmData, scenes
-from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
+from wgsparkl_amd import MpmData, _ffi, scenes
+from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, WALL_NONE, DruckerPrager, ElasticCoefficients, ParticlePhase)
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
 from helpers import (AFFINITY_FIELDS, BASE_FIELDS, CDF_FIELDS, PLASTIC_FIELDS, assert_same_bits, assert_same_bodies, assert_same_grid, debug,
@@ -465,15 +465,33 @@ def test_large_two_way_scenes_with_the_near_collider_launch_first_give_the_bits_
 def test_from_scene_builds_what_new_builds(hip_libs, dim):
     """MpmData.from_scene is MpmData.new with the scene's entries: the same small scene (a floor under it) created both ways and advanced
     two substeps ends with the same bits in the particles, the grid and the body poses, and the same counters; a keyword replaces the
-    scene's entry."""
+    scene's entry. Then a scene with every optional key (a small block_in_fluid between grid walls, Tait exponent 5): MpmData.new and
+    the three setters by hand against from_scene — the same digest, particles, per-particle models and walls after two substeps; and
+    `models=None` builds it without its table."""
+    pipe = pipeline(dim)
+
+    def spelled(sc):
+        return MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+
     sc = scenes.neo_hookean_cube(n_side=8, with_floor=True) if dim == 3 else scenes.elastic_block_2d(22, 22)
     assert sc["particles"].n == (512 if dim == 3 else 484)
-    pipe = pipeline(dim)
-    spelled = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-    a, b = step_chunks(spelled, (2,)), step_chunks(MpmData.from_scene(pipe, sc), (2,))
+    a, b = step_chunks(spelled(sc), (2,)), step_chunks(MpmData.from_scene(pipe, sc), (2,))
     assert_same_bits(a.read_particles(), b.read_particles(), CDF_FIELDS)
     assert_same_grid(a.read_grid(), b.read_grid())
     assert a.n_colliders == b.n_colliders == len(sc["colliders"])
     assert_same_bodies(a.read_body_poses(), b.read_body_poses())
     assert a.stats() == b.stats()
     assert MpmData.from_scene(pipe, sc, colliders=[]).n_colliders == 0
+
+    sc = scenes.block_in_fluid(dim, tank=(12, 8, 8) if dim == 3 else (24, 12), block=4, gap=0.1, drop_speed=6.0, walls="grid", gamma=5.0)
+    assert sc["fluid_gamma"] == 5.0 and sc["walls"] is not None and len(np.unique(sc["models"])) == 2 and sc["particles"].n <= 10_000
+    a = spelled(sc)
+    a.set_fluid_eos(sc["fluid_gamma"])
+    a.set_particle_models(sc["models"])
+    a.set_domain_walls(sc["walls"])
+    a, b = step_chunks(a, (2,)), step_chunks(MpmData.from_scene(pipe, sc), (2,))
+    assert a.diagnostics(_ffi.DIAG_DIGEST).digest == b.diagnostics(_ffi.DIAG_DIGEST).digest
+    assert_same_bits(a.read_particles(), b.read_particles(), CDF_FIELDS)
+    assert np.array_equal(a.read_particle_models(), b.read_particle_models()) and np.array_equal(b.read_particle_models(), sc["models"])
+    assert a.domain_walls() == b.domain_walls() and any(w.type != WALL_NONE for w in b.domain_walls())
+    assert np.all(MpmData.from_scene(pipe, sc, models=None).read_particle_models() == sc["model"])

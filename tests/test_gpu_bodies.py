@@ -153,15 +153,15 @@ def test_two_lockstep_slabs(hip_libs, d):
     holds (guests included) and the group adds the integers, so the truth truncates per (node, rank); 8 substeps, then two
     checked ones. The nodes' affinities and closest ids are cdf_truth's (no pair may touch an undecided node); the poses are
     read from either rank."""
-    from gpu_common import _native_slabs, export_state_and_cdf
-    from wgsparkl_amd.sharded import SlabPartition, associated_block_x, native_lockstep
+    from gpu_common import export_state_and_cdf
+    from wgsparkl_amd.sharded import SlabPartition, associated_block_x, lockstep_slabs, native_lockstep
     import cpic_truth as CP
     h = 0.2 if d == 2 else 0.25
     sc = _dynamic_bed(d, h)
     ps = sc["particles"]
     pipe = pipeline(d)
     bx = associated_block_x(ps.pos, h, d)
-    shards, part = _native_slabs(sc, 2, pipe, part=SlabPartition([int(bx.min()), 3, int(bx.max()) + 1]))     # (the ball hangs over block 3's first cell)
+    shards, part = lockstep_slabs(pipe, sc, 2, part=SlabPartition([int(bx.min()), 3, int(bx.max()) + 1]))     # (the ball hangs over block 3's first cell)
     bw = T.bw_of(d)
     cut = part.block_range(1)[0] * bw * h
     ball_x = shards[0].read_body_poses()[1]["translation"][0]

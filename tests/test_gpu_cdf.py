@@ -16,9 +16,10 @@ import pytest
 import cdf_truth as CT
 import mesh_truth as MT
 import transfer_truth as T
-from gpu_common import _native_slabs, blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
+from gpu_common import blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
 from helpers import debug, new_data, pipeline, report_margin, run_oracle
 from wgsparkl_amd import _ffi
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
@@ -154,13 +155,13 @@ def test_lockstep_slabs_of_the_moving_ball_scene(hip_libs, d):
     sc, _, _ = _ball_scene(d, h)
     ps = sc["particles"]
     pipe = pipeline(d)
-    shards, part = _native_slabs(sc, 2, pipe)
+    shards, part = lockstep_slabs(pipe, sc, 2)
     cut = part.block_range(1)[0]
     for s in shards:
         s.close()
     sc, floor, ball = _ball_scene(d, h, ball_x=cut * bw - 3.7)       # (its reach ends 3 h ahead of its centre)
     assert np.array_equal(sc["particles"].pos, ps.pos)
-    shards, part = _native_slabs(sc, 2, pipe)
+    shards, part = lockstep_slabs(pipe, sc, 2)
     fails = []
     crossed = check_lockstep_slabs(f"slabs moving ball {d}D", sc, shards, part, 4, fails)
     for s in shards:

@@ -20,8 +20,9 @@ import pytest
 import cdf_truth as CT
 import cpic_truth as CP
 import transfer_truth as T
-from gpu_common import _bed_scene, _native_slabs, checked_cpic_substep, export_state_and_cdf
+from gpu_common import _bed_scene, checked_cpic_substep, export_state_and_cdf
 from helpers import debug, new_data, pipeline, report_margin
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider, SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -171,7 +172,7 @@ def test_lockstep_slabs_particle_by_particle(hip_libs, d):
     sc = _bed_scene(d, h, n=12000 if d == 2 else 6000, drift=0.5)
     ps = sc["particles"]
     pipe = pipeline(d)
-    shards, part = _native_slabs(sc, 2, pipe)
+    shards, part = lockstep_slabs(pipe, sc, 2)
     lo_hi = np.array([part.block_range(r) for r in range(2)])
 
     def run(k):

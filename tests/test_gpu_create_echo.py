@@ -9,10 +9,11 @@ import pytest
 
 from wgsparkl_amd import MpmData, scenes
 from wgsparkl_amd.models import DruckerPrager, ParticlePhase
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import SimulationParams
 
 from helpers import pipeline
-from gpu_common import _native_slabs, export_state_and_cdf
+from gpu_common import export_state_and_cdf
 
 pytestmark = pytest.mark.gpu
 
@@ -146,7 +147,7 @@ def test_two_slabs_export_the_state_and_ids_they_were_given(hip_libs, dim):
     given = ps.copy()
     sc = dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1e-3), colliders=[], cell_width=1.0,
               grid_capacity=1024, model=0)
-    shards, part = _native_slabs(sc, 2, pipeline(dim))
+    shards, part = lockstep_slabs(pipeline(dim), sc, 2)
     assert min(s.num_particles() for s in shards) > 0
     state, held, aff, dist, normal = export_state_and_cdf(shards, ps.n, dim)      # (asserts: every id exactly once)
     for f in ("pos", "vel", "def_grad", "affine", "mass"):

@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 import diag_truth as dt
-from gpu_common import _exploding_cube, _native_slabs, cloud_scene
+from gpu_common import _exploding_cube, cloud_scene
 from helpers import BASE_FIELDS, assert_same_bits, assert_same_grid, debug, new_data, pipeline, report_margin, run_gpu, run_oracle
 from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd.models import MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -301,7 +302,7 @@ def test_slabs_add_up_to_the_single_domain(world):
     from wgsparkl_amd.sharded import native_lockstep, unpack_records
     sc = cloud_scene(n=12000, dim=3, extent=30.0)
     pipe = pipeline(3)
-    shards, _ = _native_slabs(sc, world, pipe, force_plastic=True)
+    shards, _ = lockstep_slabs(pipe, sc, world, force_plastic=True)
     native_lockstep(pipe, shards, 6)
     for s in shards:
         s.sync()

@@ -14,11 +14,11 @@ import pytest
 
 import devmath_truth as T
 import field_truth as FT
-from gpu_common import _native_slabs
 from helpers import debug, new_data, pipeline, report_margin
 from test_gpu_constitutive import CASES, _scene
 from wgsparkl_amd import _ffi
 from wgsparkl_amd.models import MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import ParticleSet, SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -33,16 +33,6 @@ CANARY = 0x5a5a5a5a
 def _scene_of(ps, model, **kw):
     return dict(particles=ps, params=SimulationParams(gravity=(0.0,) * ps.dim, dt=DT), colliders=[], cell_width=H, grid_capacity=2048,
                 model=int(model), **kw)
-
-
-def _new(sc):
-    """The scene's data with its Tait exponent and its per-particle table (scene keys "fluid_gamma", "models") set."""
-    _, data = new_data(sc)
-    if "fluid_gamma" in sc:
-        data.set_fluid_eos(sc["fluid_gamma"])
-    if "models" in sc:
-        data.set_particle_models(sc["models"])
-    return data
 
 
 def _device_fields(data, extra=0):
@@ -71,13 +61,13 @@ def test_catalogue_before_the_first_substep(hip_libs, monkeypatch, dim, model, p
     monkeypatch.delenv("WGS_DEBUG", raising=False)
     ps = FT.catalogue_particles(dim, model, per_particle)
     sc = _scene_of(ps, model)
-    data = _new(sc)
+    _, data = new_data(sc)
     fields = _check(f"catalogue model {model} {'per-particle' if per_particle else 'uniform'} {dim}d", data, FT.Inputs.of(ps, model))
     assert np.array_equal(fields.model, np.full(ps.n, model, np.uint32))
     if dim == 3 and not per_particle:
         # the uniform-material layout (F[8] in XM.w, the four constants kernel arguments) against the general one: the same records
         with debug(monkeypatch, "NO_UNIFORM"):
-            general = _new(sc).particle_fields()
+            general = new_data(sc)[1].particle_fields()
         assert general.raw.tobytes() == fields.raw.tobytes(), "the uniform-material layout changes a record"
 
 
@@ -110,7 +100,7 @@ def test_the_stress_is_the_tau_of_the_step_bit_for_bit(hip_libs, monkeypatch, di
     monkeypatch.delenv("WGS_DEBUG", raising=False)
     sc = _elastic_case(name, dim)
     ps = sc["particles"]
-    data = _new(sc)
+    _, data = new_data(sc)
     before = data.particle_fields()
     data.pipeline.step(data, 1)
     data.sync()
@@ -142,7 +132,7 @@ def test_the_stress_of_drucker_prager_data_is_the_tau_of_the_step_to_rounding(hi
     state = np.tile(np.array([1.0, 1.0, 0.0], np.float32), (ps.n, 1))
     if mode == 0:
         state = np.stack([rng.uniform(0.8, 1.2, ps.n), rng.uniform(0.0, 2.0, ps.n), rng.uniform(-0.2, 0.2, ps.n)], 1).astype(np.float32)
-    data = _new(sc)
+    _, data = new_data(sc)
     data.set_plastic_state(state)
     data.pipeline.step(data, 1)
     data.sync()
@@ -166,7 +156,7 @@ def test_the_stress_of_drucker_prager_data_is_the_tau_of_the_step_to_rounding(hi
 
 # ------------------------------------------------------------------------------------------------ 3 order and ping-pong
 def _flight(dim, steps):
-    data = _new(FT.flying_cloud(dim))
+    _, data = new_data(FT.flying_cloud(dim))
     data.pipeline.step(data, steps)
     data.sync()
     return data
@@ -205,7 +195,7 @@ def test_the_last_wave_and_the_last_workgroup(hip_libs, monkeypatch, dim, n):
     monkeypatch.delenv("WGS_DEBUG", raising=False)
     model = n % 2
     ps = FT.catalogue_particles(dim, model, True, n=n, seed=n)
-    data = _new(_scene_of(ps, model))
+    _, data = new_data(_scene_of(ps, model))
     fields = _check(f"tail n={n} {dim}d", data, FT.Inputs.of(ps, model))
     words = _device_fields(data, extra=8)
     assert words[:n].tobytes() == fields.raw.tobytes()
@@ -230,7 +220,7 @@ def test_asking_changes_nothing(hip_libs, monkeypatch, kind):
         return data.diagnostics(_ffi.DIAG_DIGEST).digest
 
     def run(ask):
-        data = _new(make())
+        _, data = new_data(make())
         for k in range(20):
             data.pipeline.step(data, 1)
             if ask:
@@ -253,7 +243,7 @@ def test_asking_changes_nothing(hip_libs, monkeypatch, kind):
 def test_tait_fluid_block_after_24_substeps(hip_libs, monkeypatch):
     monkeypatch.delenv("WGS_DEBUG", raising=False)
     sc = FT.small_tait_block()
-    data = _new(sc)
+    _, data = new_data(sc)
     data.pipeline.step(data, 24)
     data.sync()
     got = data.read_particles()
@@ -270,7 +260,7 @@ def test_tait_fluid_block_after_24_substeps(hip_libs, monkeypatch):
 def test_block_in_fluid_every_particle_under_its_own_model(hip_libs, monkeypatch, dim):
     monkeypatch.delenv("WGS_DEBUG", raising=False)
     sc = FT.small_block_in_fluid(dim)
-    data = _new(sc)
+    _, data = new_data(sc)
     data.pipeline.step(data, 24)
     data.sync()
     got = data.read_particles()
@@ -297,12 +287,12 @@ def test_sharded_data_and_null_outputs_are_refused(hip_libs, monkeypatch, dim):
     dev = torch.full((sc["particles"].n * words,), CANARY, dtype=torch.int32, device="cuda:0")
     torch.cuda.synchronize()
     pout = out.ctypes.data_as(C.POINTER(T_.ParticleField))
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     for s in shards:
         for call in (lambda: lib.wgs_read_particle_fields(s._h, pout), lambda: lib.wgs_read_particle_fields_device(s._h, C.c_void_p(dev.data_ptr()))):
             assert call() == UNSUPPORTED
             assert b"sharded" in lib.wgs_last_error()
-    data = _new(sc)
+    _, data = new_data(sc)
     for call in (lambda: lib.wgs_read_particle_fields(data._h, None), lambda: lib.wgs_read_particle_fields_device(data._h, None),
                  lambda: lib.wgs_read_particle_fields_device(data._h, C.c_void_p(dev.data_ptr() + 4))):     # (not aligned to a vector)
         assert call() == INVALID

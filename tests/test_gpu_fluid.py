@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 import fluid_truth as ft
-from gpu_common import GRID_V_TOL, PART_TOL, _native_slabs
+from gpu_common import GRID_V_TOL, PART_TOL
 from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, rel_rms, report_margin
 from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd._ffi import WgsError
 from wgsparkl_amd.models import MODEL_FLUID, MODEL_NEO_HOOKEAN, DruckerPrager, FluidCoefficients, ParticlePhase
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import ParticleSet, SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -22,15 +23,8 @@ U = 2.0 ** -53
 ELASTIC_ROUNDINGS = 256    # the allowance tests/test_gpu_diagnostics.py gives the elastic sum of the other models
 
 
-def _new(sc):
-    _, data = new_data(sc)
-    if "fluid_gamma" in sc:
-        data.set_fluid_eos(sc["fluid_gamma"])
-    return data
-
-
 def _run(sc, calls=(12, 12)):
-    data = _new(sc)
+    _, data = new_data(sc)
     for k in calls:
         data.pipeline.step(data, k)
     data.sync()
@@ -162,7 +156,7 @@ def test_checkpoint_and_model_switches(hip_libs, dim):
     def switched():
         s = _falling_block(dim, True, 0.0, 7.0)
         s["model"] = MODEL_NEO_HOOKEAN
-        d = _new(s)
+        _, d = new_data(s)
         d.pipeline.step(d, 8)
         pre = d.read_particles()
         d.set_constitutive_model(MODEL_FLUID)
@@ -207,7 +201,7 @@ def test_unsupported_on_plastic_data_and_eos_argument_checks(hip_libs, dim):
     ps = scenes.random_cloud(800, dim=dim, seed=3, young=1e6, plasticity=DruckerPrager.new(1e6, 0.25), phase=None)
     sc = dict(particles=ps, params=SimulationParams((0.0, -9.81, 0.0)[:dim], 8e-4), colliders=[], cell_width=1.0, grid_capacity=4096,
               model=MODEL_NEO_HOOKEAN)
-    data = _new(sc)
+    _, data = new_data(sc)
     with pytest.raises(WgsError) as e:
         data.set_constitutive_model(MODEL_FLUID)
     assert e.value.code == 6                                            # WGS_ERR_UNSUPPORTED
@@ -261,10 +255,8 @@ def test_fluid_block_as_lockstep_slabs_matches_the_single_domain(hip_libs, world
     k = 80
     ref = _run(sc, (k,)).read_particles()
     pipe = pipeline(3)
-    shards, part = _native_slabs(sc, world, pipe)
+    shards, part = lockstep_slabs(pipe, sc, world)
     assert part.min_interior_width() >= 3
-    for s in shards:
-        s.set_fluid_eos(sc["fluid_gamma"])
     n0 = [s.num_particles() for s in shards]
     native_lockstep(pipe, shards, 30)
     native_lockstep(pipe, shards, k - 30)

@@ -144,10 +144,7 @@ def _slab_shards(pipe, make_slab, world, velocity, **caps):
         ps = sc["particles"]
         velocity(ps, sc["global_ids"].astype(np.float64))
         total += ps.n
-        lo, hi = sc["partition"].block_range(rank)
-        shards.append(NativeShard(pipe, sc["params"], ps, sc["global_ids"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], lo, hi,
-                                  rank > 0, rank < world - 1, particle_capacity=int(ps.n * 1.5) + 4096, model=sc["model"],
-                                  uniform_material=uniform_material_of(ps), **caps))
+        shards.append(NativeShard.from_scene(pipe, sc, rank, particle_capacity=int(ps.n * 1.5) + 4096, uniform_material=uniform_material_of(ps), **caps))
     return shards, total
 
 

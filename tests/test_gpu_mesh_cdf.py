@@ -16,8 +16,9 @@ import pytest
 import cdf_truth as CT
 import mesh_truth as MT
 import transfer_truth as T
-from gpu_common import _native_slabs, blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
+from gpu_common import blocks_in_reach, check_blocks, check_lockstep_slabs, checked_substep
 from helpers import debug, new_data, pipeline, report_margin, run_oracle
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
@@ -147,7 +148,7 @@ def test_lockstep_slabs_with_a_mesh_across_the_cut(hip_libs, d):
     sc, _, _ = _moving_mesh_scene(d, h)
     ps = sc["particles"]
     pipe = pipeline(d)
-    shards, part = _native_slabs(sc, 2, pipe)
+    shards, part = lockstep_slabs(pipe, sc, 2)
     cut = part.block_range(1)[0]
     for s in shards:
         s.close()
@@ -158,7 +159,7 @@ def test_lockstep_slabs_with_a_mesh_across_the_cut(hip_libs, d):
     x0 = front - WIDTH[d] if d == 3 else front - WIDTH[d] - (bw + 4.0)
     sc, fixed, sheet = _moving_mesh_scene(d, h, x0=x0)
     assert np.array_equal(sc["particles"].pos, ps.pos)
-    shards, part = _native_slabs(sc, 2, pipe)
+    shards, part = lockstep_slabs(pipe, sc, 2)
     fails = []
     crossed = check_lockstep_slabs(f"slabs moving mesh {d}D", sc, shards, part, 4, fails)
     for s in shards:

@@ -15,7 +15,7 @@ import pytest
 import diag_truth as dt_
 import fluid_truth as ft
 import mixed_truth as mt
-from gpu_common import GRID_V_TOL, PART_TOL, _native_slabs
+from gpu_common import GRID_V_TOL, PART_TOL
 from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, report_margin
 from oracle import np_oracle
 from test_gpu_fluid import ELASTIC_ROUNDINGS, FIELDS, SHAPES
@@ -23,6 +23,7 @@ from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd._ffi import WgsError
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, MODEL_PER_PARTICLE, DruckerPrager, ElasticCoefficients,
                                  FluidCoefficients, ParticlePhase)
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -31,18 +32,8 @@ U = 2.0 ** -53
 ARRAYS = [f.name for f in dataclasses.fields(ParticleSet) if f.name != "dim"]
 
 
-def _new(sc, table=True, model=None):
-    """The scene's data; with `table` its per-particle models are set (scene key "models")."""
-    _, data = new_data(sc, **({} if model is None else {"model": model}))
-    if "fluid_gamma" in sc:
-        data.set_fluid_eos(sc["fluid_gamma"])
-    if table and "models" in sc:
-        data.set_particle_models(sc["models"])
-    return data
-
-
-def _run(sc, calls=(15, 15), **kw):
-    data = _new(sc, **kw)
+def _run(sc, calls=(15, 15), **overrides):
+    _, data = new_data(sc, **overrides)
     for k in calls:
         data.pipeline.step(data, k)
     data.sync()
@@ -252,7 +243,7 @@ def test_diagnostics_and_vertex_buffer_go_by_the_particles_model(hip_libs, dim, 
     sc, _, _ = mt.coupled_truths(dim, solid_model, "random")
     fl = sc["fluid"]
     gamma = sc["fluid_gamma"]
-    data = _new(sc, table=False)
+    _, data = new_data(sc, models=None)
     before = data.diagnostics(_ffi.DIAG_PARTICLES)
     data.set_particle_models(sc["models"])
     after = data.diagnostics(_ffi.DIAG_PARTICLES)
@@ -294,7 +285,7 @@ def test_diagnostics_and_vertex_buffer_go_by_the_particles_model(hip_libs, dim, 
 @pytest.mark.parametrize("dim", [3, 2])
 def test_refusals_leave_the_data_alone(hip_libs, dim):
     sc, _, _ = mt.coupled_truths(dim, MODEL_NEO_HOOKEAN, "plane")
-    data = _new(sc)
+    _, data = new_data(sc)
     data.pipeline.step(data, 3)
     data.sync()
     state = (_digest(data), data.read_particles(), data.read_particle_models())
@@ -353,7 +344,7 @@ def test_refusals_leave_the_data_alone(hip_libs, dim):
 def test_sharded_data_is_refused(hip_libs):
     sc = scenes.tait_fluid_block(32, 16, 16, with_floor=False)
     pipe = pipeline(3)
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     s = shards[0]
     before = s.diagnostics(_ffi.DIAG_DIGEST).digest
     table = np.zeros(sc["particles"].n, np.uint8)

@@ -12,9 +12,9 @@ import pytest
 
 import probe_truth as PT
 import transfer_truth as T
-from gpu_common import _native_slabs
 from helpers import assert_same_grid, new_data, pipeline, report_margin, run_gpu
 from wgsparkl_amd import _ffi, scenes
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -314,7 +314,7 @@ def test_sharded_data_is_refused(hip_libs, d):
     import torch
     sc = _stirred(d)
     pipe = pipeline(d)
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     lib, T_ = pipe.lib, pipe.T
     pts = np.zeros((4, d), np.float32)
     out = (T_.GridSample * 4)()

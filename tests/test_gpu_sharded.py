@@ -5,10 +5,11 @@ import pytest
 
 from wgsparkl_amd import scenes
 from wgsparkl_amd.models import ParticlePhase
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider, SimulationParams
 
 from helpers import debug, max_abs, new_data, pipeline, rel_rms, report_margin, run_gpu
-from gpu_common import FUZZ_BODY_ATOL, _native_slabs
+from gpu_common import FUZZ_BODY_ATOL
 
 from golden_cases import CASES as _CASES
 
@@ -34,11 +35,8 @@ def test_bench_decomposition_eight_ranks_on_one_gpu(hip_libs):
         ps = sc["particles"]
         ps.vel[:, 0] = vx(sc["global_ids"])
         total += ps.n
-        lo, hi = sc["partition"].block_range(rank)
-        shards.append(NativeShard(pipe, sc["params"], ps, sc["global_ids"], sc["colliders"], sc["cell_width"],
-                                  sc["grid_capacity"], lo, hi, rank > 0, rank < world - 1,
-                                  particle_capacity=int(ps.n * 1.25) + 4096, model=sc["model"], uniform_material=uniform_material_of(ps),
-                                  halo_capacity_records=2 * ((n_side // 8 + 3) ** 2 + 32), migrant_capacity=512))
+        shards.append(NativeShard.from_scene(pipe, sc, rank, particle_capacity=int(ps.n * 1.25) + 4096, uniform_material=uniform_material_of(ps),
+                                             halo_capacity_records=2 * ((n_side // 8 + 3) ** 2 + 32), migrant_capacity=512))
     assert total == full["global_particles"] == full["particles"].n
     n0 = [s.num_particles() for s in shards]
     native_lockstep(pipe, shards, k)
@@ -85,7 +83,7 @@ def test_random_scenes_sharded_match_single_domain(hip_libs, seed):
     k = 30
     ref = run_gpu(sc, k).read_particles()
     pipe = pipeline(dim)
-    shards, part = _native_slabs(sc, world, pipe)
+    shards, part = lockstep_slabs(pipe, sc, world)
     assert part.min_interior_width() >= 3
     n0 = [s.num_particles() for s in shards]
     native_lockstep(pipe, shards, k)
@@ -122,10 +120,8 @@ def test_sharded_run_with_kinematic_collider(hip_libs):
     shards = []
     for r in range(world):
         sc = c4(r)
-        lo, hi = sc["partition"].block_range(r)
-        shards.append(NativeShard(pipe, sc["params"], sc["particles"], sc["global_ids"], sc["colliders"], sc["cell_width"], sc["grid_capacity"],
-                                  lo, hi, r > 0, r < world - 1, particle_capacity=full["particles"].n, model=sc["model"],
-                                  uniform_material=uniform_material_of(sc["particles"]), halo_capacity_records=512, migrant_capacity=2048))
+        shards.append(NativeShard.from_scene(pipe, sc, r, particle_capacity=full["particles"].n, uniform_material=uniform_material_of(sc["particles"]),
+                                             halo_capacity_records=512, migrant_capacity=2048))
     n0 = [s.num_particles() for s in shards]
     native_lockstep(pipe, shards, k)
     for s in shards:
@@ -159,7 +155,7 @@ def test_dynamic_bodies_on_sharded_data(hip_libs, name):
     ref = run_gpu(sc, k)
     ref_p, ref_b = ref.read_particles(), ref.read_body_poses()
     pipe = pipeline(dim)
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     assert min(s.num_particles() for s in shards) > 0
     native_lockstep(pipe, shards, k)
     for s in shards:
@@ -207,7 +203,7 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
         ps.vel[:] = rng.normal(0.0, 2.0, ps.vel.shape).astype(np.float32)
         ps.vel[:, 0] += 8.0
         pipe = pipeline(dim)
-        shards, part = _native_slabs(sc, world, pipe)
+        shards, part = lockstep_slabs(pipe, sc, world)
         native_lockstep(pipe, shards, 40)
         for sh in shards:
             sh.sync()                                          # (the near-collider lists are seen here: paired launches from now on)
@@ -255,7 +251,7 @@ def test_native_lockstep_matches_single_domain(hip_libs, world, dim, monkeypatch
     k = 80
     ref = run_gpu(sc, k).read_particles()
     pipe = pipeline(dim)
-    shards, part = _native_slabs(sc, world, pipe)
+    shards, part = lockstep_slabs(pipe, sc, world)
     assert part.min_interior_width() >= 3
     n0 = [s.num_particles() for s in shards]
     native_lockstep(pipe, shards, 30)
@@ -283,7 +279,7 @@ def test_particles_enter_an_empty_slab_and_leave_theirs_empty(hip_libs, with_flo
     the first arrivals find none of their blocks active on their new rank and read their nodes from the message (the old
     owner's partial sums are then the totals; with the floor also the node cdfs, evaluated on the spot) — and keeps going
     until slab 0 is empty. Both against the single-domain run."""
-    from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, native_lockstep, split_scene, uniform_material_of
+    from wgsparkl_amd.sharded import SlabPartition, associated_block_x, native_lockstep
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=with_floor)
     ps = sc["particles"]
     if with_floor:
@@ -294,12 +290,7 @@ def test_particles_enter_an_empty_slab_and_leave_theirs_empty(hip_libs, with_flo
     bx = associated_block_x(ps.pos, sc["cell_width"], 3)
     part = SlabPartition([int(bx.min()), int(bx.max()) + 1, int(bx.max()) + 12])
     pipe = pipeline(3)
-    shards = []
-    for r, (sub, gids) in enumerate(split_scene(ps, part, sc["cell_width"])):
-        lo, hi = part.block_range(r)
-        shards.append(NativeShard(pipe, sc["params"], sub, gids, sc["colliders"], sc["cell_width"], sc["grid_capacity"], lo, hi, r > 0, r < 1,
-                                  particle_capacity=ps.n, model=sc["model"], uniform_material=uniform_material_of(ps),
-                                  halo_capacity_records=256, migrant_capacity=2048))
+    shards, _ = lockstep_slabs(pipe, sc, 2, part=part, halo_capacity_records=256, migrant_capacity=2048)
     assert [s.num_particles() for s in shards] == [ps.n, 0]
     native_lockstep(pipe, shards, 20)
     mid = [s.num_particles() for s in shards]
@@ -323,7 +314,7 @@ def test_slabs_evict_the_blocks_a_body_leaves_behind(hip_libs):
     rebuilt its table every 1 024 substeps and whenever a moving body had used up the ids). A 16^3 cube flies through three slabs at a third of
     a cell per substep, with a block capacity that 150 substeps of its trail would exhaust: every slab builds its table once, ids come back
     on the free lists, nothing overflows, and the particles are those of the single-domain run."""
-    from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, native_lockstep, split_scene, uniform_material_of
+    from wgsparkl_amd.sharded import SlabPartition, associated_block_x, native_lockstep
     sc = scenes.neo_hookean_cube(n_side=16, with_floor=False)
     ps = sc["particles"]
     ps.vel[:, 0] = 400.0
@@ -338,12 +329,7 @@ def test_slabs_evict_the_blocks_a_body_leaves_behind(hip_libs):
     b0 = int(bx.min())
     part = SlabPartition([b0, b0 + 5, b0 + 10, b0 + 18])
     pipe = pipeline(3)
-    shards = []
-    for r, (sub, gids) in enumerate(split_scene(ps, part, sc["cell_width"])):
-        lo, hi = part.block_range(r)
-        shards.append(NativeShard(pipe, sc["params"], sub, gids, sc["colliders"], sc["cell_width"], sc["grid_capacity"], lo, hi, r > 0, r < 2,
-                                  particle_capacity=ps.n, model=sc["model"], uniform_material=uniform_material_of(ps),
-                                  halo_capacity_records=512, migrant_capacity=4096))
+    shards, _ = lockstep_slabs(pipe, sc, 3, part=part, halo_capacity_records=512, migrant_capacity=4096)
     for _ in range(k // 10):
         native_lockstep(pipe, shards, 10)
         for s in shards:
@@ -374,7 +360,7 @@ def test_mesh_colliders_on_sharded_data(hip_libs, name):
     dim = sc["particles"].dim
     ref = run_gpu(sc, k).read_particles()
     pipe = pipeline(dim)
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     assert min(s.num_particles() for s in shards) > 0
     native_lockstep(pipe, shards, k)
     for s in shards:
@@ -479,8 +465,8 @@ def test_a_refused_lockstep_call_leaves_the_slabs_usable(hip_libs):
     heavy = ball.with_density(500.0, 2)
     ps = sc["particles"]
     pipe = pipeline(2)
-    first, _ = _native_slabs({**sc, "colliders": [ball]}, 2, pipe)
-    second, _ = _native_slabs({**sc, "colliders": [heavy]}, 2, pipe)
+    first, _ = lockstep_slabs(pipe, {**sc, "colliders": [ball]}, 2)
+    second, _ = lockstep_slabs(pipe, {**sc, "colliders": [heavy]}, 2)
     assert min(s.num_particles() for s in first) > 0
 
     first[0].set_body_mass_properties([heavy])
@@ -506,3 +492,41 @@ def test_a_refused_lockstep_call_leaves_the_slabs_usable(hip_libs):
         for key in pa[0]:
             assert np.array_equal(pa[0][key], pb[0][key]), (r, key)
     assert first[0].read_body_poses()[0]["linvel"][1] != 0.0, "the ball has a mass now: gravity and the block move it"
+
+
+def test_lockstep_slabs_builds_what_the_spelled_slabs_build(hip_libs):
+    """sharded.lockstep_slabs is split_scene + NativeShard + set_fluid_eos per slab: a Tait fluid block with exponent 5 (with the
+    default 7 a forgotten setter would pass), stirred so that it compresses, as two lockstep slabs built both ways, four substeps
+    each — every field of the two export()s equal bit for bit; slabs built without the exponent (`fluid_gamma=None`) end elsewhere."""
+    from wgsparkl_amd.sharded import NativeShard, SlabPartition, associated_block_x, native_lockstep, split_scene, uniform_material_of
+    sc = scenes.tait_fluid_block(32, 16, 16, with_floor=False, gamma=5.0)
+    ps = sc["particles"]
+    ps.vel[:] = np.random.default_rng(8).normal(0.0, 3.0, ps.vel.shape).astype(np.float32)
+    pipe = pipeline(3)
+    part = SlabPartition.balanced(associated_block_x(ps.pos, sc["cell_width"], 3), 2)
+    spelled = []
+    for r, (sub, gids) in enumerate(split_scene(ps, part, sc["cell_width"])):
+        lo, hi = part.block_range(r)
+        spelled.append(NativeShard(pipe, sc["params"], sub, gids, sc["colliders"], sc["cell_width"], sc["grid_capacity"], lo, hi, r > 0, r < 1,
+                                   particle_capacity=ps.n, model=sc["model"], uniform_material=uniform_material_of(ps)))
+    for s in spelled:
+        s.set_fluid_eos(sc["fluid_gamma"])
+    built, built_part = lockstep_slabs(pipe, sc, 2)
+    assert built_part == part and min(s.num_particles() for s in built) > 0
+    forgotten, _ = lockstep_slabs(pipe, sc, 2, fluid_gamma=None)
+    for shards in (spelled, built, forgotten):
+        native_lockstep(pipe, shards, 4)
+        for s in shards:
+            s.sync()
+
+    def by_id(shard):          # (the slots of a slab are not in a reproducible order: its particles are named by their global ids)
+        e = shard.export()
+        order = np.argsort(e["ids"], kind="stable")
+        return {f: v[order] for f, v in e.items()}
+
+    for r, (a, b) in enumerate(zip(spelled, built)):
+        ea, eb = by_id(a), by_id(b)
+        assert set(ea) == set(eb) and len(ea["ids"]) > 0
+        for f in ea:
+            assert ea[f].tobytes() == eb[f].tobytes(), (r, f)
+    assert any(by_id(a)["vel"].tobytes() != by_id(c)["vel"].tobytes() for a, c in zip(spelled, forgotten)), "the exponent does not matter here"

@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 import transfer_truth as T
-from gpu_common import _native_slabs, check_blocks
+from gpu_common import check_blocks
 from helpers import compare_grids, grid_of, pipeline, report_margin, run_gpu, run_oracle
+from wgsparkl_amd.sharded import lockstep_slabs
 
 pytestmark = pytest.mark.gpu
 
@@ -134,7 +135,7 @@ def test_lockstep_slabs_particle_by_particle(hip_libs, world, d, h):
     sc = _drifting(d, h, world, seed=30 + world + d)
     ps = sc["particles"]
     pipe = pipeline(d)
-    shards, part = _native_slabs(sc, world, pipe)
+    shards, part = lockstep_slabs(pipe, sc, world)
     bw = T.bw_of(d)
     lo_hi = np.array([part.block_range(r) for r in range(world)])
     cuts = lo_hi[1:, 0] * bw

@@ -17,10 +17,10 @@ import pytest
 
 import transfer_truth as T
 import wall_truth as W
-from gpu_common import _native_slabs
 from helpers import debug, new_data, pipeline, report_margin
 from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd.models import WALL_NONE, WALL_SEPARATE, WALL_SLIP, WALL_STICKY, Wall
+from wgsparkl_amd.sharded import lockstep_slabs
 from wgsparkl_amd.solver import Collider
 
 pytestmark = pytest.mark.gpu
@@ -327,7 +327,7 @@ def test_refusals_change_nothing(hip_libs, d):
     assert lib.wgs_set_domain_walls(h, one) == 0
     data.set_domain_walls(good)
     # a lockstep slab: WGS_ERR_UNSUPPORTED, in the words of the other single-domain calls
-    shards, _ = _native_slabs(sc, 2, pipe)
+    shards, _ = lockstep_slabs(pipe, sc, 2)
     for s in shards:
         out = (_ffi.Wall * (2 * d))()
         C.memset(out, 0x5a, C.sizeof(out))
@@ -343,8 +343,6 @@ def test_a_tank_of_domain_walls(hip_libs, d):
     sc = scenes.block_in_fluid(dim=d, walls="grid")
     assert sc["colliders"] == []
     _, data = new_data(sc)
-    data.set_fluid_eos(sc["fluid_gamma"])
-    data.set_particle_models(sc["models"])
     assert [w.type for w in data.domain_walls()] == [WALL_NONE if w is None else w.type for w in sc["walls"]]
     mass0 = data.diagnostics(_ffi.DIAG_PARTICLES).sums["mass"]
     pipeline(d).step(data, 24)

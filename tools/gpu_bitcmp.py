@@ -16,7 +16,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     elif name == "c3s": sc = scenes.config_scene("c3", n_side=64)
     else: sc = scenes.neo_hookean_cube(n_side=48, with_floor=True)
     pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    data = MpmData.from_scene(pipe, sc)
     pipe.step(data, steps); data.sync()
     p = data.read_particles()
     np.savez(out, pos=p.pos, vel=p.vel, F=p.def_grad, C=p.affine, dp=p.dp_state, aff=p.cdf_affinity, nrm=p.cdf_normal, dist=p.cdf_dist)

@@ -18,7 +18,7 @@ for bits in sys.argv[5:]:
         for i in range(nd):
             sc = _random_scene(seed)
             pipe = pipeline(sc["particles"].dim)
-            datas.append(MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"]))
+            datas.append(MpmData.from_scene(pipe, sc))
         bad = None
         for k in range(ksub):
             for dd in datas: pipe.step(dd, 1)

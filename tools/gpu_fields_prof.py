@@ -31,7 +31,7 @@ RENDER_VOLUME = 1   # include/wgsparkl_hip.h WGS_RENDER_VOLUME
 n_side = int(args[0]) if args else 100
 sc = scenes.neo_hookean_cube(n_side=n_side, with_floor=True)
 pipe = MpmPipeline(0, 3)
-data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+data = MpmData.from_scene(pipe, sc)
 pipe.step(data, 50)
 data.sync()
 stream = torch.cuda.ExternalStream(int(data.device_ptrs().hip_stream))

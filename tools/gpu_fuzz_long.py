@@ -14,7 +14,7 @@ for seed in range(lo, hi):
             from helpers import pipeline                     # near-collider list the host last saw get exercised
             from wgsparkl_amd import MpmData
             pipe = pipeline(sc["particles"].dim)
-            data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+            data = MpmData.from_scene(pipe, sc)
             done = 0
             while done < k:
                 pipe.step(data, min(chunk, k - done)); data.sync(); done += chunk

@@ -3,10 +3,9 @@
 import sys, traceback; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import numpy as np
 from helpers import pipeline, rel_rms, run_gpu
-from gpu_common import _native_slabs
 from wgsparkl_amd import scenes
 from wgsparkl_amd.models import ParticlePhase
-from wgsparkl_amd.sharded import native_lockstep
+from wgsparkl_amd.sharded import lockstep_slabs, native_lockstep
 from wgsparkl_amd.solver import Collider, SimulationParams
 lo, hi = int(sys.argv[1]), int(sys.argv[2])
 k = int(sys.argv[3]) if len(sys.argv) > 3 else 30
@@ -33,7 +32,7 @@ for seed in range(lo, hi):
             ref_data = run_gpu(sc, k)
             ref = ref_data.read_particles()
             pipe = pipeline(dim)
-            shards, part = _native_slabs(sc, world, pipe)
+            shards, part = lockstep_slabs(pipe, sc, world)
             if part.min_interior_width() < 3:
                 skipped += 1
                 continue

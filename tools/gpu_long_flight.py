@@ -11,7 +11,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sc["particles"].vel[:, 0] = 48.0 + 1.5 * rel[:, 2]; sc["particles"].vel[:, 1] = 48.0; sc["particles"].vel[:, 2] = 48.0 - 1.5 * rel[:, 0]
     sc["params"].gravity = (0.0, 0.0, 0.0) if hasattr(sc["params"], "gravity") else None
     pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    data = MpmData.from_scene(pipe, sc)
     pipe.step(data, 5); data.sync()
     s0 = data.stats(); t0 = time.perf_counter()
     for _ in range(20):

@@ -25,9 +25,7 @@ elif a.table == "thirds":
     table = np.random.default_rng(6).integers(0, 3, n).astype(np.uint8)
 elif a.table:
     sys.exit(__doc__)
-d = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], model if table is None else (model + 1) % 2)
-if table is not None:
-    d.set_particle_models(table)
+d = MpmData.from_scene(pipe, sc, model=model if table is None else (model + 1) % 2, models=table)
 pipe.step(d, 40); d.sync()
 tag = f"{cfg} model {model}" + (f" table {a.table}" if a.table else "")
 reps = []

@@ -34,7 +34,7 @@ for self_nb in (False, True):
     assert data.num_particles() == ps.n
     data.close(); comm.close()
 sc = slab_scene() if cfg == "c5" else scenes.neo_hookean_cube(n_side=100, with_floor=True)
-d1 = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+d1 = MpmData.from_scene(pipe, sc)
 pipe.step(d1, 30); d1.sync()
 for k in (100, 300):
     t0 = time.perf_counter(); pipe.step(d1, k); t1 = time.perf_counter(); d1.sync(); t2 = time.perf_counter()

@@ -11,7 +11,7 @@ ksub = int(sys.argv[2]) if len(sys.argv) > 2 else 400
 pipe = pipeline(3)
 def make():
     sc = scenes.reference_sand3() if cfg == "sand3" else scenes.neo_hookean_cube(n_side=32, with_floor=True) if cfg == "small" else scenes.config_scene(cfg)
-    return MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    return MpmData.from_scene(pipe, sc)
 datas = [make() for _ in range(int(os.environ.get("NDATA", "2")))]
 for d in datas: pipe.step(d, 60); d.sync()
 def run(ds, chunk=10):

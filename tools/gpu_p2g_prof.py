@@ -16,7 +16,7 @@ else:
     n_side = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     sc = scenes.neo_hookean_cube(n_side=n_side, with_floor=True)
 pipe = pipeline(3)
-data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+data = MpmData.from_scene(pipe, sc)
 ROWS = 8192
 buf = (C.c_ulonglong * (ROWS * 8))()
 pipe.step(data, 200 if len(sys.argv) > 1 and sys.argv[1] == 'landed' else 20); data.sync()

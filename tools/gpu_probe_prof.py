@@ -26,7 +26,7 @@ npts = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
 sc = scenes.neo_hookean_cube(n_side=n_side, with_floor=True)
 h = sc["cell_width"]
 pipe = pipeline(3)
-data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], h, sc["grid_capacity"], sc["model"])
+data = MpmData.from_scene(pipe, sc, cell_width=h)
 pipe.step(data, 50)
 data.sync()
 pos = data.read_positions()

@@ -11,7 +11,7 @@ if name == "stirred":       # bench.py's c2_stirred leg
     sc["particles"].vel[:, 1] = 48.0
     sc["particles"].vel[:, 2] = 48.0 - 1.5 * rel[:, 0]
 pipe = pipeline(sc["particles"].dim)
-data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+data = MpmData.from_scene(pipe, sc)
 pipe.step(data, 100 if name != 'stirred' else 5); data.sync()
 pipe.step(data, 50 if name in ('stirred', 'c4leg') else 200); data.sync()
 print(data.stats())

@@ -9,7 +9,7 @@ from wgsparkl_amd.solver import Collider
 def run(name, sc, warm=60, steps=100):
     dim = sc["particles"].dim
     pipe = pipeline(dim)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    data = MpmData.from_scene(pipe, sc)
     pipe.step(data, warm); data.sync()
     t0 = time.perf_counter(); pipe.step(data, steps); data.sync(); t1 = time.perf_counter()
     pipe.step(data, 32, timestamps=True); data.sync()

@@ -8,7 +8,7 @@ from golden_cases import dynamic_ball3d, mesh_floor3d, polyline2d, dynamic_ball2
 def run(name, sc, steps, chunk=200):
     dim = sc["particles"].dim
     pipe = pipeline(dim)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc.get("model", 0))
+    data = MpmData.from_scene(pipe, sc)
     t0 = time.time()
     done = 0
     while done < steps:

@@ -8,7 +8,7 @@ from wgsparkl_amd import MpmData, scenes
 for cfg, total, per in (("c2", 20000, 500), ("c3", 4000, 250), ("c5", 1500, 250)):
     sc = scenes.config_scene(cfg)
     pipe = pipeline(3)
-    data = MpmData.new(pipe, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+    data = MpmData.from_scene(pipe, sc)
     t0 = time.perf_counter()
     for _ in range(total // per):
         pipe.step(data, per)

@@ -4,9 +4,8 @@ import os, sys, time; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 if os.environ.get("WGS_SOAK_NO_PERIOD") != "1": os.environ.setdefault("WGS_REHASH_PERIOD", "256")   # (WGS_SOAK_NO_PERIOD=1: no periodic rebuild — eviction keeps the slabs' tables instead)
 import numpy as np
 from helpers import pipeline
-from gpu_common import _native_slabs
 from wgsparkl_amd import scenes
-from wgsparkl_amd.sharded import native_lockstep
+from wgsparkl_amd.sharded import lockstep_slabs, native_lockstep
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
 for world, dim, floor in ((4, 3, True), (3, 2, True), (8, 3, False)):
     if dim == 3:
@@ -21,7 +20,7 @@ for world, dim, floor in ((4, 3, True), (3, 2, True), (8, 3, False)):
     ps.vel[:] = rng.normal(0.0, 3.0, ps.vel.shape).astype(np.float32)
     ps.vel[:, 0] += 6.0 + 4.0 * np.sign(np.sin(np.arange(ps.n) * 0.01)).astype(np.float32)      # a drift along x (across the cuts) + bands moving against each other
     pipe = pipeline(dim)
-    shards, part = _native_slabs(sc, world, pipe)
+    shards, part = lockstep_slabs(pipe, sc, world)
     t0 = time.time(); done = 0; crossed = 0
     n_prev = [s.num_particles() for s in shards]
     while done < steps:

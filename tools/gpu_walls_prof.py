@@ -28,15 +28,6 @@ from wgsparkl_amd.solver import ParticleSet, SimulationParams  # noqa: E402
 OUT = {}
 
 
-def make(pipe, sc, walls):
-    data = MpmData.from_scene(pipe, sc, walls=walls)
-    if sc.get("model") == MODEL_FLUID or "models" in sc:
-        data.set_fluid_eos(sc.get("fluid_gamma", 7.0))
-    if "models" in sc:
-        data.set_particle_models(sc["models"])
-    return data
-
-
 def us_per_substep(pipe, data, k):
     data.sync()
     t0 = time.perf_counter()
@@ -47,7 +38,7 @@ def us_per_substep(pipe, data, k):
 
 def ab(pipe, tag, variants, warm=100, k=300, reps=7, passes=False):
     """`variants`: name -> (scene, walls); every variant is created once, then timed `reps` times in turn"""
-    datas = {name: make(pipe, s, w) for name, (s, w) in variants.items()}
+    datas = {name: MpmData.from_scene(pipe, s, walls=w) for name, (s, w) in variants.items()}
     for d in datas.values():
         pipe.step(d, warm)
         d.sync()
@@ -109,7 +100,7 @@ def part_rest(pipe, substeps=6000):
             s = dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0), dt=1.0 / 1200.0), colliders=[], cell_width=h, grid_capacity=4096,
                      model=MODEL_FLUID if mat == "tait_fluid" else MODEL_NEO_HOOKEAN, fluid_gamma=7.0)
             walls = [Wall(typ, 0.0, 7), Wall(typ, 0.0, 18), Wall(typ, 0.0, plane), None, Wall(typ, 0.0, 7), Wall(typ, 0.0, 18)]
-            d = make(pipe, s, walls)
+            d = MpmData.from_scene(pipe, s, walls=walls)
             lows = []
             for i in range(substeps // 100):
                 pipe.step(d, 100)

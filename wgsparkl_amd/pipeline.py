@@ -427,12 +427,15 @@ class MpmData(DataHandle):
 
     @classmethod
     def from_scene(cls, pipeline, scene, **overrides):
-        """`new` from one of the dicts `wgsparkl_amd.scenes` returns (a missing "model" is MODEL_COROTATED); a keyword replaces the
-        scene's entry of that name for this call: `colliders=[]`, `grid_capacity=128`, `particles=snap`."""
+        """The data one of the dicts `wgsparkl_amd.scenes` returns describes (the key table in that module's docstring): `new` with
+        its "model", then its "fluid_gamma", "models" and "walls" through their setters, in that order, each only where the scene
+        has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
+        `particles=snap`); `None` for one of the three optional keys builds the scene without it (`models=None`: no table)."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
         data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        if sc.get("walls") is not None:
-            data.set_domain_walls(sc["walls"])
+        for key, apply in (("fluid_gamma", data.set_fluid_eos), ("models", data.set_particle_models), ("walls", data.set_domain_walls)):
+            if sc.get(key) is not None:
+                apply(sc[key])
         return data
 
     def set_domain_walls(self, walls):

@@ -4,6 +4,23 @@ Conventions follow the reference's example scenes: lattice spacing h/2
 (8 particles per cell in 3D, 4 in 2D), radius h/4, `with_density`
 (crates/wgsparkl3d/examples/sand3.rs:28-49, crates/wgsparkl2d/examples/elasticity2.rs:33-55),
 plus a reproducible jitter so cells are not degenerate.
+
+The scene contract. Every builder returns a dict, and `MpmData.from_scene` (a whole scene) and `NativeShard.from_scene` /
+`sharded.lockstep_slabs` (slabs) are the ones that read it:
+
+| key | | what the constructors do with it |
+|---|---|---|
+| `particles`, `params`, `colliders`, `cell_width`, `grid_capacity` | required | the arguments of `MpmData.new` / `NativeShard` |
+| `model` | optional | the data's single constitutive model; default `MODEL_COROTATED` |
+| `fluid_gamma` | optional | the Tait exponent of `MODEL_FLUID`: `set_fluid_eos` |
+| `models` | optional | the per-particle table (np.uint8): `MpmData.set_particle_models`; an error on a slab |
+| `walls` | optional | the 2 * dim domain walls: `MpmData.set_domain_walls`; an error on a slab |
+| `global_ids`, `partition` | slab scenes | the particles' names in the whole scene; the `SlabPartition` the slab's block range and neighbours come from |
+| `uniform_material` | slab scenes, optional | (mass, init_volume, lambda, mu) shared by every particle of every rank |
+
+The optional keys are applied at creation in the order of the table, each only where the scene has the key and its value is not
+None. Any other key (`fluid`, `solid_model`, `global_particles`, `name`, `bytes_per_particle`, ...) is information for the
+caller; the constructors ignore it.
 """
 from __future__ import annotations
 
@@ -296,7 +313,7 @@ def fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, cell_wi
 def tait_fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, cell_width=1.0, with_floor=True,
                      density=1000.0, bulk_modulus=1.0e7, viscosity=0.0, gamma=7.0, grid_capacity=None):
     """The lattice of `fluid_block` under MODEL_FLUID: Tait pressure with bulk modulus `bulk_modulus` and exponent `gamma`
-    (scene key "fluid_gamma": MpmData.set_fluid_eos), dynamic viscosity `viscosity`. Same particles, ids and slabs as
+    (scene key "fluid_gamma", see the key table of this module), dynamic viscosity `viscosity`. Same particles, ids and slabs as
     `fluid_block` for the same arguments; to first order in J - 1 the same pressure."""
     sc = fluid_block(nx, ny, nz, world=world, rank=rank, jitter=jitter, cell_width=cell_width, with_floor=with_floor,
                      density=density, bulk_modulus=bulk_modulus, grid_capacity=grid_capacity)
@@ -309,7 +326,7 @@ def tait_fluid_block(nx=256, ny=250, nz=250, world=1, rank=None, jitter=0.05, ce
 
 def _container(walls):
     if walls not in ("colliders", "grid"):
-        raise ValueError(f"walls={walls!r}: 'colliders' (CPIC cuboids) or 'grid' (domain walls, MpmData.set_domain_walls)")
+        raise ValueError(f"walls={walls!r}: 'colliders' (CPIC cuboids) or 'grid' (domain walls, scene key \"walls\")")
     return walls == "grid"
 
 
@@ -336,7 +353,7 @@ def dam_break(nx=24, ny=40, nz=16, jitter=0.05, cell_width=1.0, density=1000.0, 
 def block_in_fluid(dim=3, tank=(24, 16, 16), block=8, gap=0.5, drop_speed=0.0, solid_model=MODEL_NEO_HOOKEAN, jitter=0.05, cell_width=1.0,
                    density=1000.0, bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, solid_density=2000.0, young_modulus=2.0e5, poisson=0.3,
                    walls="colliders", wall_type=WALL_SLIP, wall_friction=0.0):
-    """Fluid and solid in one simulation (MpmData.set_particle_models): a tank of Tait fluid — `tank` particles at spacing h/2 standing on
+    """Fluid and solid in one simulation (scene key "models", see the key table of this module): a tank of Tait fluid — `tank` particles at spacing h/2 standing on
     the floor cuboid between four wall cuboids (two in 2D), like `dam_break` but closed — and an elastic block of `block`^dim particles
     hanging `gap` cells above the middle of its surface, falling at `drop_speed`. The two interact through the grid alone. Returns the
     scene dict with "models" (np.uint8 per particle: MODEL_FLUID for the tank, `solid_model` for the block) and "solid_model";

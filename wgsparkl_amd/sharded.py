@@ -147,6 +147,28 @@ class NativeShard(DataHandle):
         self.part_rec = self.lib.wgs_shard_particle_record_bytes() // 4
         self.hdr = self.lib.wgs_shard_buffer_header_bytes() // 4
 
+    @classmethod
+    def from_scene(cls, pipeline: MpmPipeline, slab_scene, rank: int, comm: Optional[NativeComm] = None, particle_capacity: int = 0,
+                   force_plastic: bool = False, halo_capacity_records: int = 4096, migrant_capacity: int = 4096, **overrides):
+        """The slab of `rank` from a slab scene (the key table in the docstring of `wgsparkl_amd.scenes`): its block range and
+        its neighbours from the scene's "partition", its "global_ids", "model" and "uniform_material", then its "fluid_gamma".
+        A keyword replaces the scene's entry of that name, as in `MpmData.from_scene`. "models" and "walls" are single-domain
+        features the library refuses on a slab: a scene that holds one is an error unless the caller passes `models=None` /
+        `walls=None`. `particle_capacity` = 0: room for the slab's own particles only."""
+        sc = {"model": MODEL_COROTATED, **slab_scene, **overrides}
+        for key in ("models", "walls"):
+            if sc.get(key) is not None:
+                raise ValueError(f"NativeShard.from_scene: the scene's {key!r} cannot be applied to a slab; pass {key}=None to build it without")
+        part = sc["partition"]
+        lo, hi = part.block_range(rank)
+        shard = cls(pipeline, sc["params"], sc["particles"], sc["global_ids"], sc["colliders"], sc["cell_width"], sc["grid_capacity"],
+                    lo, hi, rank > 0, rank < part.world - 1, particle_capacity, model=sc["model"], force_plastic=force_plastic,
+                    halo_capacity_records=halo_capacity_records, migrant_capacity=migrant_capacity, comm=comm,
+                    uniform_material=sc.get("uniform_material"))
+        if sc.get("fluid_gamma") is not None:
+            shard.set_fluid_eos(sc["fluid_gamma"])
+        return shard
+
     def step(self, num_substeps: int):
         """`wgs_sharded_step`: whole substeps incl. the neighbour exchange, asynchronous."""
         _ffi.check(self.lib, self.lib.wgs_sharded_step(self.pipeline._h, self._h, int(num_substeps)))
@@ -230,3 +252,15 @@ def split_scene(particles: ParticleSet, partition: SlabPartition, cell_width: fl
         sub = ParticleSet(**{k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in particles.__dict__.items()})
         out.append((sub, idx.astype(np.uint32)))
     return out
+
+
+def lockstep_slabs(pipeline: MpmPipeline, scene, world: int, part: Optional[SlabPartition] = None, **kw):
+    """A whole scene cut into `world` x-slabs balanced by particle count (or by the given SlabPartition), each a NativeShard of a
+    lockstep group (`native_lockstep`) with room for every particle of the scene; `kw` as in `NativeShard.from_scene`.
+    Returns (shards, partition)."""
+    ps = scene["particles"]
+    part = part or SlabPartition.balanced(associated_block_x(ps.pos, scene["cell_width"], ps.dim), world)
+    kw.setdefault("particle_capacity", ps.n)
+    slab = {**scene, "partition": part, "uniform_material": uniform_material_of(ps)}
+    return [NativeShard.from_scene(pipeline, {**slab, "particles": sub, "global_ids": gids}, r, **kw)
+            for r, (sub, gids) in enumerate(split_scene(ps, part, scene["cell_width"]))], part
