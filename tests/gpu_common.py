@@ -6,6 +6,7 @@ import pytest
 
 from wgsparkl_amd import MpmData, scenes
 from wgsparkl_amd.models import (MODEL_COROTATED, MODEL_NEO_HOOKEAN, DruckerPrager, ElasticCoefficients, ParticlePhase)
+from wgsparkl_amd.sharded import join_slabs, native_lockstep
 from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
 
 import body_truth as BT
@@ -283,54 +284,28 @@ def _bed_scene(d, h, n=None, drift=0.0):
     return sc
 
 
-def _export_records(shard):
-    """the exchange records of the particles a slab holds [count, floats per record]: every quad of the particle, its global id
-    and the substep its cdf was computed in"""
-    import ctypes as C
-    import torch
-    from wgsparkl_amd import _ffi
-    D = shard.dim
-    buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
-    torch.cuda.current_stream(buf.device).synchronize()
-    cnt = C.c_uint32(0)
-    _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
-    return buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
+def _joined_with_cdf(shards, n):
+    """sharded.join_slabs of every slab's state and cdf, every particle exactly once; and (cdf_affinity, cdf_dist, cdf_normal) in the
+    same order under the one rule that is not the record's: a cdf whose stamp is not the newest stamp is the default cdf"""
+    joined = join_slabs([s.export(cdf=True) for s in shards], np.arange(n))
+    assert joined.exact, joined.problem
+    f = joined.fields
+    live = f["cdf_stamp"] == f["cdf_stamp"].max()
+    return joined, (np.where(live, f["cdf_affinity"], 0).astype(np.uint32), np.where(live, f["cdf_dist"], 0.0),
+                    np.where(live[:, None], f["cdf_normal"], 0.0))
 
 
-def _export_cdf(shard, rec=None):
-    """(global ids, positions, cdf_affinity, cdf_dist, cdf_normal, cdf stamp) of the particles a slab holds"""
-    from wgsparkl_amd.sharded import record_quad
-    D = shard.dim
-    rec = _export_records(shard) if rec is None else rec
-    ids, stamp = rec[:, -2].copy().view(np.uint32), rec[:, -1].copy().view(np.uint32)
-    q = lambda name: record_quad(rec, D, name)
-    if D == 3:
-        return ids, q("XM")[:, :3].copy(), q("CDF1")[:, 3].copy().view(np.uint32), q("CDF0")[:, 3].copy(), q("CDF0")[:, :3].copy(), stamp
-    return ids, q("XM")[:, :2].copy(), q("CDF0")[:, 3].copy().view(np.uint32), q("CDF0")[:, 2].copy(), q("CDF0")[:, :2].copy(), stamp
-
-
-def _export_all(shards, n, d, recs=None):
-    """the particles of all slabs in the order of their global ids; a cdf whose stamp is not the newest is the default one"""
-    parts = [_export_cdf(s, None if recs is None else recs[r]) for r, s in enumerate(shards)]
-    ids = np.concatenate([p[0] for p in parts]).astype(np.int64)
-    assert np.array_equal(np.sort(ids), np.arange(n)), "every particle exactly once"
-    order = np.argsort(ids)
-    pos, aff, dist, normal, stamp = (np.concatenate([p[k] for p in parts])[order] for k in range(1, 6))
-    live = stamp == stamp.max()
-    return pos, np.where(live, aff, 0).astype(np.uint32), np.where(live, dist, 0.0), np.where(live[:, None], normal, 0.0)
+def _export_all(shards, n, d):
+    """(pos, cdf_affinity, cdf_dist, cdf_normal) of the particles of all slabs in the order of their global ids"""
+    joined, cdf = _joined_with_cdf(shards, n)
+    return (joined.fields["pos"],) + cdf
 
 
 def export_state_and_cdf(shards, n, d):
-    """one export per slab, read twice: ({pos, vel, def_grad, affine, mass} in the order of the global ids, the rank that holds
-    each particle, cdf_affinity, cdf_dist, cdf_normal)"""
-    from wgsparkl_amd.sharded import unpack_records
-    recs = [_export_records(s) for s in shards]
-    outs = [unpack_records(rec, d, s.uniform_material if d == 3 else None) for rec, s in zip(recs, shards)]
-    ids = np.concatenate([o["ids"] for o in outs]).astype(np.int64)
-    order = np.argsort(ids)
-    held = np.concatenate([np.full(len(o["ids"]), r) for r, o in enumerate(outs)])[order]
-    _, aff, dist, normal = _export_all(shards, n, d, recs)          # (asserts that every particle is there exactly once)
-    return {f: np.concatenate([o[f] for o in outs])[order] for f in ("pos", "vel", "def_grad", "affine", "mass")}, held, aff, dist, normal
+    """({pos, vel, def_grad, affine, mass} in the order of the global ids, the rank that holds each particle, cdf_affinity, cdf_dist,
+    cdf_normal), from one export per slab"""
+    joined, cdf = _joined_with_cdf(shards, n)
+    return ({f: joined.fields[f] for f in ("pos", "vel", "def_grad", "affine", "mass")}, joined.holder) + cdf
 
 
 def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):
@@ -338,7 +313,6 @@ def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):
     against the truth of the whole domain (the samples of a mesh collider included; without one mesh_truth.rigid_of gives
     None), the nodes of each slab's own blocks against the truth restricted to them, and no collider-affine node of a
     slab's range missing from its grid. Returns, per substep, whether collider 1 votes at a node past the cut."""
-    from wgsparkl_amd.sharded import native_lockstep
     ps = sc["particles"]
     d, h = ps.dim, sc["cell_width"]
     bw = T.bw_of(d)
@@ -362,7 +336,7 @@ def check_lockstep_slabs(tag, sc, shards, part, nsteps, fails):
         CT.check_particle_cdf(f"{tag_k} end to end", e2e, aff, dist, normal, fails)
         CT.assert_caps(tag_k, whole, e2e)
         for r, s in enumerate(shards):
-            cells, _, ndist, naff, nclosest = MpmData.read_grid(s)
+            cells, _, ndist, naff, nclosest = s.read_grid()
             blk = cells[:, 0] // bw
             own = (blk >= ranges[r][0]) & (blk < ranges[r][1])
             assert own.any()

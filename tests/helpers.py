@@ -11,6 +11,7 @@ import numpy as np
 
 from oracle.orc import Oracle
 from wgsparkl_amd import MpmData, MpmPipeline
+from wgsparkl_amd.selfcheck import rel_rms
 
 _ORACLES = {}
 _LAYOUT_H = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wgsparkl_amd", "csrc", "layout.h")
@@ -122,15 +123,6 @@ def restored_colliders(colliders, bodies, dim):
     return [restored(c, b) for c, b in zip(colliders, bodies)]
 
 
-def rel_rms(a, b):
-    """RMS of (a - b) relative to RMS of b (b = truth)."""
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    den = np.sqrt(np.mean(b * b))
-    num = np.sqrt(np.mean((a - b) ** 2))
-    return num / den if den > 0 else num
-
-
 def max_abs(a, b):
     return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)))) if len(a) else 0.0
 
@@ -170,6 +162,18 @@ def report_margin(name, value, bound, **extra):
     if path:
         with open(path, "a") as f:
             f.write(json.dumps(rec) + "\n")
+
+
+def assert_joined_close(joined, ref, checks, name, ref_order=None, **extra):
+    """The joined slabs of a decomposition (sharded.join_slabs) against the single-domain run `ref`, whose particles are in the order
+    of the ids (or brought into it by `ref_order`): every id exactly once, then for each (field, tolerance) of `checks` the rel_rms,
+    reported under name.format(f=field) with `extra`, below the tolerance."""
+    assert joined.exact, joined.problem
+    for f, tol in checks:
+        want = getattr(ref, f)
+        err = rel_rms(joined.fields[f], want if ref_order is None else want[ref_order])
+        report_margin(name.format(f=f), err, tol, **extra)
+        assert err < tol, (f, err)
 
 
 def assert_close_to_truth(name, got, ref32, truth, rel_tol, k32=None):

@@ -286,20 +286,11 @@ def test_non_finite_particles_are_counted_and_left_out():
     assert np.array_equal(d.aabb_min, ref.aabb_min) and np.array_equal(d.aabb_max, ref.aabb_max)
 
 
-def _raw_records(shard):
-    import torch
-    buf = torch.zeros(shard.hdr + shard.capacity * shard.part_rec, dtype=torch.float32, device=torch.device("cuda", shard.pipeline.device))
-    torch.cuda.current_stream(buf.device).synchronize()
-    cnt = C.c_uint32(0)
-    _ffi.check(shard.lib, shard.lib.wgs_shard_export(shard._h, C.c_void_p(buf.data_ptr()), shard.capacity, C.byref(cnt)))
-    return buf[shard.hdr: shard.hdr + cnt.value * shard.part_rec].cpu().numpy().reshape(cnt.value, shard.part_rec)
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_slabs_add_up_to_the_single_domain(world):
     """G7: 2 and 3 lockstep slabs after a few substeps: the counts add up to N, the digests add up (mod 2^64) to the numpy digest of
-    the concatenated wgs_shard_export records, mass and momentum add up to the single-domain run's within the sums' bounds + 1e-5."""
-    from wgsparkl_amd.sharded import native_lockstep, unpack_records
+    the concatenated export_records() of the slabs, mass and momentum add up to the single-domain run's within the sums' bounds + 1e-5."""
+    from wgsparkl_amd.sharded import native_lockstep, record_quad, unpack_records
     sc = cloud_scene(n=12000, dim=3, extent=30.0)
     pipe = pipeline(3)
     shards, _ = lockstep_slabs(pipe, sc, world, force_plastic=True)
@@ -308,13 +299,13 @@ def test_slabs_add_up_to_the_single_domain(world):
         s.sync()
     ds = [s.diagnostics(ALL) for s in shards]
     assert sum(d.num_particles for d in ds) == sc["particles"].n
-    recs = [_raw_records(s) for s in shards]
     hashes = []
-    for s, rec in zip(shards, recs):
+    for s in shards:
+        rec = s.export_records()
         r = unpack_records(rec, 3, s.uniform_material)
-        q = lambda k: rec[:, 4 * k:4 * k + 4]
-        state = np.concatenate([q(8)[:, 2:4], q(9)[:, 0:1]], 1)          # layout.h: DP1 = (.., .., st0, st1), DP2 = (st2, phase, max_stretch, -)
-        phase = q(9)[:, 1:3]
+        dp1, dp2 = record_quad(rec, 3, "DP1"), record_quad(rec, 3, "DP2")
+        state = np.concatenate([dp1[:, 2:4], dp2[:, 0:1]], 1)            # layout.h: DP1 = (.., .., st0, st1), DP2 = (st2, phase, max_stretch, -)
+        phase = dp2[:, 1:3]
         words = np.concatenate([np.ascontiguousarray(a, np.float32).view(np.uint32) for a in
                                 (r["pos"], r["vel"], r["def_grad"], r["affine"], state, phase)], 1)
         hashes.append(dt.particle_hashes(r["ids"], words))

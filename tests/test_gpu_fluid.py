@@ -10,11 +10,11 @@ import pytest
 
 import fluid_truth as ft
 from gpu_common import GRID_V_TOL, PART_TOL
-from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, rel_rms, report_margin
+from helpers import BASE_FIELDS, assert_close_to_truth, assert_joined_close, assert_same_bits, debug, new_data, pipeline, report_margin
 from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd._ffi import WgsError
 from wgsparkl_amd.models import MODEL_FLUID, MODEL_NEO_HOOKEAN, DruckerPrager, FluidCoefficients, ParticlePhase
-from wgsparkl_amd.sharded import lockstep_slabs
+from wgsparkl_amd.sharded import join_slabs, lockstep_slabs
 from wgsparkl_amd.solver import ParticleSet, SimulationParams
 
 pytestmark = pytest.mark.gpu
@@ -262,13 +262,8 @@ def test_fluid_block_as_lockstep_slabs_matches_the_single_domain(hip_libs, world
     native_lockstep(pipe, shards, k - 30)
     for s in shards:
         s.sync()
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32))
-    assert [len(o["ids"]) for o in outs] != n0, "the test scene must make particles migrate"
-    order = np.argsort(ids)
+    joined = join_slabs([s.export() for s in shards], np.arange(ps.n))
+    assert joined.exact, joined.problem
+    assert joined.counts != n0, "the test scene must make particles migrate"
     assert np.abs(ref.def_grad[:, 0] - 1.0).max() > 1e-3
-    for f, tol in (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5), ("affine", 2e-4)):
-        err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
-        report_margin(f"fluid, {world} lockstep slabs, {f}", err, tol)
-        assert err < tol, (f, err)
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5), ("affine", 2e-4)), f"fluid, {world} lockstep slabs, {{f}}")

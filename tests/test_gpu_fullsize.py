@@ -152,7 +152,7 @@ def test_c5_strong_scaling_slabs_on_one_gpu(hip_libs):
     """The decomposition bench.py --config c5 --scaling strong uses, 8 x-slabs of the fluid block advanced in
     lockstep on one GPU (wgs_sharded_step_lockstep: the per-phase code of wgs_sharded_step, device-to-device copies as the
     transport) at a reduced y/z extent: nobody is lost, the slabs reproduce the single-domain run."""
-    from wgsparkl_amd.sharded import native_lockstep
+    from wgsparkl_amd.sharded import join_slabs, native_lockstep
     world, dims, k = 8, (256, 24, 24), 12
     pipe = pipeline(3)
     full = scenes.fluid_block(*dims)
@@ -166,14 +166,11 @@ def test_c5_strong_scaling_slabs_on_one_gpu(hip_libs):
                                  halo_capacity_records=512, migrant_capacity=2048)
     assert total == full["particles"].n
     native_lockstep(pipe, shards, k)
-    ids, pos, velo = [], [], []
     for s in shards:
         s.sync()
-        e = s.export()
-        ids.append(e["ids"]); pos.append(e["pos"]); velo.append(e["vel"])
-    ids = np.concatenate(ids); pos = np.concatenate(pos); velo = np.concatenate(velo)
-    assert len(ids) == full["particles"].n and len(np.unique(ids)) == len(ids)
-    assert np.abs(pos - ref.pos[ids]).max() < 1e-5 and np.abs(velo - ref.vel[ids]).max() < 2e-4
+    joined = join_slabs([s.export() for s in shards], np.arange(full["particles"].n), fields=("pos", "vel"))
+    assert joined.exact, joined.problem
+    assert np.abs(joined.fields["pos"] - ref.pos).max() < 1e-5 and np.abs(joined.fields["vel"] - ref.vel).max() < 2e-4
 
 
 def test_bench_slabs_at_full_size_fit_their_exchange_buffers(hip_libs):

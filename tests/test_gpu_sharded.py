@@ -5,10 +5,10 @@ import pytest
 
 from wgsparkl_amd import scenes
 from wgsparkl_amd.models import ParticlePhase
-from wgsparkl_amd.sharded import lockstep_slabs
+from wgsparkl_amd.sharded import by_id, join_slabs, lockstep_slabs
 from wgsparkl_amd.solver import Collider, SimulationParams
 
-from helpers import debug, max_abs, new_data, pipeline, rel_rms, report_margin, run_gpu
+from helpers import assert_joined_close, debug, max_abs, new_data, pipeline, rel_rms, report_margin, run_gpu
 from gpu_common import FUZZ_BODY_ATOL
 
 from golden_cases import CASES as _CASES
@@ -42,17 +42,9 @@ def test_bench_decomposition_eight_ranks_on_one_gpu(hip_libs):
     native_lockstep(pipe, shards, k)
     for s in shards:
         s.sync()                                             # would report a message / capacity overflow
-    outs = [s.export() for s in shards]
-    assert [len(o["ids"]) for o in outs] != n0, "particles must have crossed the faces"
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.sort(full["global_ids"]))
-    order = np.argsort(ids)
-    ref_order = np.argsort(full["global_ids"])
-    for f in ("pos", "vel"):
-        got = np.concatenate([o[f] for o in outs])[order]
-        err = rel_rms(got, getattr(ref, f)[ref_order])
-        report_margin(f"bench decomposition, 8 slabs, {f}", err, 1e-5)
-        assert err < 1e-5, f
+    joined = join_slabs([s.export() for s in shards], full["global_ids"])
+    assert joined.counts != n0, "particles must have crossed the faces"
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5)), "bench decomposition, 8 slabs, {f}", ref_order=np.argsort(full["global_ids"]))
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -89,16 +81,8 @@ def test_random_scenes_sharded_match_single_domain(hip_libs, seed):
     native_lockstep(pipe, shards, k)
     for s in shards:
         s.sync()
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32))
-    order = np.argsort(ids)
-    for f in ("pos", "vel"):
-        got = np.concatenate([o[f] for o in outs])[order]
-        tol = 1e-5 if f == "pos" else 2e-4
-        err = rel_rms(got, getattr(ref, f))
-        report_margin(f"sharded fuzz {f}", err, tol, migrated=bool([len(o["ids"]) for o in outs] != n0))
-        assert err < tol, f
+    joined = join_slabs([s.export() for s in shards], np.arange(ps.n))
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 2e-4)), "sharded fuzz {f}", migrated=bool(joined.counts != n0))
 
 
 def test_sharded_run_with_kinematic_collider(hip_libs):
@@ -126,16 +110,9 @@ def test_sharded_run_with_kinematic_collider(hip_libs):
     native_lockstep(pipe, shards, k)
     for s in shards:
         s.sync()
-    outs = [s.export() for s in shards]
-    assert [len(o["ids"]) for o in outs] != n0
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.sort(full["global_ids"]))
-    order, ref_order = np.argsort(ids), np.argsort(full["global_ids"])
-    for f in ("pos", "vel"):
-        got = np.concatenate([o[f] for o in outs])[order]
-        err = rel_rms(got, getattr(ref, f)[ref_order])
-        report_margin(f"sharded c4 {f}", err, 1e-5)
-        assert err < 1e-5, f
+    joined = join_slabs([s.export() for s in shards], full["global_ids"])
+    assert joined.counts != n0
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5)), "sharded c4 {f}", ref_order=np.argsort(full["global_ids"]))
     for s in shards:                                        # every rank holds the same body state
         b = s.read_body_poses()
         assert np.allclose(b[1]["rotation"], ref_body[1]["rotation"], atol=1e-6)
@@ -170,15 +147,8 @@ def test_dynamic_bodies_on_sharded_data(hip_libs, name):
         assert err < 3e-4, (key, a, want)
     assert np.abs(np.stack([b["linvel"] for b in bodies[0]])[0] - np.asarray(sc["colliders"][0].linvel)[:dim]).max() > 1e-3, \
         "the dynamic body must have been pushed"
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(sc["particles"].n, dtype=np.uint32))
-    order = np.argsort(ids)
-    for f, tol in (("pos", 1e-5), ("vel", 5e-5)):
-        got = np.concatenate([o[f] for o in outs])[order]
-        err = rel_rms(got, getattr(ref_p, f))
-        report_margin(f"sharded two-way {f}", err, tol)
-        assert err < tol, (f, err)
+    joined = join_slabs([s.export() for s in shards], np.arange(sc["particles"].n))
+    assert_joined_close(joined, ref_p, (("pos", 1e-5), ("vel", 5e-5)), "sharded two-way {f}")
 
 
 @pytest.mark.parametrize("dim", [3, 2])
@@ -226,10 +196,9 @@ def test_sharded_substep_with_pack_and_interior_grid_update_inside_the_p2g_launc
         e = run()
     for other in (b, c, e):
         for x, y in zip(a, other):
-            ox, oy = np.argsort(x["ids"]), np.argsort(y["ids"])    # (the storage order of a slab follows the arrival order of its guests)
-            assert np.array_equal(x["ids"][ox], y["ids"][oy])
-            for f in ("pos", "vel", "def_grad", "affine"):
-                assert np.array_equal(x[f][ox], y[f][oy]), f
+            x, y = by_id(x), by_id(y)                              # (the storage order of a slab follows the arrival order of its guests)
+            for f in ("ids", "pos", "vel", "def_grad", "affine"):
+                assert np.array_equal(x[f], y[f]), f
 
 
 @pytest.mark.parametrize("world,dim", [(2, 3), (3, 3), (4, 3), (2, 2)])
@@ -259,14 +228,10 @@ def test_native_lockstep_matches_single_domain(hip_libs, world, dim, monkeypatch
     for s in shards:
         s.sync()
     outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32))
-    assert [len(o["ids"]) for o in outs] != n0, "the test scene must make particles migrate"
-    order = np.argsort(ids)
-    for f, tol in (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5), ("affine", 2e-4)):
-        err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
-        report_margin(f"native lockstep {f}", err, tol)
-        assert err < tol, (f, err)
+    joined = join_slabs(outs, np.arange(ps.n))
+    assert joined.exact, joined.problem
+    assert joined.counts != n0, "the test scene must make particles migrate"
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5), ("affine", 2e-4)), "native lockstep {f}")
     for r, o in enumerate(outs):                               # a rank holds its core range + the particles that left it in
         lo, hi = part.block_range(r)                           # the last substep (handed over with the next message)
         bx = associated_block_x(o["pos"], sc["cell_width"], dim)
@@ -299,14 +264,9 @@ def test_particles_enter_an_empty_slab_and_leave_theirs_empty(hip_libs, with_flo
     for s in shards:
         s.sync()
     assert [s.num_particles() for s in shards] == [0, ps.n]
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32))
-    order = np.argsort(ids)
-    for f, tol in (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5)):
-        err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
-        report_margin(f"cube into an empty slab ({'floor' if with_floor else 'free'}) {f}", err, tol)
-        assert err < tol, (f, err)
+    joined = join_slabs([s.export() for s in shards], np.arange(ps.n))
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5)),
+                        f"cube into an empty slab ({'floor' if with_floor else 'free'}) {{f}}")
 
 
 def test_slabs_evict_the_blocks_a_body_leaves_behind(hip_libs):
@@ -339,14 +299,8 @@ def test_slabs_evict_the_blocks_a_body_leaves_behind(hip_libs):
     assert all(x["table_rebuilds"] <= 1 for x in st), [x["table_rebuilds"] for x in st]
     assert sum(x["block_ids_free"] + x["table_marks"] for x in st) > 0, "no slab evicted a block"
     assert [s.num_particles() for s in shards][0] == 0
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32))
-    order = np.argsort(ids)
-    for f, tol in (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5)):
-        err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
-        report_margin(f"slabs evicting a body's trail {f}", err, tol)
-        assert err < tol, (f, err)
+    joined = join_slabs([s.export() for s in shards], np.arange(ps.n))
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 1e-5), ("def_grad", 1e-5)), "slabs evicting a body's trail {f}")
 
 
 @pytest.mark.parametrize("name", ["mesh_floor3d", "polyline2d"])
@@ -365,15 +319,10 @@ def test_mesh_colliders_on_sharded_data(hip_libs, name):
     native_lockstep(pipe, shards, k)
     for s in shards:
         s.sync()
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs])
-    assert np.array_equal(np.sort(ids), np.arange(sc["particles"].n, dtype=np.uint32))
-    order = np.argsort(ids)
+    joined = join_slabs([s.export() for s in shards], np.arange(sc["particles"].n))
+    assert joined.exact, joined.problem
     assert (ref.cdf_affinity != 0).sum() > 10, "the scene must feel its mesh"
-    for f, tol in (("pos", 1e-5), ("vel", 5e-5), ("def_grad", 1e-5)):
-        err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
-        report_margin(f"sharded mesh {f}", err, tol)
-        assert err < tol, (f, err)
+    assert_joined_close(joined, ref, (("pos", 1e-5), ("vel", 5e-5), ("def_grad", 1e-5)), "sharded mesh {f}")
 
 
 def test_native_sharded_step_over_rccl_one_rank(hip_libs):
@@ -395,9 +344,8 @@ def test_native_sharded_step_over_rccl_one_rank(hip_libs):
                      False, False, ps.n, sc["model"], comm=comm, halo_capacity_records=64, migrant_capacity=64)
     sh.step(k)
     sh.sync()
-    out = sh.export()
-    order = np.argsort(out["ids"])
-    assert rel_rms(out["pos"][order], ref.pos) < 1e-6 and rel_rms(out["vel"][order], ref.vel) < 1e-5
+    out = by_id(sh.export())
+    assert rel_rms(out["pos"], ref.pos) < 1e-6 and rel_rms(out["vel"], ref.vel) < 1e-5
     sh.close(); comm.close()
     # (b) self-neighbour proxy
     comm = NativeComm(pipe, None, 0, 1, flags=1)
@@ -519,14 +467,9 @@ def test_lockstep_slabs_builds_what_the_spelled_slabs_build(hip_libs):
         for s in shards:
             s.sync()
 
-    def by_id(shard):          # (the slots of a slab are not in a reproducible order: its particles are named by their global ids)
-        e = shard.export()
-        order = np.argsort(e["ids"], kind="stable")
-        return {f: v[order] for f, v in e.items()}
-
-    for r, (a, b) in enumerate(zip(spelled, built)):
-        ea, eb = by_id(a), by_id(b)
+    for r, (a, b) in enumerate(zip(spelled, built)):     # (the slots of a slab are not in a reproducible order: its particles are named by their global ids)
+        ea, eb = by_id(a.export()), by_id(b.export())
         assert set(ea) == set(eb) and len(ea["ids"]) > 0
         for f in ea:
             assert ea[f].tobytes() == eb[f].tobytes(), (r, f)
-    assert any(by_id(a)["vel"].tobytes() != by_id(c)["vel"].tobytes() for a, c in zip(spelled, forgotten)), "the exponent does not matter here"
+    assert any(by_id(a.export())["vel"].tobytes() != by_id(c.export())["vel"].tobytes() for a, c in zip(spelled, forgotten)), "the exponent does not matter here"

@@ -14,7 +14,7 @@ import pytest
 import transfer_truth as T
 from gpu_common import check_blocks
 from helpers import compare_grids, grid_of, pipeline, report_margin, run_gpu, run_oracle
-from wgsparkl_amd.sharded import lockstep_slabs
+from wgsparkl_amd.sharded import join_slabs, lockstep_slabs
 
 pytestmark = pytest.mark.gpu
 
@@ -115,14 +115,9 @@ def _drifting(d, h, world, seed):
 
 
 def _export(shards, n):
-    outs = [s.export() for s in shards]
-    ids = np.concatenate([o["ids"] for o in outs]).astype(np.int64)
-    assert np.array_equal(np.sort(ids), np.arange(n)), (
-        f"every particle exactly once: per rank {[len(o['ids']) for o in outs]}, missing {np.setdiff1d(np.arange(n), ids)[:20].tolist()}, "
-        f"duplicated {np.unique(ids)[np.unique(ids, return_counts=True)[1] > 1][:20].tolist()}")
-    order = np.argsort(ids)
-    held = np.concatenate([np.full(len(o["ids"]), r) for r, o in enumerate(outs)])[order]
-    return {f: np.concatenate([o[f] for o in outs])[order] for f in ("pos", "vel", "def_grad", "affine", "mass")}, held
+    joined = join_slabs([s.export() for s in shards], np.arange(n), fields=("pos", "vel", "def_grad", "affine", "mass"))
+    assert joined.exact, joined.problem
+    return joined.fields, joined.holder
 
 
 @pytest.mark.parametrize("world,d,h", [(2, 3, 0.5), (3, 3, 0.3), (2, 2, 0.3), (3, 2, 2.0)])

@@ -5,7 +5,7 @@ import numpy as np
 from helpers import pipeline, rel_rms, run_gpu
 from wgsparkl_amd import scenes
 from wgsparkl_amd.models import ParticlePhase
-from wgsparkl_amd.sharded import lockstep_slabs, native_lockstep
+from wgsparkl_amd.sharded import join_slabs, lockstep_slabs, native_lockstep
 from wgsparkl_amd.solver import Collider, SimulationParams
 lo, hi = int(sys.argv[1]), int(sys.argv[2])
 k = int(sys.argv[3]) if len(sys.argv) > 3 else 30
@@ -38,12 +38,10 @@ for seed in range(lo, hi):
                 continue
             native_lockstep(pipe, shards, k)
             for s in shards: s.sync()
-            outs = [s.export() for s in shards]
-            ids = np.concatenate([o["ids"] for o in outs])
-            assert np.array_equal(np.sort(ids), np.arange(ps.n, dtype=np.uint32)), "ids"
-            order = np.argsort(ids)
+            joined = join_slabs([s.export() for s in shards], np.arange(ps.n))
+            assert joined.exact, joined.problem
             for f, tol in (("pos", 1e-5), ("vel", 2e-4)):
-                err = rel_rms(np.concatenate([o[f] for o in outs])[order], getattr(ref, f))
+                err = rel_rms(joined.fields[f], getattr(ref, f))
                 assert err < tol, (f, err)
         finally:   # (device memory of every seed is released whatever happened: a long range must not fail on leaked memory)
             for s in shards: s.close()

@@ -5,7 +5,7 @@ if os.environ.get("WGS_SOAK_NO_PERIOD") != "1": os.environ.setdefault("WGS_REHAS
 import numpy as np
 from helpers import pipeline
 from wgsparkl_amd import scenes
-from wgsparkl_amd.sharded import lockstep_slabs, native_lockstep
+from wgsparkl_amd.sharded import join_slabs, lockstep_slabs, native_lockstep
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
 for world, dim, floor in ((4, 3, True), (3, 2, True), (8, 3, False)):
     if dim == 3:
@@ -29,9 +29,8 @@ for world, dim, floor in ((4, 3, True), (3, 2, True), (8, 3, False)):
         n_now = [s.num_particles() for s in shards]
         crossed += sum(abs(a - b) for a, b in zip(n_now, n_prev)); n_prev = n_now
         assert sum(n_now) == ps.n, (done, n_now)
-    outs = [s.export() for s in shards]
-    ids = np.sort(np.concatenate([o["ids"] for o in outs]))
-    ok = np.array_equal(ids, np.arange(ps.n, dtype=np.uint32)) and all(np.isfinite(o["pos"]).all() and np.isfinite(o["vel"]).all() for o in outs)
+    joined = join_slabs([s.export() for s in shards], np.arange(ps.n), fields=("pos", "vel"))
+    ok = joined.exact and all(np.isfinite(v).all() for v in joined.fields.values())
     print(f"{world} slabs, {dim}D, floor={floor}: {steps} substeps, {ps.n} particles, {time.time()-t0:.1f}s, ids exact and finite: {ok}, net count changes {crossed}, per slab {n_prev}", flush=True)
-    assert ok
+    assert ok, joined.problem
     for s in shards: s.close()

@@ -373,6 +373,27 @@ class DataHandle:
         combining them is the caller's task."""
         return read_diagnostics(self.lib, self._h, self.dim, what)
 
+    def read_grid(self):
+        """(cells[int32 M x D], vel_mass[M x (D+1)], cdf_dist, cdf_aff, cdf_closest), lexicographically
+        sorted by cell coordinate (physical node ids are not comparable between runs). On a slab: the nodes of its own grid."""
+        T, D = self.T, self.dim
+        cnt = C.c_size_t(0)
+        _ffi.check(self.lib, self.lib.wgs_read_grid(self._h, None, 0, C.byref(cnt)))
+        m = cnt.value
+        words = C.sizeof(T.NodeRecord) // 4
+        raw = np.zeros((max(m, 1), words), np.int32)
+        if m:
+            _ffi.check(self.lib, self.lib.wgs_read_grid(self._h, raw.ctypes.data_as(C.POINTER(T.NodeRecord)), m, C.byref(cnt)))
+        raw = raw[:m]
+        cells = raw[:, :D].copy()
+        fl = raw.view(F32)
+        vm = fl[:, D:2 * D + 1].copy()
+        dist = fl[:, 2 * D + 1].copy()
+        aff = raw.view(np.uint32)[:, 2 * D + 2].copy()
+        closest = raw.view(np.uint32)[:, 2 * D + 3].copy()
+        order = np.lexsort(cells.T[::-1]) if m else np.zeros(0, np.int64)
+        return cells[order], vm[order], dist[order], aff[order], closest[order]
+
     def enqueue_diagnostics(self, device_ptr: int, what: int = _ffi.DIAG_PARTICLES):
         """`wgs_enqueue_diagnostics`: the same, stream-ordered; the struct (`ctypes.sizeof(_ffi.Diagnostics)` bytes) is left at the
         DEVICE address `device_ptr`. Returns at once."""
@@ -517,27 +538,6 @@ class MpmData(DataHandle):
         bit-exactly."""
         st = np.ascontiguousarray(dp_state, F32).reshape(self.n, 3)
         _ffi.check(self.lib, self.lib.wgs_set_plastic_state(self._h, st.ctypes.data_as(C.POINTER(self.T.PlasticState))))
-
-    def read_grid(self):
-        """(cells[int32 M x D], vel_mass[M x (D+1)], cdf_dist, cdf_aff, cdf_closest), lexicographically
-        sorted by cell coordinate (physical node ids are not comparable between runs)."""
-        T, D = self.T, self.dim
-        cnt = C.c_size_t(0)
-        _ffi.check(self.lib, self.lib.wgs_read_grid(self._h, None, 0, C.byref(cnt)))
-        m = cnt.value
-        words = C.sizeof(T.NodeRecord) // 4
-        raw = np.zeros((max(m, 1), words), np.int32)
-        if m:
-            _ffi.check(self.lib, self.lib.wgs_read_grid(self._h, raw.ctypes.data_as(C.POINTER(T.NodeRecord)), m, C.byref(cnt)))
-        raw = raw[:m]
-        cells = raw[:, :D].copy()
-        fl = raw.view(F32)
-        vm = fl[:, D:2 * D + 1].copy()
-        dist = fl[:, 2 * D + 1].copy()
-        aff = raw.view(np.uint32)[:, 2 * D + 2].copy()
-        closest = raw.view(np.uint32)[:, 2 * D + 3].copy()
-        order = np.lexsort(cells.T[::-1]) if m else np.zeros(0, np.int64)
-        return cells[order], vm[order], dist[order], aff[order], closest[order]
 
     def read_blocks(self, with_sorted_ids: bool = True):
         """(vid, first_particle, num_particles) sorted by vid, and sorted particle ids."""

@@ -14,10 +14,12 @@ from __future__ import annotations
 import numpy as np
 
 
-def _rel_rms(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    den = float(np.sqrt(np.mean(b * b)))
-    num = float(np.sqrt(np.mean((a - b) ** 2)))
+def rel_rms(a, b):
+    """RMS of (a - b) relative to RMS of b (b = truth)."""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64)
+    den = np.sqrt(np.mean(b * b))
+    num = np.sqrt(np.mean((a - b) ** 2))
     return num / den if den > 0 else num
 
 
@@ -29,7 +31,7 @@ def compare_with_single_domain(pipe, dist, comm, world, rank, slab, full_scene, 
     `wgs_sharded_step`, gathers every rank's particles on rank 0 and compares them with rank 0's single-domain run.
     Returns the same verdict dict on every rank ({"ok": bool, ...})."""
     from . import MpmData
-    from .sharded import NativeShard
+    from .sharded import NativeShard, join_slabs
     ps = slab["particles"]
     ys = ps.pos[:, 1] if ps.n else np.zeros(1, np.float32)
     zs = ps.pos[:, 2] if ps.n and ps.dim == 3 else np.zeros(1, np.float32)
@@ -65,15 +67,14 @@ def compare_with_single_domain(pipe, dist, comm, world, rank, slab, full_scene, 
         ref = data.read_particles()
         ref_bodies = data.read_body_poses() if full["colliders"] else []
         data.close()
-        ids = np.concatenate([g["ids"] for g in gathered]).astype(np.int64)
-        v = {"ranks": world, "substeps": substeps, "particles": int(fp.n), "ids_exact": bool(np.array_equal(np.sort(ids), np.sort(gid))),
-             "migrated": bool([len(g["ids"]) for g in gathered] != [g["n0"] for g in gathered]),
-             "particles_per_rank_after": [int(len(g["ids"])) for g in gathered], "against": "wgs_step on the whole scene, rank 0"}
-        if v["ids_exact"]:
-            order, ref_order = np.argsort(ids), np.argsort(gid)
-            for f, tol in (("pos", pos_tol), ("vel", vel_tol), ("def_grad", pos_tol)):
-                got = np.concatenate([g[f] for g in gathered])[order]
-                v[f + "_rel_rms"] = _rel_rms(got, getattr(ref, f)[ref_order])
+        joined = join_slabs(gathered, gid, fields=("pos", "vel", "def_grad"))
+        v = {"ranks": world, "substeps": substeps, "particles": int(fp.n), "ids_exact": joined.exact,
+             "migrated": bool(joined.counts != [g["n0"] for g in gathered]),
+             "particles_per_rank_after": joined.counts, "against": "wgs_step on the whole scene, rank 0"}
+        if joined.exact:
+            ref_order = np.argsort(gid)
+            for f in joined.fields:
+                v[f + "_rel_rms"] = float(rel_rms(joined.fields[f], getattr(ref, f)[ref_order]))
             v["ok"] = bool(v["pos_rel_rms"] < pos_tol and v["vel_rel_rms"] < vel_tol and v["def_grad_rel_rms"] < pos_tol)
         else:
             v["ok"] = False

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -176,16 +176,21 @@ class NativeShard(DataHandle):
     def num_particles(self) -> int:
         return self.stats()["num_particles"]
 
-    def export(self):
-        """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now (blocking)."""
+    def export_records(self) -> np.ndarray:
+        """The exchange records of the particles this rank holds now, float32 [count, record_floats(dim)]: every quad of the
+        particle, its global id and the substep its cdf was computed in (blocking). The one caller of `wgs_shard_export`."""
         import torch
         buf = torch.zeros(self.hdr + self.capacity * self.part_rec, dtype=torch.float32, device=torch.device("cuda", self.pipeline.device))
         # the library writes on its own non-blocking stream: torch's fill must be done first, or it can land on the export
         torch.cuda.current_stream(buf.device).synchronize()
         cnt = C.c_uint32(0)
         _ffi.check(self.lib, self.lib.wgs_shard_export(self._h, C.c_void_p(buf.data_ptr()), self.capacity, C.byref(cnt)))
-        rec = buf[self.hdr: self.hdr + cnt.value * self.part_rec].cpu().numpy().reshape(cnt.value, self.part_rec)
-        return unpack_records(rec, self.dim, self.uniform_material if self.dim == 3 else None)
+        return buf[self.hdr: self.hdr + cnt.value * self.part_rec].cpu().numpy().reshape(cnt.value, self.part_rec)
+
+    def export(self, cdf: bool = False):
+        """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now, with `cdf` also their cdf
+        (`unpack_records`); blocking."""
+        return unpack_records(self.export_records(), self.dim, self.uniform_material if self.dim == 3 else None, cdf)
 
 
 def native_lockstep(pipeline: MpmPipeline, shards: List[NativeShard], num_substeps: int):
@@ -223,9 +228,10 @@ def record_quad(rec: np.ndarray, dim: int, name: str) -> np.ndarray:
     return rec[:, 4 * k:4 * k + 4]
 
 
-def unpack_records(rec: np.ndarray, dim: int, uniform_material=None):
+def unpack_records(rec: np.ndarray, dim: int, uniform_material=None, cdf: bool = False):
     """Particle records (quad layout of csrc/layout.h) -> dict of arrays. In uniform-material mode (3D) the record's
-    XM.w slot holds F[8] and the mass is the shared one."""
+    XM.w slot holds F[8] and the mass is the shared one. `cdf`: also cdf_affinity, cdf_dist, cdf_normal and cdf_stamp, the
+    substep the cdf was computed in."""
     ids = rec[:, -2].copy().view(np.uint32)     # [..quads.., pid, cdf epoch]
     q = lambda name: record_quad(rec, dim, name)
     if dim == 3:
@@ -236,10 +242,51 @@ def unpack_records(rec: np.ndarray, dim: int, uniform_material=None):
         if uniform_material is not None:
             F = np.concatenate([q("F0"), q("F1"), q("XM")[:, 3:4]], 1)
             mass = np.full(len(rec), np.float32(uniform_material[0]), np.float32)
+        aff, dist, normal = q("CDF1")[:, 3], q("CDF0")[:, 3], q("CDF0")[:, :3]
     else:
         pos, mass = q("XM")[:, :2], q("XM")[:, 2]
         C_, vel, F = q("CV0"), q("CV2")[:, :2], q("F0")
-    return dict(ids=ids, pos=pos.copy(), vel=vel.copy(), def_grad=F.copy(), affine=C_.copy(), mass=mass.copy())
+        aff, dist, normal = q("CDF0")[:, 3], q("CDF0")[:, 2], q("CDF0")[:, :2]
+    out = dict(ids=ids, pos=pos.copy(), vel=vel.copy(), def_grad=F.copy(), affine=C_.copy(), mass=mass.copy())
+    if cdf:
+        out.update(cdf_affinity=aff.copy().view(np.uint32), cdf_dist=dist.copy(), cdf_normal=normal.copy(),
+                   cdf_stamp=rec[:, -1].copy().view(np.uint32))
+    return out
+
+
+class JoinedSlabs(NamedTuple):
+    """what join_slabs returns"""
+    ids: np.ndarray              # the ids the slabs hold, ascending (int64)
+    fields: dict                 # each field concatenated over the ranks, in the order of `ids`
+    holder: np.ndarray           # the rank that holds each particle, in the same order
+    counts: list                 # particles per rank
+    exact: bool                  # the ids are the expected set, each once
+    problem: str                 # the message of a failed `assert joined.exact`
+
+
+def join_slabs(outs, ids=None, fields=None) -> JoinedSlabs:
+    """The slabs of a decomposition as one domain, in the order of the global ids: a slab holds its particles in the order they
+    arrived, so ids, never slots, are what two runs have in common. `outs`: one mapping per rank with an "ids" entry (`export()`
+    dicts, a worker's saved arrays); `fields`: the per-particle entries to join (default: every key of the first mapping but
+    "ids"); `ids`: the expected ids (default: 0 .. total - 1). Pure numpy; raises nothing: `exact` is the verdict."""
+    fields = [k for k in outs[0].keys() if k != "ids"] if fields is None else fields
+    counts = [int(len(o["ids"])) for o in outs]
+    got = np.concatenate([o["ids"] for o in outs]).astype(np.int64)
+    order = np.argsort(got, kind="stable")
+    got = got[order]
+    want = np.arange(len(got)) if ids is None else np.sort(np.asarray(ids, np.int64))
+    uniq, times = np.unique(got, return_counts=True)
+    problem = (f"every particle exactly once: per rank {counts}, missing {np.setdiff1d(want, uniq)[:20].tolist()}, "
+               f"duplicated {uniq[times > 1][:20].tolist()}, unexpected {np.setdiff1d(uniq, want)[:20].tolist()}")
+    return JoinedSlabs(got, {f: np.concatenate([o[f] for o in outs])[order] for f in fields},
+                       np.concatenate([np.full(c, r) for r, c in enumerate(counts)])[order], counts, bool(np.array_equal(got, want)), problem)
+
+
+def by_id(out):
+    """One export with every entry in the order of ascending ids (stable): two slabs that hold the same particles compare
+    entry by entry, whatever order their slots are in."""
+    order = np.argsort(out["ids"], kind="stable")
+    return {k: v[order] for k, v in out.items()}
 
 
 def split_scene(particles: ParticleSet, partition: SlabPartition, cell_width: float):
