@@ -351,13 +351,46 @@ def dp_alpha64(dp, q):
     return np.sqrt(2.0 / 3.0) * (2.0 * sa) / (3.0 - sa)
 
 
-def dp_outcomes64(dp, state, F, svd):
+def dp_outcomes64(dp, state, F, svd, f_err=None):
     # F: [n, d, d] float64 (the fp32 input, unchanged by branch 'N')
     """fp64 Drucker-Prager (models/drucker_prager.wgsl) from an fp64 SVD, every branch evaluated: returns a dict with the
     decision quantities, the branch fp64 takes ('A' = projection to the tip, 'B' = onto the cone, 'N' = unchanged), the
-    outcome (F', state') of each branch, and the fp32 band around each threshold."""
+    outcome (F', state') of each branch, and the fp32 band around each threshold.
+
+    `f_err` [n] (None: 0, the input is an exact fp32 matrix): F is known only to within |dF|_F <= f_err — the matrix a kernel
+    projects is its own fp32 F_trial = F + (grad dt) F, the truth holds the fp64 one (tests/plastic_truth.py passes
+    transfer_truth's b_F). What that does to the bands and to the outcomes, to first order in f_err:
+
+    singular values: |ds_i| <= |dF|_2 <= f_err (Weyl), and |ds|_2 <= |dF|_F (Mirsky). With f_err <= s_min / 2 every value on
+    the segment between the two matrices is at least s_i - f_err >= s_i / 2, so a log-strain moves by at most
+    f_err / (s_i - f_err) <= 2 f_err / s_i (this sum is added to band_strain: the trace moves by at most the sum, |dev| by
+    at most the 2-norm of the movements, which is below it), and the whole strain vector by |d eps|_2 <= de := f_err /
+    (s_min - f_err). gamma = |dev| + c tr (c = coef alpha) moves by at most (1 + |c|) times the strains' sum: the existing
+    expression of band_gamma with the widened band_strain. A matrix with f_err > s_min / 2 may lose a singular value
+    altogether: `amb_input`, every branch allowed, counted as decision-ambiguous.
+
+    outcomes: each branch is an isotropic map F = U diag(s) V^T -> U diag(p(s)) V^T with p symmetric in s. In the frame of
+    U, V and with E = U^T dF V its derivative is, entry by entry (Daleckii-Krein for singular values),
+        diagonal       dp_i = sum_j (dp_i / ds_j) E_jj
+        i != j         (p_i - p_j) / (s_i - s_j) * (E_ij + E_ji) / 2  +  (p_i + p_j) / (s_i + s_j) * (E_ij - E_ji) / 2,
+    so |dF'|_F <= K |dF|_F with K the largest of the three kinds of coefficient.
+      N: p = s, K = 1; the state does not move.
+      A: p = 1: only the third kind is left, K = 2 / (s_i + s_j) at the two smallest values (the polar factor's bound).
+         state: hard = |eps| moves by at most de; log prev_det by at most sqrt(d) de (Cauchy-Schwarz on the sum), and st0
+         by |st0'| times that.
+      B: p_i = exp(H_i), H = (tr / d) 1 - c tr nhat, nhat = dev / |dev|. |d tr| <= sqrt(d) |d eps|, |d nhat| <= |d eps| / |dev|,
+         so |dH| <= (1 + sqrt(d) |c| + |c tr| / |dev|) |d eps| =: L |d eps| and the diagonal kind is at most p_max L / s_min.
+         H_i - H_j = -(c tr / |dev|) (log s_i - log s_j), so the first kind is at most p_max |c tr| / (|dev| s_min), below
+         it; the third is at most p_max / s_min, below it as well. K = p_max L / s_min — the cone map with the SVD's
+         kappa (1 / s_min against p_max) and the 1 / |dev| of the direction. state: hard = gamma moves by at most
+         (1 + sqrt(d) |c|) de, the two log dets by sqrt(d) de each.
+    s_min, |dev|, |tr| and p_max are taken at their worst on the segment (s - f_err, |dev| - de, |tr| + sqrt(d) de, p_max
+    exp(L de); the first two no further than a factor 2 from their value: beyond that the particle is ambiguous anyway).
+    tests/test_plastic_truth.py draws dF at |dF|_F = f_err and holds every branch's movement below K f_err (`lip_F`,
+    `lip_state` of each outcome)."""
     U, s, V = svd
     n, d = s.shape
+    fe = np.zeros(n) if f_err is None else np.broadcast_to(np.asarray(f_err, np.float64), (n,))
     dp = np.asarray(dp, np.float64)
     state = np.asarray(state, np.float64)
     with np.errstate(all="ignore"):
@@ -371,8 +404,18 @@ def dp_outcomes64(dp, state, F, svd):
         a = np.abs(s)
         kap = a.max(1)[:, None] / a
         # fp32 band of the strains: logf of a singular value that carries ~u s_max of round-off, plus the log's own ulp
-        band_strain = C_DEC * U32 * ((np.abs(np.log(a)) + kap).sum(1) + np.abs(state[:, 2]))
+        band_fp32 = C_DEC * U32 * ((np.abs(np.log(a)) + kap).sum(1) + np.abs(state[:, 2]))
+        band_strain = band_fp32 + (2.0 * fe[:, None] / a).sum(1)
         band_gamma = band_strain * (1.0 + np.abs(coef * alpha)) + C_DEC * U32 * (dev_norm + np.abs(coef * tr * alpha))
+        amb_input = fe > 0.5 * a.min(1)
+        # the segment's worst s, |dev|, |tr| (see the docstring); all of it exactly neutral at f_err = 0
+        a_eff = np.maximum(a - fe[:, None], 0.5 * a)
+        exact = fe == 0.0
+        de = np.where(exact, 0.0, fe / a_eff.min(1))
+        two = np.sort(a_eff, 1)[:, :2].sum(1)
+        c_abs = np.abs(coef * alpha)
+        dn_eff = np.maximum(dev_norm - de, 0.5 * dev_norm)
+        lip_H = 1.0 + np.sqrt(d) * c_abs + c_abs * (np.abs(tr) + np.sqrt(d) * de) / np.maximum(dn_eff, 1e-300)
         all_zero = np.all(dev == 0.0, axis=1)
         branch = np.where((tr > 0) | all_zero, "A", np.where(gamma > 0, "B", "N"))
         amb_trace = np.abs(tr) <= band_strain
@@ -397,18 +440,27 @@ def dp_outcomes64(dp, state, F, svd):
             # also the direction dev / |dev|, which carries the strains' band over |dev|
             rel = kap.max(1) + np.abs(strain).sum(1) + 1.0
             if br == "B":
-                rel = rel + np.abs(gamma) * band_strain / (C_DEC * U32) / np.maximum(dev_norm, 1e-300)
-            out[br] = dict(F=Fn, state=st, rel=rel, hard=hard, new_det=new_det)
+                rel = rel + np.abs(gamma) * band_fp32 / (C_DEC * U32) / np.maximum(dev_norm, 1e-300)
+            if br == "A":
+                lip_F = np.where(exact, 0.0, 2.0 * fe / two)
+                lip_state = np.stack([np.abs(st[:, 0]) * np.sqrt(d) * de, de, np.sqrt(d) * de], 1)
+            else:
+                lip_F = np.where(exact, 0.0, nsv.max(1) * np.exp(lip_H * de) * lip_H * de)
+                lip_state = np.stack([np.abs(st[:, 0]) * 2.0 * np.sqrt(d) * de, (1.0 + np.sqrt(d) * c_abs) * de, 2.0 * np.sqrt(d) * de], 1)
+            lip_state = np.where(exact[:, None], 0.0, lip_state)
+            out[br] = dict(F=Fn, state=st, rel=rel, hard=hard, new_det=new_det, lip_F=lip_F, lip_state=lip_state)
         out["N"] = dict(F=np.asarray(F, np.float64), state=state.copy(), rel=np.ones(n),
-                        hard=np.zeros(n), new_det=prev_det)
+                        hard=np.zeros(n), new_det=prev_det, lip_F=fe, lip_state=np.zeros((n, 3)))
     return dict(branch=branch, tr=tr, gamma=gamma, dev_norm=dev_norm, amb_trace=amb_trace, amb_zero=amb_zero,
-                amb_gamma=amb_gamma, out=out, prev_det=prev_det)
+                amb_gamma=amb_gamma, amb_input=amb_input, out=out, prev_det=prev_det)
 
 
 def dp_allowed(res):
     """[n] list of the branches a correct fp32 evaluation may take: the fp64 one, and across every threshold the fp64
-    values put within the fp32 band, the branch on its other side"""
-    allowed = []
+    values put within the fp32 band, the branch on its other side (computed once per `res`: dp_match asks per particle)"""
+    if "_allowed" in res:
+        return res["_allowed"]
+    allowed = res["_allowed"] = []
     for i, br in enumerate(res["branch"]):
         s = {br}
         other = "B" if res["gamma"][i] > 0 else "N"
@@ -416,6 +468,8 @@ def dp_allowed(res):
             s |= {"A", other}
         if res["amb_gamma"][i]:
             s |= {"B", "N"}
+        if res["amb_input"][i]:
+            s = {"A", "B", "N"}
         allowed.append(s)
     return allowed
 
@@ -429,12 +483,13 @@ def dp_match(res, i, changed, F_gpu, st_gpu, fnorm_in):
             continue
         Fo, so = o["F"][i], o["state"][i]
         scale_F = max(np.linalg.norm(Fo), fnorm_in) * o["rel"][i]
-        r = [np.linalg.norm(F_gpu - Fo) / (C_DP * U32 * scale_F)]
+        lf, ls = o["lip_F"][i], o["lip_state"][i]      # (the input's own uncertainty, dp_outcomes64: 0.0 for an exact input)
+        r = [np.linalg.norm(F_gpu - Fo) / (C_DP * U32 * scale_F + lf)]
         if br != "N":
             prev, new = abs(res["prev_det"][i]), abs(o["new_det"][i])
-            r.append(abs(st_gpu[0] - so[0]) / (C_DP * U32 * abs(so[0]) * o["rel"][i] * 4.0 + 1e-300))
-            r.append(abs(st_gpu[1] - so[1]) / (C_DP * U32 * (abs(so[1]) + o["rel"][i] * (abs(o["hard"][i]) + 1.0)) + 1e-300))
-            r.append(abs(st_gpu[2] - so[2]) / (C_DP * U32 * (abs(so[2]) + abs(np.log(prev)) + abs(np.log(new)) + o["rel"][i]) + 1e-300))
+            r.append(abs(st_gpu[0] - so[0]) / (C_DP * U32 * abs(so[0]) * o["rel"][i] * 4.0 + 1e-300 + ls[0]))
+            r.append(abs(st_gpu[1] - so[1]) / (C_DP * U32 * (abs(so[1]) + o["rel"][i] * (abs(o["hard"][i]) + 1.0)) + 1e-300 + ls[1]))
+            r.append(abs(st_gpu[2] - so[2]) / (C_DP * U32 * (abs(so[2]) + abs(np.log(prev)) + abs(np.log(new)) + o["rel"][i]) + 1e-300 + ls[2]))
         else:
             r.append(float(np.max(np.abs(st_gpu - so))) / (C_DP * U32 * (np.abs(so).max() + 1.0)))
         w = float(max(r))

@@ -175,3 +175,26 @@ def test_unpack_records_reads_the_words_the_quad_table_names(dim, uniform):
     assert set(plain) == {"ids", "pos", "vel", "def_grad", "affine", "mass"}
     for key in plain:
         assert plain[key].dtype == got[key].dtype and np.array_equal(plain[key], got[key]), key
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_unpack_records_reads_the_plastic_quads_on_request(dim):
+    """plastic=True adds dp, dp_state and phase from the words the general layout of DP0 / DP1 / DP2 names (h0..h3 | lambda, mu,
+    plastic det, hardening | log_vol_gain, phase, max_stretch), with and without the cdf keys; every other key is untouched."""
+    from wgsparkl_amd.sharded import QUADS, record_floats, unpack_records
+    n, nf = 4, record_floats(dim)
+    rec = (1000.0 * np.arange(1, n + 1)[:, None] + np.arange(nf)[None, :]).astype(np.float32)
+    rec.view(np.uint32)[:, -2] = 70 + np.arange(n)
+    w = lambda name, *lanes: rec[:, [4 * QUADS[dim][name] + k for k in lanes]]
+    want = dict(dp=np.concatenate([w("DP0", 0, 1, 2, 3), w("DP1", 0, 1)], 1), dp_state=np.concatenate([w("DP1", 2, 3), w("DP2", 0)], 1),
+                phase=w("DP2", 1, 2))
+    plain = unpack_records(rec, dim)
+    for cdf in (False, True):
+        base = unpack_records(rec, dim, cdf=cdf)
+        got = unpack_records(rec, dim, cdf=cdf, plastic=True)
+        assert set(got) == set(base) | set(want)
+        for key in want:
+            assert got[key].dtype == np.float32 and np.array_equal(got[key], want[key]), key
+        for key in base:
+            assert got[key].dtype == base[key].dtype and np.array_equal(got[key], base[key]), key
+    assert set(plain) == {"ids", "pos", "vel", "def_grad", "affine", "mass"}

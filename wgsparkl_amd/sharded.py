@@ -187,10 +187,10 @@ class NativeShard(DataHandle):
         _ffi.check(self.lib, self.lib.wgs_shard_export(self._h, C.c_void_p(buf.data_ptr()), self.capacity, C.byref(cnt)))
         return buf[self.hdr: self.hdr + cnt.value * self.part_rec].cpu().numpy().reshape(cnt.value, self.part_rec)
 
-    def export(self, cdf: bool = False):
-        """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now, with `cdf` also their cdf
-        (`unpack_records`); blocking."""
-        return unpack_records(self.export_records(), self.dim, self.uniform_material if self.dim == 3 else None, cdf)
+    def export(self, cdf: bool = False, plastic: bool = False):
+        """(global ids, pos, vel, def_grad, affine, mass) of the particles this rank owns now, with `cdf` also their cdf, with
+        `plastic` also their plasticity parameters, plastic state and phase (`unpack_records`); blocking."""
+        return unpack_records(self.export_records(), self.dim, self.uniform_material if self.dim == 3 else None, cdf, plastic)
 
 
 def native_lockstep(pipeline: MpmPipeline, shards: List[NativeShard], num_substeps: int):
@@ -228,10 +228,11 @@ def record_quad(rec: np.ndarray, dim: int, name: str) -> np.ndarray:
     return rec[:, 4 * k:4 * k + 4]
 
 
-def unpack_records(rec: np.ndarray, dim: int, uniform_material=None, cdf: bool = False):
+def unpack_records(rec: np.ndarray, dim: int, uniform_material=None, cdf: bool = False, plastic: bool = False):
     """Particle records (quad layout of csrc/layout.h) -> dict of arrays. In uniform-material mode (3D) the record's
     XM.w slot holds F[8] and the mass is the shared one. `cdf`: also cdf_affinity, cdf_dist, cdf_normal and cdf_stamp, the
-    substep the cdf was computed in."""
+    substep the cdf was computed in. `plastic`: also dp [n, 6], dp_state [n, 3] and phase [n, 2] in the general layout of the
+    DP quads, the only one a slab uses (layout.h: uni_dp is single-domain)."""
     ids = rec[:, -2].copy().view(np.uint32)     # [..quads.., pid, cdf epoch]
     q = lambda name: record_quad(rec, dim, name)
     if dim == 3:
@@ -251,6 +252,9 @@ def unpack_records(rec: np.ndarray, dim: int, uniform_material=None, cdf: bool =
     if cdf:
         out.update(cdf_affinity=aff.copy().view(np.uint32), cdf_dist=dist.copy(), cdf_normal=normal.copy(),
                    cdf_stamp=rec[:, -1].copy().view(np.uint32))
+    if plastic:      # DP0 = h0..h3; DP1 = lambda, mu, plastic det, hardening; DP2 = log_vol_gain, phase, max_stretch, -
+        out.update(dp=np.concatenate([q("DP0"), q("DP1")[:, :2]], 1), dp_state=np.concatenate([q("DP1")[:, 2:4], q("DP2")[:, :1]], 1),
+                   phase=q("DP2")[:, 1:3].copy())
     return out
 
 
