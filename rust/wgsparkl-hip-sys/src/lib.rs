@@ -1,7 +1,8 @@
 //! FFI declarations for include/wgsparkl_hip.h — SOURCE ONLY: this repository's build image has no
-//! Rust toolchain, so this file is not compiled or tested here (the ctypes twin wgsparkl_amd/_ffi.py is,
-//! by tests/test_capi_abi.py). See INTEGRATION.md §3 for the safe wrapper that keeps wgsparkl's
-//! `MpmPipeline` / `MpmData` surface.
+//! Rust toolchain, so this file is not compiled here. tests/test_abi.py holds it to the header all the same: every
+//! struct's repr(C) size and field offsets (computed, both dimensions), every constant's value and every function's
+//! parameter kinds against what gcc makes of the header. See INTEGRATION.md §3 for the safe wrapper that keeps
+//! wgsparkl's `MpmPipeline` / `MpmData` surface.
 //! build.rs: println!("cargo:rustc-link-lib=dylib=wgsparkl3d_hip");   (feature dim3; wgsparkl2d_hip for dim2)
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_void};
@@ -9,8 +10,42 @@ use std::os::raw::{c_char, c_void};
 pub const DIM: usize = if cfg!(feature = "dim2") { 2 } else { 3 };
 pub type wgs_status = i32;
 pub const WGS_OK: wgs_status = 0;
+pub const WGS_ERR_INVALID_ARGUMENT: wgs_status = 1;
+pub const WGS_ERR_NO_DEVICE: wgs_status = 2;
+pub const WGS_ERR_HIP: wgs_status = 3;
+pub const WGS_ERR_GRID_OVERFLOW: wgs_status = 4;
+pub const WGS_ERR_KEY_RANGE: wgs_status = 5;
+pub const WGS_ERR_UNSUPPORTED: wgs_status = 6;
 pub const WGS_MAX_COLLIDERS: usize = 16;
+/// `shape_type` of a `wgs_collider`
+pub const WGS_SHAPE_BALL: u32 = 0;
+pub const WGS_SHAPE_CUBOID: u32 = 1;
+pub const WGS_SHAPE_CAPSULE: u32 = 2;
+pub const WGS_SHAPE_MESH: u32 = 3;
+/// `wgs_set_constitutive_model`; the entries of `wgs_set_particle_models` (0 / 1 / 2); `wgs_diagnostics::model` (3 under a table)
+pub const WGS_MODEL_COROTATED: i32 = 0;
+pub const WGS_MODEL_NEO_HOOKEAN: i32 = 1;
+pub const WGS_MODEL_FLUID: i32 = 2;
+pub const WGS_MODEL_PER_PARTICLE: i32 = 3;
+/// indices into the `ms` of `wgs_read_timings`
+pub const WGS_PASS_UPDATE_RIGID_PARTICLES: usize = 0;
+pub const WGS_PASS_GRID_SORT: usize = 1;
+pub const WGS_PASS_GRID_UPDATE_CDF: usize = 2;
+pub const WGS_PASS_P2G_CDF: usize = 3;
+pub const WGS_PASS_G2P_CDF: usize = 4;
+pub const WGS_PASS_P2G: usize = 5;
+pub const WGS_PASS_GRID_UPDATE: usize = 6;
+pub const WGS_PASS_G2P: usize = 7;
+pub const WGS_PASS_PARTICLES_UPDATE: usize = 8;
+pub const WGS_PASS_INTEGRATE_BODIES: usize = 9;
 pub const WGS_NUM_PASSES: usize = 10;
+/// `mode` of `wgs_prep_vertex_buffer*` = RenderMode (src_testbed/prep_vertex_buffer.rs:11-18)
+pub const WGS_RENDER_DEFAULT: u32 = 0;
+pub const WGS_RENDER_VOLUME: u32 = 1;
+pub const WGS_RENDER_VELOCITY: u32 = 2;
+pub const WGS_RENDER_CDF_NORMALS: u32 = 3;
+pub const WGS_RENDER_CDF_DISTANCES: u32 = 4;
+pub const WGS_RENDER_CDF_SIGNS: u32 = 5;
 pub enum wgs_pipeline {}
 pub enum wgs_data {}
 
@@ -19,6 +54,29 @@ pub enum wgs_data {}
 pub struct wgs_sim_params {
     pub gravity: [f32; DIM],
     pub dt: f32,
+}
+/// The three small records `wgs_particle` holds flattened (`model`, `plasticity`, `phase`: the same bytes), by name.
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_elastic_coefficients {
+    pub lambda: f32,
+    pub mu: f32,
+}
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_drucker_prager {
+    pub h0: f32,
+    pub h1: f32,
+    pub h2: f32,
+    pub h3: f32,
+    pub lambda: f32,
+    pub mu: f32,
+}
+#[repr(C)]
+#[derive(Copy, Clone)]
+pub struct wgs_particle_phase {
+    pub phase: f32,
+    pub max_stretch: f32,
 }
 #[repr(C)]
 #[derive(Copy, Clone)]
@@ -241,6 +299,17 @@ pub const WGS_COMM_SELF_NEIGHBOURS: i32 = 1;
 
 /// include/wgsparkl_hip.h WGS_ABI_VERSION as this file mirrors it
 pub const ABI_VERSION: u32 = 7;
+
+/// The structs carry no size field, so a library built from another header version must be refused before anything else is called:
+/// `Err` holds the version the library reports. Call once after loading.
+pub fn check_abi() -> Result<(), u32> {
+    let got = unsafe { wgs_abi_version() };
+    if got == ABI_VERSION {
+        Ok(())
+    } else {
+        Err(got)
+    }
+}
 
 extern "C" {
     pub fn wgs_last_error() -> *const c_char;

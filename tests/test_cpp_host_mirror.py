@@ -26,7 +26,7 @@ def test_cpp_mirror_compiles_and_refuses_to_run_without_a_gpu(hip_libs, tmp_path
     if torch.cuda.is_available():
         assert r.returncode == 3, r.stdout          # a pipeline could be created
     else:
-        assert r.returncode == 0 and "status 2" in r.stdout, r.stdout + r.stderr
+        assert r.returncode == 0 and f"status {hip_libs.ERR_NO_DEVICE}" in r.stdout, r.stdout + r.stderr
 
 
 @pytest.mark.gpu

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 H, DT = FT.H, FT.DT
 ARRAYS = [f.name for f in dataclasses.fields(ParticleSet) if f.name != "dim"]
 FIELDS = ("stress", "mean_stress", "von_mises", "volume_ratio", "stretch", "model")
-UNSUPPORTED, INVALID = 6, 1
+UNSUPPORTED, INVALID = _ffi.ERR_UNSUPPORTED, _ffi.ERR_INVALID_ARGUMENT
 CANARY = 0x5a5a5a5a
 
 

@@ -204,18 +204,18 @@ def test_unsupported_on_plastic_data_and_eos_argument_checks(hip_libs, dim):
     _, data = new_data(sc)
     with pytest.raises(WgsError) as e:
         data.set_constitutive_model(MODEL_FLUID)
-    assert e.value.code == 6                                            # WGS_ERR_UNSUPPORTED
+    assert e.value.code == _ffi.ERR_UNSUPPORTED
     assert data.diagnostics(_ffi.DIAG_PARTICLES).model == MODEL_NEO_HOOKEAN
     data.pipeline.step(data, 2)
     data.sync()
     for bad in (1.0, 0.5, -7.0, float("nan"), float("inf")):
         with pytest.raises(WgsError) as e:
             data.set_fluid_eos(bad)
-        assert e.value.code == 1                                        # WGS_ERR_INVALID_ARGUMENT
+        assert e.value.code == _ffi.ERR_INVALID_ARGUMENT
     data.set_fluid_eos(1.5)                                             # allowed under any model
     with pytest.raises(WgsError) as e:
         data.set_constitutive_model(3)
-    assert e.value.code == 1
+    assert e.value.code == _ffi.ERR_INVALID_ARGUMENT
 
 
 def test_gamma_is_read_by_the_fluid_only_and_matters(hip_libs):

@@ -299,11 +299,11 @@ def test_refusals_leave_the_data_alone(hip_libs, dim):
     bad[-1] = 3
     with pytest.raises(WgsError) as e:
         data.set_particle_models(bad)
-    assert e.value.code == 1 and "entry" in str(e.value)              # WGS_ERR_INVALID_ARGUMENT, through wgs_last_error
+    assert e.value.code == _ffi.ERR_INVALID_ARGUMENT and "entry" in str(e.value)              # through wgs_last_error
     unchanged(data, state)
     with pytest.raises(WgsError) as e:
         data.set_constitutive_model(MODEL_PER_PARTICLE)                 # never a model to select
-    assert e.value.code == 1
+    assert e.value.code == _ffi.ERR_INVALID_ARGUMENT
     unchanged(data, state)
     # the same table again: not a bit changes
     data.set_particle_models(sc["models"])
@@ -335,7 +335,7 @@ def test_refusals_leave_the_data_alone(hip_libs, dim):
     assert np.all(st[2] == MODEL_NEO_HOOKEAN)
     with pytest.raises(WgsError) as e:
         pl.set_particle_models(np.zeros(ps.n, np.uint8))
-    assert e.value.code == 6 and "plastic" in str(e.value)             # WGS_ERR_UNSUPPORTED
+    assert e.value.code == _ffi.ERR_UNSUPPORTED and "plastic" in str(e.value)
     unchanged(pl, st)
     assert pl.diagnostics(_ffi.DIAG_PARTICLES).model == MODEL_NEO_HOOKEAN
     pl.set_particle_models(None)                                        # nothing to drop: fine
@@ -349,8 +349,8 @@ def test_sharded_data_is_refused(hip_libs):
     before = s.diagnostics(_ffi.DIAG_DIGEST).digest
     table = np.zeros(sc["particles"].n, np.uint8)
     for arg in (table.ctypes.data_as(C.POINTER(C.c_uint8)), None):
-        assert s.lib.wgs_set_particle_models(s._h, arg) == 6            # WGS_ERR_UNSUPPORTED
+        assert s.lib.wgs_set_particle_models(s._h, arg) == _ffi.ERR_UNSUPPORTED
         assert b"sharded" in s.lib.wgs_last_error()
-    assert s.lib.wgs_read_particle_models(s._h, table.ctypes.data_as(C.POINTER(C.c_uint8))) == 6
+    assert s.lib.wgs_read_particle_models(s._h, table.ctypes.data_as(C.POINTER(C.c_uint8))) == _ffi.ERR_UNSUPPORTED
     assert s.diagnostics(_ffi.DIAG_DIGEST).digest == before
     assert s.diagnostics(_ffi.DIAG_PARTICLES).model == MODEL_FLUID

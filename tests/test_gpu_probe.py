@@ -19,7 +19,7 @@ from wgsparkl_amd.solver import SimulationParams
 
 pytestmark = pytest.mark.gpu
 
-INVALID, UNSUPPORTED = 1, 6      # WGS_ERR_INVALID_ARGUMENT, WGS_ERR_UNSUPPORTED
+INVALID, UNSUPPORTED = _ffi.ERR_INVALID_ARGUMENT, _ffi.ERR_UNSUPPORTED
 
 
 def _bits(a):

@@ -316,23 +316,24 @@ def test_refusals_change_nothing(hip_libs, d):
     lo, hi = good[2].plane, good[3].plane
     bad = [arr(1, typ=4), arr(0, typ=0xffffffff), arr(2, friction=float("nan"), plane=lo), arr(2, friction=float("inf"), plane=lo),
            arr(3, friction=-0.5, plane=hi), arr(2, plane=hi), arr(2, plane=hi + 1), arr(3, plane=lo)]
+    invalid, unsupported = _ffi.ERR_INVALID_ARGUMENT, _ffi.ERR_UNSUPPORTED
     for a in bad:
-        assert lib.wgs_set_domain_walls(h, a) == 1 and lib.wgs_last_error()          # WGS_ERR_INVALID_ARGUMENT
+        assert lib.wgs_set_domain_walls(h, a) == invalid and lib.wgs_last_error()
         assert data.domain_walls() == good
-    assert lib.wgs_get_domain_walls(h, None) == 1 and lib.wgs_set_domain_walls(None, arr(0)) == 1 and lib.wgs_get_domain_walls(None, arr(0)) == 1
+    assert lib.wgs_get_domain_walls(h, None) == invalid and lib.wgs_set_domain_walls(None, arr(0)) == invalid and lib.wgs_get_domain_walls(None, arr(0)) == invalid
     assert _digest(data) == digest
     # low.plane >= high.plane is refused only where BOTH faces of the axis are set
     one = arr(2, plane=hi + 5)
     one[3].type = WALL_NONE
-    assert lib.wgs_set_domain_walls(h, one) == 0
+    assert lib.wgs_set_domain_walls(h, one) == _ffi.WGS_OK
     data.set_domain_walls(good)
     # a lockstep slab: WGS_ERR_UNSUPPORTED, in the words of the other single-domain calls
     shards, _ = lockstep_slabs(pipe, sc, 2)
     for s in shards:
         out = (_ffi.Wall * (2 * d))()
         C.memset(out, 0x5a, C.sizeof(out))
-        assert lib.wgs_set_domain_walls(s._h, arr(0)) == 6 and b"single-domain data only" in lib.wgs_last_error()
-        assert lib.wgs_get_domain_walls(s._h, out) == 6 and bytes(out) == b"\x5a" * C.sizeof(out)
+        assert lib.wgs_set_domain_walls(s._h, arr(0)) == unsupported and b"single-domain data only" in lib.wgs_last_error()
+        assert lib.wgs_get_domain_walls(s._h, out) == unsupported and bytes(out) == b"\x5a" * C.sizeof(out)
     assert _digest(data) == digest and data.domain_walls() == good
 
 

@@ -1,61 +1,26 @@
-"""-m "not gpu": the C ABI of the domain walls (include/wgsparkl_hip.h): wgs_wall has the size and the field offsets the header
-compiles to, in both dimensions; the two entry points are exported with full prototypes, next to wgs_set_grid_growth; every mirror
-declares them; calling them without a usable handle fails through the status path. No compute call is made here."""
+"""-m "not gpu": the domain walls (include/wgsparkl_hip.h) as far as a box without a GPU sees them: what the header says about
+them and where the documents name them; calling the two entry points without a usable handle fails through the status path; the
+Python mirror and the scenes. The layout of wgs_wall, the WGS_WALL_* values, the prototypes and the mirrors are tests/test_abi.py.
+No compute call is made here."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("wgs_set_domain_walls", "wgs_get_domain_walls")
-FIELDS = ("type", "friction", "plane")
-
-
-@pytest.mark.parametrize("dim", [2, 3])
-def test_wall_layout_matches_the_header(hip_libs, dim, tmp_path):
-    assert C.sizeof(hip_libs.Wall) == 12
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#define WGS_DIM {dim}', '#include "wgsparkl_hip.h"', 'int main(void) {',
-             '  printf("%zu", sizeof(wgs_wall));']
-    lines += [f'  printf(" %zu", offsetof(wgs_wall, {f}));' for f in FIELDS]
-    lines += ['  printf(" %d %d %d %d", WGS_WALL_NONE, WGS_WALL_STICKY, WGS_WALL_SLIP, WGS_WALL_SEPARATE);', '  printf("\\n");', '  return 0; }']
-    src, exe = tmp_path / "wall_abi.c", tmp_path / "wall_abi"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-std=c11", f"-I{os.path.join(ROOT, 'include')}", str(src), "-o", str(exe)], check=True)
-    seen = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert seen[0] == C.sizeof(hip_libs.Wall) == 12
-    assert seen[1:4] == [getattr(hip_libs.Wall, f).offset for f in FIELDS] == [0, 4, 8]
-    assert seen[4:] == [hip_libs.WALL_NONE, hip_libs.WALL_STICKY, hip_libs.WALL_SLIP, hip_libs.WALL_SEPARATE] == [0, 1, 2, 3]
-    from wgsparkl_amd import models
-    assert [models.WALL_NONE, models.WALL_STICKY, models.WALL_SLIP, models.WALL_SEPARATE] == seen[4:]
-
-
-@pytest.mark.parametrize("dim", [2, 3])
-def test_the_two_symbols_are_exported_with_prototypes(hip_libs, dim):
-    lib, T = hip_libs.load(dim)
-    names = list(hip_libs.prototypes(T))
-    at = names.index("wgs_set_grid_growth")
-    assert names[at + 1:at + 3] == list(NAMES), "the two prototypes stand behind wgs_set_grid_growth, in the header's order"
-    for name in NAMES:
-        fn = getattr(lib, name)                     # (AttributeError: the library does not export it)
-        assert fn.restype is C.c_int32 and len(fn.argtypes) == 2
-    assert lib.wgs_abi_version() == 7
 
 
 def test_the_header_tells_a_binding_how_to_detect_the_feature():
     header = open(os.path.join(ROOT, "include", "wgsparkl_hip.h")).read()
-    assert "#define WGS_ABI_VERSION 7" in header
     assert "detect wgs_set_domain_walls by symbol lookup" in header
     assert header.index("wgs_set_grid_growth(") < header.index("wgs_set_domain_walls(") < header.index("wgs_get_domain_walls(") < header.index("wgs_debug_scan(")
     assert "axis 0 low, axis 0 high, axis 1 low" in header, "the header states the order in which a corner node takes the faces"
     for said in ("AFTER the walls", "WGS_PASS_GRID_UPDATE", "(low.plane - 1.5) h"):
         assert said in header, said
-    hpp = open(os.path.join(ROOT, "include", "wgsparkl_hip.hpp")).read()
-    rs = open(os.path.join(ROOT, "rust", "wgsparkl-hip-sys", "src", "lib.rs")).read()
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in NAMES:
-        assert name + "(" in hpp and "pub fn " + name + "(" in rs and name in integration, name
-    assert "pub struct wgs_wall" in rs
+        assert name in integration, name
     for doc in ("README.md", "DESIGN.md"):
         assert "wgs_set_domain_walls" in open(os.path.join(ROOT, doc)).read(), doc
 
@@ -69,7 +34,7 @@ def test_calls_without_a_handle_fail_through_the_status_path(hip_libs, dim):
     C.memset(walls, 0x5a, C.sizeof(walls))
     for call in (lambda: lib.wgs_set_domain_walls(None, walls), lambda: lib.wgs_set_domain_walls(None, None),
                  lambda: lib.wgs_get_domain_walls(None, walls), lambda: lib.wgs_get_domain_walls(None, None)):
-        assert call() == 1                                   # WGS_ERR_INVALID_ARGUMENT
+        assert call() == hip_libs.ERR_INVALID_ARGUMENT
         assert lib.wgs_last_error()
     assert bytes(walls) == b"\x5a" * C.sizeof(walls)
 

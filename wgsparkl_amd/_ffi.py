@@ -13,7 +13,9 @@ import sys
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 
 WGS_OK = 0
-ABI_VERSION = 7   # include/wgsparkl_hip.h WGS_ABI_VERSION
+# wgs_status (include/wgsparkl_hip.h WGS_ERR_*): what WgsError.code and a raw call's return value compare with
+ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_GRID_OVERFLOW, ERR_KEY_RANGE, ERR_UNSUPPORTED = 1, 2, 3, 4, 5, 6
+ABI_VERSION = 7  # include/wgsparkl_hip.h WGS_ABI_VERSION
 WGS_NUM_PASSES = 10
 PASS_NAMES = ("update rigid particles", "grid sort", "grid_update_cdf", "p2g_cdf", "g2p_cdf", "p2g",
               "grid_update", "g2p", "particles_update", "integrate_bodies")  # src/pipeline.rs:201-271
