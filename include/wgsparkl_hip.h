@@ -220,7 +220,9 @@ const char *wgs_build_info(void);
  * added the same way (one new struct and four new symbols) — detect wgs_sample_grid by symbol lookup. Still 7: wgs_particle_field and
  * wgs_read_particle_fields[_device] were added the same way (one new struct and two new symbols) —
  * detect wgs_read_particle_fields by symbol lookup. Still 7: wgs_wall and wgs_set_domain_walls / wgs_get_domain_walls were added the
- * same way (one new struct, one enum and two new symbols) — detect wgs_set_domain_walls by symbol lookup. */
+ * same way (one new struct, one enum and two new symbols) — detect wgs_set_domain_walls by symbol lookup; and, still 7, the
+ * plasticity extension of wgsparkl_hip_plasticity.h (included below: wgs_set_plasticity_model / wgs_get_plasticity_model and the
+ * WGS_PLASTICITY_* values, one enum and two new symbols) — detect wgs_set_plasticity_model by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -410,6 +412,9 @@ typedef struct { uint32_t type; float friction; int32_t plane; } wgs_wall;   /* 
 wgs_status wgs_set_domain_walls(wgs_data *data, const wgs_wall *walls /* 2*WGS_DIM, or NULL */);
 /* What wgs_set_domain_walls last took (2 * WGS_DIM entries); all WGS_WALL_NONE when none is set. */
 wgs_status wgs_get_domain_walls(wgs_data *data, wgs_wall *out);
+/* The plasticity extension (snow): wgs_set_plasticity_model / wgs_get_plasticity_model and WGS_PLASTICITY_*, a header of their own that
+ * this one includes — what is declared in THIS file is the surface of ABI version 7 as it was first fixed, entry for entry. */
+#include "wgsparkl_hip_plasticity.h"
 /* Environment (read once per wgs_data_create; developer switches, none of them changes a result): WGS_DEBUG = bit mask of
  * launch-SHAPE choices (two launches instead of one paired launch, the general binning pass on every substep, the grid
  * update and the message packing as launches of their own instead of workgroups of the P2G launch, ...) and

@@ -145,6 +145,15 @@ class MpmData {
         check(wgs_get_domain_walls(h_, out.data()));
         return out;
     }
+    // the plasticity rule (no reference counterpart): WGS_PLASTICITY_DRUCKER_PRAGER (default) or WGS_PLASTICITY_SNOW — singular-value clamp
+    // with hardening on the corotated stress; the wgs_drucker_prager slots of a particle then read theta_c, theta_s, xi, exponent cap,
+    // switch, unused. Stream-ordered; single-domain data under WGS_MODEL_COROTATED.
+    void set_plasticity_model(int32_t kind) { check(wgs_set_plasticity_model(h_, kind)); }
+    int32_t plasticity_model() {
+        int32_t kind = WGS_PLASTICITY_DRUCKER_PRAGER;
+        check(wgs_get_plasticity_model(h_, &kind));
+        return kind;
+    }
     // device.poll(Maintain::Wait) (src/pipeline.rs:339); also reports device-side sticky errors (grid overflow, key range)
     void sync() { check(wgs_sync(h_)); }
     // the per-frame host -> device writes of src_testbed/step.rs:79-119 and ui.rs:91-104

@@ -216,6 +216,15 @@ def prototypes(T):
     }
 
 
+def plasticity_prototypes():
+    """name -> (restype, argtypes) of the entry points of include/wgsparkl_hip_plasticity.h, the plasticity extension the main header
+    includes (the plasticity rule of the data: Drucker-Prager | snow; no reference counterpart), in that header's order."""
+    return {
+        "wgs_set_plasticity_model": (C.c_int32, [C.c_void_p, C.c_int32]),
+        "wgs_get_plasticity_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    }
+
+
 EXPORTS = tuple(prototypes(make_types(3)))   # the names do not depend on the dimension
 
 _LIBS = {}
@@ -240,7 +249,7 @@ def load(dim: int):
         print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
-    for name, (restype, argtypes) in prototypes(T).items():
+    for name, (restype, argtypes) in {**prototypes(T), **plasticity_prototypes()}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)

@@ -54,3 +54,5 @@ using namespace wgs;
 #include "capi_fields.inc"       // ... extern "C": wgs_read_particle_fields[_device]
 #include "kernels_walls.h"       // domain walls: the projection of the wall nodes' velocities (behind them, likewise) ...
 #include "capi_walls.inc"        // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_domain_walls
+#include "capi_plasticity.inc"   // the plasticity rule: the snow instantiations of the fused G2P, the field read-out and the energy passes (behind
+                                 // them, likewise; their launch sites reach them by declaration) and extern "C": wgs_set / wgs_get_plasticity_model

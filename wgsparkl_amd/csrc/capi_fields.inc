@@ -3,6 +3,11 @@
 // enqueues on the data's stream; the host form stages through a Scratch and ends in download(), like the readers of
 // capi_io.inc. Neither writes simulation state, touches Dev or keeps device memory.
 
+namespace {
+// the same launch under WGS_PLASTICITY_SNOW on data with plastic state (capi_plasticity.inc: its kernel behind every other)
+void launch_particle_fields_snow(wgs_data *d, dim3 blocks, float *device_out);
+}
+
 extern "C" {
 
 wgs_status wgs_read_particle_fields_device(wgs_data *d, wgs_particle_field *device_out) {
@@ -14,8 +19,9 @@ wgs_status wgs_read_particle_fields_device(wgs_data *d, wgs_particle_field *devi
     const uint32_t n = d->dev.n;
     if (n == 0) return WGS_OK;
     const uint32_t groups = (n + FIELD_THREADS - 1) / FIELD_THREADS;
-    hipLaunchKernelGGL(k_particle_fields<D>, dim3(std::min(groups, (uint32_t)grid_for(d, 8))), dim3(FIELD_THREADS), 0, d->stream, d->dev,
-                       d->side, reinterpret_cast<float *>(device_out));
+    const dim3 blocks(std::min(groups, (uint32_t)grid_for(d, 8)));
+    if (d->plastic && d->plasticity == WGS_PLASTICITY_SNOW) launch_particle_fields_snow(d, blocks, reinterpret_cast<float *>(device_out));
+    else hipLaunchKernelGGL(k_particle_fields<D>, blocks, dim3(FIELD_THREADS), 0, d->stream, d->dev, d->side, reinterpret_cast<float *>(device_out));
     HIP_TRY(hipGetLastError());
     return WGS_OK;
 }

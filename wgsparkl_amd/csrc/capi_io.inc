@@ -105,6 +105,9 @@ wgs_status wgs_set_grid_growth(wgs_data *d, int32_t enabled) {
 wgs_status wgs_set_constitutive_model(wgs_data *d, int32_t model) {
     if (!d) return fail(WGS_ERR_INVALID_ARGUMENT, "data is NULL");
     if (model != WGS_MODEL_COROTATED && model != WGS_MODEL_NEO_HOOKEAN && model != WGS_MODEL_FLUID) return fail(WGS_ERR_INVALID_ARGUMENT, "unknown model");
+    // (snow is defined on the corotated stress and exists as instantiations of that model only: capi_plasticity.inc)
+    if (d->plasticity == WGS_PLASTICITY_SNOW && model != WGS_MODEL_COROTATED)
+        return fail(WGS_ERR_UNSUPPORTED, "wgs_set_constitutive_model: WGS_PLASTICITY_SNOW is set (wgs_set_plasticity_model): the corotated model only");
     if (model == WGS_MODEL_FLUID) {
         // (only the instantiations without plastic state exist for the fluid: host_substep.inc launch_g2p)
         if (d->plastic) return fail(WGS_ERR_UNSUPPORTED, "WGS_MODEL_FLUID: this data's step carries plastic state (Drucker-Prager particles, phases or force_plastic)");

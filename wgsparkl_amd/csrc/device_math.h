@@ -620,6 +620,30 @@ template <int D> __device__ inline bool drucker_prager_project(const float *dp, 
     return true;
 }
 
+// Snow (WGS_PLASTICITY_SNOW, include/wgsparkl_hip.h "Snow plasticity"; Stomakhin et al. 2013; no reference counterpart). The six
+// slots of a particle's wgs_drucker_prager are read as dp[0] = theta_c, dp[1] = theta_s, dp[2] = xi, dp[3] = the cap on the hardening
+// exponent. The hardening factor of a plastic volume ratio Jp: the ONE place that evaluates it (the step on the Jp it has just
+// updated, the read-outs on the stored one: both get the same bits).
+__device__ inline float snow_hardening(const float *dp, float jp) { return expf(fminf(dp[2] * (1.0f - jp), dp[3])); }
+
+// The projection: every signed singular value clamped to [1 - theta_c, 1 + theta_s] (an inverted or vanished one comes back to the
+// lower edge: 1 - theta_c > 0), Jp <- Jp prod |s_k| / prod s^_k, F <- U diag(s^) V^T. Updates `d.s`, state[0] and F in place like
+// drucker_prager_project; state[1] and state[2] are not touched. Returns the hardening factor of the UPDATED Jp.
+template <int D> __device__ inline float snow_project(const float *dp, float *state, float *F, Svd<D> &d) {
+    const float lo = 1.0f - dp[0], hi = 1.0f + dp[1];
+    float prev = 1.0f, now = 1.0f;
+#pragma unroll
+    for (int k = 0; k < D; k++) {
+        const float sc = fminf(fmaxf(d.s[k], lo), hi);
+        prev = prev * fabsf(d.s[k]);
+        now = now * sc;
+        d.s[k] = sc;
+    }
+    state[0] = state[0] * prev / now;
+    svd_recompose<D>(d, d.s, F);
+    return snow_hardening(dp, state[0]);
+}
+
 // grid/grid.wgsl:390-404 project_velocity (friction 20)
 template <int D> __device__ inline void project_velocity(const float *vel, const float *n, float *out) {
     float nv = 0.f;

@@ -5,12 +5,18 @@
 // MODEL: 0 corotated, 1 neo-Hookean, 2 fluid — one model for every particle — or 3: every particle under its OWN model, a byte that
 // travels with it (Dev::pmodel; loaded beside the pid through the sort permutation, stored beside it at the sorted slot). Only the
 // particle update knows: the transfer, the binning and the CPIC paths are those of the other models, word for word.
+// MODEL 4: the corotated model under the SNOW plasticity rule (WGS_PLASTICITY_SNOW, device_math.h snow_project; PLASTIC only). A value
+// of MODEL rather than a parameter of its own: every instantiation that existed keeps its name and its code, and the plastic pair —
+// beyond the instruction cache as it is — carries no branch for a rule it does not run. Everywhere but in the plastic block and at
+// the stress it is MODEL 0 (`COROT`).
 // SHARD: the data is one slab of a decomposition (particle counts in device counters, guests dropped, leavers listed).
 // A template parameter rather than the run-time field it mirrors: this kernel lives at the limit of its scalar
 // registers, and the single-domain instantiation should not carry a single one of them for a decomposition.
     constexpr bool CPIC = G2P_CMODE == 2;
     constexpr int BW = Dim<D>::BW, BS = Dim<D>::BSHIFT, TW = Dim<D>::TW, TILE = Dim<D>::TILE, NN = Dim<D>::NNBR;
     constexpr int DD = D * D;
+    constexpr bool COROT = MODEL == 0 || MODEL == 4;
+    static_assert(MODEL != 4 || PLASTIC, "the snow rule lives in the plastic block");
     // the node tile staged slice by slice (below): the one-chunk main body of the neo-Hookean elastic kernels in 3D on single-domain data — the
     // headline's pair and its collider-free twin, the two instantiations the change was timed on (notes/round_15.md). The list walk and the
     // multi-chunk kernels keep a staged tile across chunks, 2D tiles have no slices; the other models' one-chunk kernels, the plastic ones and a
@@ -147,7 +153,7 @@
         // VGPRs at the 168 cap in 3D, 8-20 B more scratch per lane than MODEL 0 where that one spills at all — the model byte and its
         // prefetched copy are two more values live across the pass). What upset the neo-Hookean kernels was measured on THEIR
         // allocation, which does not exist once the SVD is compiled in. Neither alternative was timed for MODEL 3.)
-        constexpr bool together = npass <= 2u || MODEL == 0 || MODEL == 3;
+        constexpr bool together = npass <= 2u || COROT || MODEL == 3;
         const uint32_t src_any = second ? nx_src : (((together ? inb : valid) && (together || g2p_wanted(cid_raw, only))) ? d.perm[j] : 0u);
         // (a visit's lane whose particle belongs to another block than the listed one asks for slot 0 instead of its particle)
         const uint32_t src = (second || g2p_wanted(cid_raw, only)) ? src_any : 0u;
@@ -269,7 +275,7 @@
             // (the block of the leader: by v_readlane — the id then lives in a scalar register and the kernels shed 4-32 B of scratch per
             // lane: C4's fused G2P 445 -> 413 us — except in the neo-Hookean elastic kernels, whose allocation the same change upsets:
             // the headline's ran 44.8 -> 46.5 us over five alternations on one box, C5's was a wash. They keep the permute.)
-            const uint32_t b = (MODEL == 0 || MODEL == 3 || PLASTIC) ? lane_value(myblock, leader) : (uint32_t)__shfl(myblock, leader);
+            const uint32_t b = (COROT || MODEL == 3 || PLASTIC) ? lane_value(myblock, leader) : (uint32_t)__shfl(myblock, leader);
             const bool mine = myblock == b;
             todo &= ~__ballot(mine);
             int bc[3] = {0, 0, 0};
@@ -697,8 +703,14 @@
                         for (int k = 0; k < D; k++) broken = broken || sv.s[k] > max_stretch;
                         if (broken) phase = 0.f;
                     }
-                    if (phase == 0.f && dp[4] != 0.f)  // particle_update.wgsl:118-122, drucker_prager.wgsl:134
-                        drucker_prager_project<D>(dp, st, Fm, sv);  // sv.s follows the projected F
+                    // (MODEL 4: the hardening factor of a snow particle — 1: the particle is not one — waits for the stress in tau[0], which nobody
+                    // has written yet. Not a variable of its own: the instantiations of the other models would declare it too, and two of
+                    // them came out of the compiler with a pair of instructions swapped)
+                    if constexpr (MODEL == 4) tau[0] = 1.0f;
+                    if (phase == 0.f && dp[4] != 0.f) {  // particle_update.wgsl:118-122, drucker_prager.wgsl:134
+                        if constexpr (MODEL == 4) tau[0] = snow_project<D>(dp, st, Fm, sv);   // (the same gate, the other rule)
+                        else drucker_prager_project<D>(dp, st, Fm, sv);  // sv.s follows the projected F
+                    }
                     if (d.uni_dp == 2u) {
                         stq(out, npad, P::DP1, j, make_float4(st[0], st[1], st[2], phase));
                     } else {
@@ -724,6 +736,10 @@
                     Fm[0] = fluid_update<D>(lambda, mu, d.fluid_gamma, grad, dt, Fm[0], tau);   // def_grad = diag(J, 1[, 1]): layout.h
                 } else if constexpr (MODEL == 1) {
                     kirchoff_neo_hookean<D>(lambda, mu, Fm, tau);
+                } else if constexpr (MODEL == 4) {
+                    // lambda hf, mu hf with hf of the UPDATED Jp; the stored coefficients stay the particle's own (hf is never stored)
+                    const float hf = tau[0];
+                    kirchoff_corotated<D>(lambda * hf, mu * hf, Fm, sv, tau);
                 } else {
                     if constexpr (!PLASTIC) svd<D>(Fm, sv);
                     kirchoff_corotated<D>(lambda, mu, Fm, sv, tau);

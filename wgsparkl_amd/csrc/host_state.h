@@ -282,6 +282,10 @@ struct wgs_data {
     // enqueue_finish then launches k_grid_walls behind the grid update, with these as its argument (no device memory)
     wgs_wall walls[2 * WGS_DIM] = {};
     bool walls_set = false;
+    // the plasticity rule (capi_plasticity.inc, wgs_set_plasticity_model): WGS_PLASTICITY_*. A host-side choice of instantiation —
+    // launch_g2p, the field read-out and the energy sum pick the snow kernels by it —, not a field of Dev: no kernel that existed
+    // gets another argument block
+    int32_t plasticity = WGS_PLASTICITY_DRUCKER_PRAGER;
 
     // ---- allocation: every device buffer above and in `dev` (dev_alloc; wgs_data_destroy releases them all)
     DeviceMemory mem;

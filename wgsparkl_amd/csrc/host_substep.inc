@@ -145,7 +145,8 @@ template <int DIM, int MODEL, bool PL, int NP, class Mark>
 void launch_g2p_shape(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark) {
     constexpr int WPE = PL ? WGS_PLASTIC_WPE : G2P_WAVES_PER_EU, WPE_DENSE = PL ? WGS_PLASTIC_WPE_DENSE : G2P_WAVES_PER_EU;
     // (per-particle models exist on single-domain data only — wgs_set_particle_models refuses slabs —: no slab instantiation of MODEL 3)
-    constexpr bool SH = MODEL != 3;
+    // (likewise the snow rule, MODEL 4: wgs_set_plasticity_model refuses slabs)
+    constexpr bool SH = MODEL != 3 && MODEL != 4;
     const dim3 g(p.g), pg(p.g + 8u * p.nlist), t(G2P_THREADS);
     switch (p.shape) {
         case G2pShape::pair_dense:
@@ -179,23 +180,31 @@ void launch_g2p_model(const Dev &dev, hipStream_t s, int side, uint32_t epoch, c
 // (the fluid exists without plastic state only — wgs_set_constitutive_model refuses it on such data — and comes last: the
 // instantiations of the other models keep their places in the code object)
 // (a table of per-particle models — Dev::pmodel, likewise without plastic state and on single-domain data only — behind the fluid)
-enum class G2pVariant { corotated, corotated_plastic, neo_hookean, neo_hookean_plastic, fluid, per_particle };
-G2pVariant g2p_variant(const Dev &dev, bool plastic) {
+// (snow — the corotated plastic variant under the other plasticity rule, wgs_set_plasticity_model; single-domain data with plastic
+// state only — behind them all, and its kernels behind every kernel of the library: launch_g2p_snow, capi_plasticity.inc)
+enum class G2pVariant { corotated, corotated_plastic, neo_hookean, neo_hookean_plastic, fluid, per_particle, snow };
+G2pVariant g2p_variant(const Dev &dev, bool plastic, int32_t plasticity = WGS_PLASTICITY_DRUCKER_PRAGER) {
+    // (WGS_PLASTICITY_SNOW is only ever set under WGS_MODEL_COROTATED, and plastic data carries no table: wgs_set_plasticity_model)
+    if (plastic && plasticity == WGS_PLASTICITY_SNOW) return G2pVariant::snow;
     if (dev.pmodel[0]) return G2pVariant::per_particle;
     if (dev.model == WGS_MODEL_FLUID) return G2pVariant::fluid;
     if (dev.model == WGS_MODEL_NEO_HOOKEAN) return plastic ? G2pVariant::neo_hookean_plastic : G2pVariant::neo_hookean;
     return plastic ? G2pVariant::corotated_plastic : G2pVariant::corotated;
 }
 
+struct Mark;
+void launch_g2p_snow(const Dev &dev, hipStream_t s, int side, uint32_t epoch, const G2pLaunch &p, const Mark &mark);   // capi_plasticity.inc
+
 // the fused G2P; `mark(6)` between the two launches of that shape
-template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, const G2pLaunch &p, const Mark &mark) {
-    switch (g2p_variant(dev, plastic)) {
+template <int DIM, class Mark> void launch_g2p(const Dev &dev, hipStream_t s, int side, uint32_t epoch, bool plastic, int32_t plasticity, const G2pLaunch &p, const Mark &mark) {
+    switch (g2p_variant(dev, plastic, plasticity)) {
         case G2pVariant::corotated: launch_g2p_model<DIM, 0, false>(dev, s, side, epoch, p, mark); break;
         case G2pVariant::corotated_plastic: launch_g2p_model<DIM, 0, true>(dev, s, side, epoch, p, mark); break;
         case G2pVariant::neo_hookean: launch_g2p_model<DIM, 1, false>(dev, s, side, epoch, p, mark); break;
         case G2pVariant::neo_hookean_plastic: launch_g2p_model<DIM, 1, true>(dev, s, side, epoch, p, mark); break;
         case G2pVariant::fluid: launch_g2p_model<DIM, 2, false>(dev, s, side, epoch, p, mark); break;
         case G2pVariant::per_particle: launch_g2p_model<DIM, 3, false>(dev, s, side, epoch, p, mark); break;
+        case G2pVariant::snow: launch_g2p_snow(dev, s, side, epoch, p, mark); break;   // (MODEL 4, instantiated behind every other kernel)
     }
 }
 
@@ -509,7 +518,7 @@ template <int DIM> wgs_status enqueue_finish(wgs_data *d) {
     mark(5);
     // ---- "g2p" + "particles_update", fused (mark 6: between the two launches of a collider simulation's G2P)
     const G2pLaunch g2p = plan_g2p(d);
-    if (dev.nv > 0) launch_g2p<DIM>(dev, s, side, epoch, d->plastic, g2p, mark);
+    if (dev.nv > 0) launch_g2p<DIM>(dev, s, side, epoch, d->plastic, d->plasticity, g2p, mark);
     if (!(dev.nv > 0 && g2p.shape == G2pShape::two_launches)) mark(6);
     // sharded step: the particles that arrived with this substep's messages are advanced too (kernels_arrivals.h), by a
     // launch of their own behind the fused G2P. (As extra workgroups INSIDE that launch — first or last in its grid — they

@@ -220,134 +220,30 @@ __device__ inline unsigned long long diag_abs_bits(double t) { return (unsigned 
 // Pass 1 over the particles. PART: counts of non-finite particles, bounds, the largest |term| of every particle sum (ENERGY: of
 // WGS_SUM_ELASTIC too); DIGEST: the two digest sums. `phase_by_pid`: the caller's input phase of data whose step carries no plastic
 // state (null on sharded data of that kind).
+// SNOW (the bodies below; data with plastic state under WGS_PLASTICITY_SNOW, kernels in capi_plasticity.inc): WGS_SUM_ELASTIC takes Psi
+// of a snow particle — phase == 0 and plasticity.lambda != 0 in the stored state — with lambda hf, mu hf, hf of its stored Jp
+// (device_math.h snow_hardening): the coefficients of the stress the step applied. Nothing else differs; the digest hashes the stored
+// coefficients.
+__device__ inline void diag_snow_harden(Unpacked &u) {
+    if (u.phase[0] == 0.f && u.dp[4] != 0.f) {
+        const float hf = snow_hardening(u.dp, u.st[0]);
+        u.lam = u.lam * hf;
+        u.mu = u.mu * hf;
+    }
+}
+
+// (the bodies of the two passes are included textually — diag_pass1_body.inc / diag_pass2_body.inc, with SNOW in scope — so that the snow
+// kernels of capi_plasticity.inc compile the very text of these and these stay the code they were)
 template <bool PART, bool ENERGY, bool DIGEST>
 __global__ __launch_bounds__(256) void k_diag_pass1(Dev d, int side, bool plastic, const float *phase_by_pid, DiagAcc *acc) {
-    __shared__ unsigned long long s_add[DA_NADD], s_tmax[DG_PARTICLE_GROUPS];
-    __shared__ uint32_t s_umax[DM_NMAX], s_umin[DN_NMIN];
-    if (threadIdx.x < DA_NADD) s_add[threadIdx.x] = 0ull;
-    if (threadIdx.x < DG_PARTICLE_GROUPS) s_tmax[threadIdx.x] = 0ull;
-    if (threadIdx.x < DM_NMAX) s_umax[threadIdx.x] = 0u;
-    if (threadIdx.x < DN_NMIN) s_umin[threadIdx.x] = 0xffffffffu;
-    __syncthreads();
-    const float *in = d.buf[side];
-    const uint32_t npad = d.npad, n = num_slots(d);
-    const double h2q = 0.25 * (double)d.h * (double)d.h;
-    const double grav[3] = {(double)d.sp->gravity[0], (double)d.sp->gravity[1], D == 3 ? (double)d.sp->gravity[D - 1] : 0.0};
-    unsigned long long add[DA_NADD] = {0ull, 0ull, 0ull, 0ull}, tmax[DG_PARTICLE_GROUPS];
-    uint32_t umax[DM_NMAX], umin[DN_NMIN];
-    for (int k = 0; k < DG_PARTICLE_GROUPS; k++) tmax[k] = 0ull;
-    for (int k = 0; k < DM_NMAX; k++) umax[k] = 0u;
-    for (int k = 0; k < DN_NMIN; k++) umin[k] = 0xffffffffu;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
-        const uint32_t pid = ldpid<D>(in, npad, j);
-        if (pid == PID_DEAD) continue;
-        Unpacked u;
-        unpack_slot<D>(in, npad, j, DIGEST && plastic, false, 0u, u);
-        fix_uniform<D>(d, u);
-        add[DA_COUNT]++;
-        if constexpr (DIGEST) {
-            float st[3] = {1.f, 1.f, 0.f}, ph[2] = {0.f, 0.f};
-            if (plastic) {
-                for (int k = 0; k < 3; k++) st[k] = u.st[k];
-                ph[0] = u.phase[0]; ph[1] = u.phase[1];
-            } else if (phase_by_pid) {
-                ph[0] = phase_by_pid[(size_t)pid * 2]; ph[1] = phase_by_pid[(size_t)pid * 2 + 1];
-            }
-            const unsigned long long h = diag_hash(pid, u, st, ph);
-            add[DA_DIGEST0] += h;
-            add[DA_DIGEST1] += diag_mix(h + DIAG_SECOND);
-        }
-        if constexpr (PART) {
-            if (!diag_finite(u)) { add[DA_NONFINITE]++; continue; }
-            double t[DIAG_PARTICLE_SUMS];
-            // (Psi of the particle's OWN model where the data carries a table: layout.h Dev::pmodel)
-            diag_particle_terms<ENERGY>(u, h2q, grav, d.pmodel[side] ? (int)d.pmodel[side][j] : d.model, (double)d.fluid_gamma, t);
-#pragma unroll
-            for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) {
-                const unsigned long long b = diag_abs_bits(t[s]);
-                tmax[diag_group_of(s)] = b > tmax[diag_group_of(s)] ? b : tmax[diag_group_of(s)];
-            }
-            double vv = 0.0, aa = 0.0;
-            float vinf = 0.f;
-            for (int k = 0; k < D; k++) {
-                const uint32_t o = diag_ord(u.x[k]);
-                umax[DM_AABB + k] = max(umax[DM_AABB + k], o);
-                umin[DN_AABB + k] = min(umin[DN_AABB + k], o);
-                vv += (double)u.v[k] * (double)u.v[k];
-                vinf = fmaxf(vinf, fabsf(u.v[k]));
-            }
-            for (int k = 0; k < DD; k++) aa += (double)u.C[k] * (double)u.C[k];
-            const uint32_t det = diag_ord((float)diag_det(u.F));
-            umax[DM_DET] = max(umax[DM_DET], det);
-            umin[DN_DET] = min(umin[DN_DET], det);
-            // (non-negative fp32 values: their bit patterns are ordered as they are)
-            umax[DM_SPEED] = max(umax[DM_SPEED], __float_as_uint((float)sqrt(vv)));
-            umax[DM_AFFINE] = max(umax[DM_AFFINE], __float_as_uint((float)sqrt(aa)));
-            umax[DM_VINF] = max(umax[DM_VINF], __float_as_uint(vinf));
-            const double w2 = u.mass > 0.f ? ((double)u.lam + 2.0 * (double)u.mu) * (double)u.vol / (double)u.mass : 0.0;
-            if (w2 > 0.0) umax[DM_WAVE] = max(umax[DM_WAVE], __float_as_uint((float)sqrt(w2)));
-        }
-    }
-    const bool leader = (threadIdx.x & 63u) == 0u;
-    for (int k = 0; k < DA_NADD; k++) {
-        const unsigned long long v = diag_wave_add(add[k]);
-        if (leader && v) atomicAdd(&s_add[k], v);
-    }
-    if constexpr (PART) {
-        for (int k = 0; k < DG_PARTICLE_GROUPS; k++) {
-            const unsigned long long v = diag_wave_max(tmax[k]);
-            if (leader) atomicMax(&s_tmax[k], v);
-        }
-        for (int k = 0; k < DM_NMAX; k++) {
-            const uint32_t v = diag_wave_max(umax[k]);
-            if (leader) atomicMax(&s_umax[k], v);
-        }
-        for (int k = 0; k < DN_NMIN; k++) {
-            const uint32_t v = diag_wave_min(umin[k]);
-            if (leader) atomicMin(&s_umin[k], v);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < DA_NADD && s_add[threadIdx.x]) atomicAdd(&acc->add[threadIdx.x], s_add[threadIdx.x]);
-    if constexpr (PART) {
-        if (threadIdx.x < DG_PARTICLE_GROUPS && s_tmax[threadIdx.x]) atomicMax(&acc->tmax[threadIdx.x], s_tmax[threadIdx.x]);
-        if (threadIdx.x < DM_NMAX) atomicMax(&acc->umax[threadIdx.x], s_umax[threadIdx.x]);
-        if (threadIdx.x < DN_NMIN) atomicMin(&acc->umin[threadIdx.x], s_umin[threadIdx.x]);
-    }
+    constexpr bool SNOW = false;
+#include "diag_pass1_body.inc"
 }
 
 // Pass 2 over the particles: rint(term * 2^-exponent) as int64, summed
 template <bool ENERGY> __global__ __launch_bounds__(256) void k_diag_pass2(Dev d, int side, DiagAcc *acc) {
-    __shared__ unsigned long long s_fixed[DIAG_PARTICLE_SUMS];
-    if (threadIdx.x < DIAG_PARTICLE_SUMS) s_fixed[threadIdx.x] = 0ull;
-    __syncthreads();
-    const float *in = d.buf[side];
-    const uint32_t npad = d.npad, n = num_slots(d);
-    const double h2q = 0.25 * (double)d.h * (double)d.h;
-    const double grav[3] = {(double)d.sp->gravity[0], (double)d.sp->gravity[1], D == 3 ? (double)d.sp->gravity[D - 1] : 0.0};
-    double scale[DG_PARTICLE_GROUPS];
-    for (int k = 0; k < DG_PARTICLE_GROUPS; k++) scale[k] = acc->scale[k];
-    unsigned long long fixed[DIAG_PARTICLE_SUMS];   // (two's complement: the wrap-around sum of the bit patterns is the signed sum)
-    for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) fixed[s] = 0ull;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
-        if (ldpid<D>(in, npad, j) == PID_DEAD) continue;
-        Unpacked u;
-        unpack_slot<D>(in, npad, j, false, false, 0u, u);
-        fix_uniform<D>(d, u);
-        if (!diag_finite(u)) continue;
-        double t[DIAG_PARTICLE_SUMS];
-        diag_particle_terms<ENERGY>(u, h2q, grav, d.pmodel[side] ? (int)d.pmodel[side][j] : d.model, (double)d.fluid_gamma, t);
-#pragma unroll
-        for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) fixed[s] += (unsigned long long)__double2ll_rn(t[s] * scale[diag_group_of(s)]);
-    }
-    const bool leader = (threadIdx.x & 63u) == 0u;
-    for (int s = 0; s < DIAG_PARTICLE_SUMS; s++) {
-        const unsigned long long v = diag_wave_add(fixed[s]);
-        if (leader && v) atomicAdd(&s_fixed[s], v);
-    }
-    __syncthreads();
-    if (threadIdx.x < DIAG_PARTICLE_SUMS && s_fixed[threadIdx.x])
-        atomicAdd(reinterpret_cast<unsigned long long *>(&acc->fixed[threadIdx.x]), s_fixed[threadIdx.x]);
+    constexpr bool SNOW = false;
+#include "diag_pass2_body.inc"
 }
 
 // The grid sums walk the active list like k_export_grid: node t of the list is node t & 63 of block active[t >> 6]. PASS 1: the largest
@@ -469,6 +365,10 @@ template <int DIM> __global__ void k_diag_finish(Dev d, DiagAcc *acc, uint32_t w
     *out = r;
 }
 
+// the two passes over the particles under WGS_PLASTICITY_SNOW with WGS_DIAG_ENERGY (capi_plasticity.inc: kernels behind every other)
+void launch_diag_pass1_snow(wgs_data *d, bool digest, dim3 blocks, DiagAcc *acc);
+void launch_diag_pass2_snow(wgs_data *d, dim3 blocks, DiagAcc *acc);
+
 // the launches of one diagnostics call, in stream order; `out` is device memory
 wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     if (what == 0u || (what & ~(uint32_t)(WGS_DIAG_PARTICLES | WGS_DIAG_ENERGY | WGS_DIAG_GRID | WGS_DIAG_DIGEST)))
@@ -482,7 +382,10 @@ wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     const float *phase = (d->plastic || d->dev.sharded) ? nullptr : d->static_phase;
     hipLaunchKernelGGL(k_diag_init<D>, dim3(1), dim3(64), 0, d->stream, acc);
 #define DIAG_PASS1(P, E, G) hipLaunchKernelGGL((k_diag_pass1<P, E, G>), blocks, threads, 0, d->stream, d->dev, d->side, d->plastic, phase, acc)
-    if (part && energy && digest) DIAG_PASS1(true, true, true);
+    // (the hardened coefficients enter WGS_SUM_ELASTIC alone: every other request launches what it always did)
+    const bool snow = energy && d->plastic && d->plasticity == WGS_PLASTICITY_SNOW;
+    if (snow) launch_diag_pass1_snow(d, digest, blocks, acc);
+    else if (part && energy && digest) DIAG_PASS1(true, true, true);
     else if (part && energy) DIAG_PASS1(true, true, false);
     else if (part && digest) DIAG_PASS1(true, false, true);
     else if (part) DIAG_PASS1(true, false, false);
@@ -492,7 +395,8 @@ wgs_status diag_enqueue(wgs_data *d, uint32_t what, wgs_diagnostics *out) {
     if (grid) hipLaunchKernelGGL(k_diag_grid<1>, blocks, threads, 0, d->stream, d->dev, acc);
     if (part || grid) hipLaunchKernelGGL(k_diag_scales<D>, dim3(1), dim3(64), 0, d->stream, acc);
     if (part) {
-        if (energy) hipLaunchKernelGGL(k_diag_pass2<true>, blocks, threads, 0, d->stream, d->dev, d->side, acc);
+        if (snow) launch_diag_pass2_snow(d, blocks, acc);
+        else if (energy) hipLaunchKernelGGL(k_diag_pass2<true>, blocks, threads, 0, d->stream, d->dev, d->side, acc);
         else hipLaunchKernelGGL(k_diag_pass2<false>, blocks, threads, 0, d->stream, d->dev, d->side, acc);
     }
     if (grid) hipLaunchKernelGGL(k_diag_grid<2>, blocks, threads, 0, d->stream, d->dev, acc);

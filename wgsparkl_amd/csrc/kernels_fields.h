@@ -31,10 +31,20 @@ template <> struct FieldVec<2> {
 };
 
 // One record from one slot. `rec` is the record's words in the order of the struct.
-template <int DIM> __device__ inline void particle_field(const Dev &d, int side, const float *in, uint32_t j, float *rec) {
+// SNOW (data with plastic state under WGS_PLASTICITY_SNOW, corotated): a snow particle — the step's gate on the STORED state, phase == 0
+// and plasticity.lambda != 0 — takes lambda hf, mu hf with hf of its stored Jp (device_math.h snow_hardening): the coefficients the
+// step that stored the state applied. Every other particle is evaluated as without the switch, by the same instructions.
+template <int DIM, bool SNOW = false> __device__ inline void particle_field(const Dev &d, int side, const float *in, uint32_t j, float *rec) {
     Unpacked u;
-    unpack_slot<DIM>(in, d.npad, j, false, false, 0u, u);
+    unpack_slot<DIM>(in, d.npad, j, SNOW, false, 0u, u);
     fix_uniform<DIM>(d, u);
+    if constexpr (SNOW) {
+        if (u.phase[0] == 0.f && u.dp[4] != 0.f) {
+            const float hf = snow_hardening(u.dp, u.st[0]);
+            u.lam = u.lam * hf;
+            u.mu = u.mu * hf;
+        }
+    }
     // (the particle's own model where the data carries a table: layout.h Dev::pmodel)
     const int model = d.pmodel[side] ? (int)d.pmodel[side][j] : d.model;
     float tau[DD], s[D], J;
@@ -95,32 +105,11 @@ template <int DIM> __device__ inline void particle_field(const Dev &d, int side,
 // instead and FIELD_UNITS consecutive lanes write one record as vectors — in 3D four lanes fill one aligned 64-byte piece.
 // `out` must be aligned to a vector (16 bytes in 3D, 8 in 2D: capi_fields.inc checks). No atomics; a record depends on its
 // particle only.
+// (the body is included textually — fields_body.inc, with SNOW in scope — so that the snow kernel of capi_plasticity.inc compiles the
+// very text of this one and this one stays the code it was)
 template <int DIM> __global__ __launch_bounds__(FIELD_THREADS) void k_particle_fields(Dev d, int side, float *out) {
-    using V = typename FieldVec<FIELD_VEC>::type;
-    __shared__ __attribute__((aligned(16))) float s_rec[FIELD_THREADS * FIELD_STRIDE];
-    __shared__ uint32_t s_pid[FIELD_THREADS];
-    const float *in = d.buf[side];
-    const uint32_t n = d.n;
-    for (uint32_t base = blockIdx.x * FIELD_THREADS; base < n; base += gridDim.x * FIELD_THREADS) {   // (uniform over the workgroup)
-        const uint32_t j = base + threadIdx.x;
-        if (j < n) {
-            float rec[FIELD_WORDS];
-            particle_field<DIM>(d, side, in, j, rec);
-            V *row = reinterpret_cast<V *>(s_rec + threadIdx.x * FIELD_STRIDE);
-#pragma unroll
-            for (int k = 0; k < FIELD_UNITS; k++) row[k] = FieldVec<FIELD_VEC>::make(rec + FIELD_VEC * k);
-            s_pid[threadIdx.x] = ldpid<DIM>(in, d.npad, j);
-        }
-        __syncthreads();
-        const uint32_t units = min((uint32_t)FIELD_THREADS, n - base) * FIELD_UNITS;
-        for (uint32_t t = threadIdx.x; t < units; t += FIELD_THREADS) {
-            const uint32_t r = t / FIELD_UNITS, k = t - r * FIELD_UNITS;
-            const uint32_t pid = s_pid[r];
-            if (pid < n)   // (single-domain data: a permutation of [0, n); nothing is ever written past the caller's n records)
-                reinterpret_cast<V *>(out + (size_t)pid * FIELD_WORDS)[k] = reinterpret_cast<const V *>(s_rec + r * FIELD_STRIDE)[k];
-        }
-        __syncthreads();
-    }
+    constexpr bool SNOW = false;
+#include "fields_body.inc"
 }
 
 }  // namespace

@@ -86,6 +86,47 @@ class DruckerPrager:
         return np.array([self.h0, self.h1, self.h2, self.h3, self.lambda_, self.mu], dtype=F32)
 
 
+# Plasticity rule of an MpmData (include/wgsparkl_hip_plasticity.h WGS_PLASTICITY_*; `MpmData.set_plasticity_model`): what the six plasticity
+# slots of a particle mean and which projection the plastic particle update applies.
+PLASTICITY_DRUCKER_PRAGER = 0   # models/drucker_prager.wgsl (reference default)
+PLASTICITY_SNOW = 1             # singular-value clamp with hardening (Stomakhin et al. 2013; no reference counterpart)
+
+
+@dataclass(frozen=True)
+class Snow:
+    """Parameters of PLASTICITY_SNOW, carried in the six slots of `DruckerPrager` reinterpreted (include/wgsparkl_hip_plasticity.h
+    "Snow plasticity"): h0 = theta_c (critical compression), h1 = theta_s (critical stretch), h2 = xi (hardening coefficient),
+    h3 = the cap on the hardening exponent xi (1 - Jp), lambda = the switch (non-zero: on), mu unused. The elastic lambda, mu of
+    the particle are its ElasticCoefficients. Usable wherever a DruckerPrager is (`ParticleSet.uniform(plasticity=Snow())`).
+    Preconditions (checked here, documented in the header): 0 <= theta_c < 1, theta_s >= 0, xi and max_exponent finite."""
+    theta_c: float = 2.5e-2
+    theta_s: float = 7.5e-3
+    xi: float = 10.0
+    max_exponent: float = 5.0
+
+    def __post_init__(self):
+        if not (math.isfinite(self.theta_c) and 0.0 <= self.theta_c < 1.0):
+            raise ValueError("Snow: 0 <= theta_c < 1")
+        if not (math.isfinite(self.theta_s) and self.theta_s >= 0.0):
+            raise ValueError("Snow: theta_s >= 0 and finite")
+        if not (math.isfinite(self.xi) and math.isfinite(self.max_exponent)):
+            raise ValueError("Snow: xi and max_exponent finite")
+        # (the kernel reads the fp32 values: theta_c must still be below 1 there)
+        if not float(F32(self.theta_c)) < 1.0:
+            raise ValueError("Snow: theta_c rounds to 1 in fp32")
+
+    # the slots under their DruckerPrager names: whatever packs a DruckerPrager packs a Snow
+    h0 = property(lambda self: float(self.theta_c))
+    h1 = property(lambda self: float(self.theta_s))
+    h2 = property(lambda self: float(self.xi))
+    h3 = property(lambda self: float(self.max_exponent))
+    lambda_ = property(lambda self: 1.0)
+    mu = property(lambda self: 0.0)
+
+    def as_array(self):
+        return np.array([self.theta_c, self.theta_s, self.xi, self.max_exponent, 1.0, 0.0], dtype=F32)
+
+
 # src/models/drucker_prager.rs:44-53
 DRUCKER_PRAGER_DEFAULT_STATE = np.array([1.0, 1.0, 0.0], dtype=F32)
 

@@ -449,15 +449,28 @@ class MpmData(DataHandle):
     @classmethod
     def from_scene(cls, pipeline, scene, **overrides):
         """The data one of the dicts `wgsparkl_amd.scenes` returns describes (the key table in that module's docstring): `new` with
-        its "model", then its "fluid_gamma", "models" and "walls" through their setters, in that order, each only where the scene
-        has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
-        `particles=snap`); `None` for one of the three optional keys builds the scene without it (`models=None`: no table)."""
+        its "model", then its "plasticity", "fluid_gamma", "models" and "walls" through their setters, in that order, each only where
+        the scene has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
+        `particles=snap`); `None` for one of the optional keys builds the scene without it (`models=None`: no table)."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
         data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
-        for key, apply in (("fluid_gamma", data.set_fluid_eos), ("models", data.set_particle_models), ("walls", data.set_domain_walls)):
+        for key, apply in (("plasticity", data.set_plasticity_model), ("fluid_gamma", data.set_fluid_eos),
+                           ("models", data.set_particle_models), ("walls", data.set_domain_walls)):
             if sc.get(key) is not None:
                 apply(sc[key])
         return data
+
+    def set_plasticity_model(self, kind: int):
+        """`wgs_set_plasticity_model`: `models.PLASTICITY_DRUCKER_PRAGER` (default) or `models.PLASTICITY_SNOW` — the singular-value
+        clamp with hardening on the corotated stress; the plasticity slots of a particle are then those of `models.Snow`.
+        Stream-ordered; no device memory. MODEL_COROTATED data only."""
+        _ffi.check(self.lib, self.lib.wgs_set_plasticity_model(self._h, int(kind)))
+
+    def plasticity_model(self) -> int:
+        """`wgs_get_plasticity_model`: the PLASTICITY_* value in force."""
+        kind = C.c_int32(0)
+        _ffi.check(self.lib, self.lib.wgs_get_plasticity_model(self._h, C.byref(kind)))
+        return int(kind.value)
 
     def set_domain_walls(self, walls):
         """`wgs_set_domain_walls`: 2 * dim faces, `walls[2 * k]` the low face of axis k and `walls[2 * k + 1]` its high face, each a

@@ -12,6 +12,7 @@ The scene contract. Every builder returns a dict, and `MpmData.from_scene` (a wh
 |---|---|---|
 | `particles`, `params`, `colliders`, `cell_width`, `grid_capacity` | required | the arguments of `MpmData.new` / `NativeShard` |
 | `model` | optional | the data's single constitutive model; default `MODEL_COROTATED` |
+| `plasticity` | optional | the plasticity rule, `PLASTICITY_DRUCKER_PRAGER` / `PLASTICITY_SNOW`: `MpmData.set_plasticity_model`; an error on a slab |
 | `fluid_gamma` | optional | the Tait exponent of `MODEL_FLUID`: `set_fluid_eos` |
 | `models` | optional | the per-particle table (np.uint8): `MpmData.set_particle_models`; an error on a slab |
 | `walls` | optional | the 2 * dim domain walls: `MpmData.set_domain_walls`; an error on a slab |
@@ -26,8 +27,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, WALL_SLIP, DruckerPrager,
-                     ElasticCoefficients, FluidCoefficients, ParticlePhase, Wall)
+from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, PLASTICITY_DRUCKER_PRAGER, PLASTICITY_SNOW, WALL_SLIP, WALL_STICKY,
+                     DruckerPrager, ElasticCoefficients, FluidCoefficients, ParticlePhase, Snow, Wall)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -414,6 +415,31 @@ def walled_box(dim=3, n=6000, lo=2, hi=18, wall_type=WALL_SLIP, friction=0.0, ce
     ps.vel[:] = (direction * rng.uniform(0.5, 1.0, size=(n, 1)) * (speed * h / params.dt)).astype(F32)
     walls = [Wall(int(wall_type), float(friction), int(lo if f % 2 == 0 else hi)) for f in range(2 * dim)] if with_walls else None
     return dict(particles=ps, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED, walls=walls)
+
+
+def snowball(dim=3, radius=6.0, cell_width=1.0, speed=0.01, gap=0.5, snow=None, young_modulus=1.4e5, poisson=0.2, density=400.0,
+             jitter=0.05, plasticity=PLASTICITY_SNOW):
+    """A ball of snow thrown at a sticky domain wall (scene keys "plasticity" and "walls"): particles at spacing h/2 inside a ball of
+    `radius` cells, moving along -x at `speed` times the grid's cap h / dt (the default: 10 m/s, half the material's speed of sound) towards the sticky
+    low x face `gap` cells in front of it;
+    no colliders, gravity along -y. The material is that of Stomakhin et al. 2013 (E = 1.4e5, nu = 0.2, rho = 400) under
+    `models.Snow()` (or `snow`): the ball flattens against the wall, hardens where it is compressed and breaks up where it is
+    stretched. `plasticity=PLASTICITY_DRUCKER_PRAGER` gives the same particles as Drucker-Prager sand of the same stiffness (the
+    timing twin of notes/round_31.md)."""
+    h = float(cell_width)
+    n_side = int(np.ceil(4.0 * radius)) + 1
+    origin = tuple([4.0 * h + gap * h] + [4.0 * h] * (dim - 1))
+    pos = lattice((n_side,) * dim, origin, h, jitter)
+    centre = np.asarray(origin, np.float64) + 0.25 * n_side * h
+    pos = pos[np.linalg.norm(pos.astype(np.float64) - centre, axis=1) <= radius * h]
+    rule = (snow or Snow()) if plasticity == PLASTICITY_SNOW else DruckerPrager.new(young_modulus, poisson)
+    ps = ParticleSet.uniform(pos, h / 4.0, density, ElasticCoefficients.from_young_modulus(young_modulus, poisson), plasticity=rule, phase=None)
+    params = SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0e-3)
+    ps.vel[:, 0] = F32(-speed * h / params.dt)
+    walls = [Wall.low(4.0 * h, h, WALL_STICKY), None] + [None] * (2 * dim - 2)
+    return dict(particles=ps, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED,
+                plasticity=int(plasticity), walls=walls,
+                name=f"snowball {dim}D: {ps.n} particles, radius {radius} cells, thrown at a sticky wall at {speed} h/dt")
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):
