@@ -290,7 +290,7 @@ pub const WGS_WALL_STICKY: u32 = 1;
 pub const WGS_WALL_SLIP: u32 = 2;
 pub const WGS_WALL_SEPARATE: u32 = 3;
 
-/// The plasticity rule of a `wgs_data` (include/wgsparkl_hip_plasticity.h): `wgs_set_plasticity_model`
+/// The plasticity rule of a `wgs_data` (include/wgsparkl_hip.h "Snow plasticity"): `wgs_set_plasticity_model`
 pub const WGS_PLASTICITY_DRUCKER_PRAGER: i32 = 0;
 pub const WGS_PLASTICITY_SNOW: i32 = 1;
 
@@ -364,6 +364,11 @@ extern "C" {
     /// device memory. Detect by symbol lookup on older libraries.
     pub fn wgs_set_domain_walls(d: *mut wgs_data, walls: *const wgs_wall) -> wgs_status;
     pub fn wgs_get_domain_walls(d: *mut wgs_data, out: *mut wgs_wall) -> wgs_status;
+    /// the plasticity rule, one per data: `WGS_PLASTICITY_DRUCKER_PRAGER` (default) or `WGS_PLASTICITY_SNOW` (singular-value clamp with
+    /// hardening on the corotated stress; the six `wgs_drucker_prager` slots then read theta_c, theta_s, xi, exponent cap, switch, -).
+    /// Stream-ordered, single-domain data. Detect by symbol lookup on older libraries.
+    pub fn wgs_set_plasticity_model(d: *mut wgs_data, kind: i32) -> wgs_status;
+    pub fn wgs_get_plasticity_model(d: *mut wgs_data, out: *mut i32) -> wgs_status;
     pub fn wgs_set_uniform_material(d: *mut wgs_data, mass: f32, init_volume: f32, lambda: f32, mu: f32) -> wgs_status;
     /// reproducible sums, bounds and state digest, reduced on the device; blocking / stream-ordered into DEVICE memory
     pub fn wgs_read_diagnostics(d: *mut wgs_data, what: u32, out: *mut wgs_diagnostics) -> wgs_status;
@@ -404,13 +409,4 @@ extern "C" {
     pub fn wgs_sharded_step(p: *mut wgs_pipeline, d: *mut wgs_data, num_substeps: u32) -> wgs_status;
     pub fn wgs_sharded_step_lockstep(p: *mut wgs_pipeline, slabs: *mut *mut wgs_data, num_slabs: u32, num_substeps: u32) -> wgs_status;
     pub fn wgs_shard_export(d: *mut wgs_data, device_buf: *mut c_void, capacity_records: u32, count: *mut u32) -> wgs_status;
-}
-
-/// include/wgsparkl_hip_plasticity.h, the plasticity extension the main header includes (a block of its own, like the header)
-extern "C" {
-    /// the plasticity rule, one per data: `WGS_PLASTICITY_DRUCKER_PRAGER` (default) or `WGS_PLASTICITY_SNOW` (singular-value clamp with
-    /// hardening on the corotated stress; the six `wgs_drucker_prager` slots then read theta_c, theta_s, xi, exponent cap, switch, -).
-    /// Stream-ordered, single-domain data. Detect by symbol lookup on older libraries.
-    pub fn wgs_set_plasticity_model(d: *mut wgs_data, kind: i32) -> wgs_status;
-    pub fn wgs_get_plasticity_model(d: *mut wgs_data, out: *mut i32) -> wgs_status;
 }

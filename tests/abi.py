@@ -68,7 +68,7 @@ def layout(dim):
         src, exe = os.path.join(tmp, "abi.c"), os.path.join(tmp, "abi")
         with open(src, "w") as f:
             f.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c11", f"-DWGS_DIM={dim}", f"-I{INCLUDE}", src, "-o", exe], check=True)
+        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-DWGS_DIM={dim}", f"-I{INCLUDE}", src, "-o", exe], check=True)
         out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     lay = Layout({}, {s: {} for s in h.structs}, {})
     for kind, name, field, a, b in (l.split() for l in out.splitlines()):

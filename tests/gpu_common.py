@@ -13,9 +13,10 @@ import body_truth as BT
 import cdf_truth as CT
 import cpic_truth as CP
 import mesh_truth as MT
+import plastic_truth as PT
 import transfer_truth as T
-from helpers import (assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, pipeline, rel_rms, report_margin, run_gpu,
-                     run_oracle)
+from helpers import (assert_close_to_truth, compare_cpic, compare_grids, grid_of, max_abs, new_data, pipeline, rel_rms, report_margin,
+                     run_gpu, run_oracle)
 
 GRID_V_TOL = 1e-5      # relative RMS of grid velocity vs the fp64 oracle (north_star target)
 PART_TOL = 2e-5        # relative RMS of particle x, v, F, C' vs the fp64 oracle
@@ -184,6 +185,96 @@ def checked_body_substep(tag, sc, data, fails, first, part_cap=CT.PART_CAP, extr
     # a condition on the inputs, whatever the scene: every node that gives a body below the caps an impulse is visible in its velocity
     BT.assert_sensitive(tag, bodies)
     return CheckedBodies(ck, imp, bodies, before, after)
+
+
+UNTOUCHED = ("lambda_", "mu", "dp", "init_volume")     # what a plastic substep leaves bit for bit
+
+
+def _start(sc, **kw):
+    """data of a scene with the plastic state of its particles (creation takes none: set_plastic_state); `kw` as in new_data"""
+    pipe, data = new_data(sc, **kw)
+    data.set_plastic_state(kw.get("particles", sc["particles"]).dp_state)
+    return pipe, data
+
+
+def _step(pipe, data, k=1):
+    pipe.step(data, k)
+    data.sync()
+    return data.read_particles()
+
+
+def plastic_twin(sc, particles=None):
+    """one substep of the scene (or of a read-back state of it) stripped of plasticity (plastic_truth.strip), whatever its rule"""
+    return _step(*_start(PT.strip(sc, particles=particles), plasticity=None))
+
+
+class CheckedPlastic(NamedTuple):
+    """what checked_plastic_substep returns"""
+    end_to_end: object             # the particle truth of the trial state (transfer_truth.Particles), end to end
+    isolated: object               # ... from the kernel's own grid
+    keep: object                   # the particles the collider leaves to the particle checks (None without colliders: all)
+
+
+def checked_plastic_substep(tag, sc, before, got, twin, grid, poses, model, fails, extra_levels=0.0):
+    """What one substep of plastic particles is held to before its plasticity rule is looked at, from the state `before` (a ParticleSet
+    with its dp_state and phase) to `got`, with `twin` the stripped run's result, `grid` the read_grid() after the substep and
+    `poses` the bodies read before it (None without colliders; with them the trial state is cpic_truth's, from the kernel's own
+    decisions, as in checked_cpic_substep): UNTOUCHED bit for bit, the twin's x and v the plastic run's, every node, the twin's
+    particles from the kernel's own grid, and the shares near the clamp and the speed cap under plastic_truth.NEAR_MAX."""
+    d, h, prm, n = before.dim, sc["cell_width"], sc["params"], before.n
+    inp = T.Inputs.of(before)
+    cells, vm = grid[:2]
+    for k in UNTOUCHED:
+        assert np.array_equal(getattr(got, k), getattr(before, k)), f"{tag}: {k} changed"
+    assert np.array_equal(twin.pos, got.pos) and np.array_equal(twin.vel, got.vel), f"{tag}: the elastic twin's x or v differ from the plastic run's"
+    if sc["colliders"]:
+        f = CP.Fields(got.cdf_affinity, got.cdf_normal.astype(np.float64), got.cdf_dist.astype(np.float64), cells, grid[3], grid[4])
+        mo = CP.Motion.of(sc["colliders"], d, poses)
+        e2e = CP.substep(inp, h, prm.dt, prm.gravity, f, mo, extra_levels=extra_levels)
+        near_n, nn = T.check_grid(f"{tag} grid", e2e.grid, cells, vm, fails, extra_levels=extra_levels)
+        pt = e2e.particles
+        iso = CP.substep(inp, h, prm.dt, prm.gravity, f, mo, own_grid=(cells, vm[:, :d])).particles
+        keep = ~e2e.contact.near_pen
+        near_p = int((pt.near_cap | e2e.contact.near).sum())
+        assert (got.cdf_affinity != 0).sum() > 0.02 * n, f"{tag}: the collider is not felt by the cloud"
+    else:
+        st, gr, pt = T.substep(inp, h, prm.dt, prm.gravity, extra_levels=extra_levels)
+        near_n, nn = T.check_grid(f"{tag} grid", gr, cells, vm, fails, extra_levels=extra_levels)
+        iso = T.isolated(inp, st, cells, vm[:, :d], prm.dt)
+        keep = None
+        near_p = int(pt.near_cap.sum())
+    # the elastic twin: its def_grad is the kernel's own F_trial
+    T.check_particles(f"{tag} twin isolated G2P", iso, twin, model, fails, sel=keep)
+    report_margin(f"{tag}: nodes near the clamp (fraction)", near_n / max(nn, 1), PT.NEAR_MAX, count=near_n)
+    report_margin(f"{tag}: particles near the speed cap (fraction)", near_p / n, PT.NEAR_MAX, count=near_p)
+    assert near_n <= PT.NEAR_MAX * nn and near_p <= PT.NEAR_MAX * n
+    return CheckedPlastic(pt, iso, keep)
+
+
+class SteadyPlastic(NamedTuple):
+    """what steady_plastic_substep returns"""
+    before: object                 # read_particles() after the warm-up
+    got: object                    # ... and after the checked substep
+    twin: object                   # the checked substep of new data made of `before` without plasticity
+    grid: tuple                    # read_grid() after the checked substep
+    stats0: dict                   # stats() before the checked substep
+    stats1: dict                   # ... and after it
+
+
+def steady_plastic_substep(sc, warmup):
+    """`warmup` substeps, read back (plastic state and phase included), then one more: a steady-state substep, which rebuilds no table
+    and in which some particle changes its cell. The twin is new data made of the read-back state without plasticity (a restart
+    continues bit for bit)."""
+    pipe, data = _start(sc)
+    before = _step(pipe, data, warmup)
+    s0 = data.stats()
+    got = _step(pipe, data)
+    s1 = data.stats()
+    grid = data.read_grid()
+    twin = plastic_twin(sc, particles=before)
+    assert s1["table_rebuilds"] == s0["table_rebuilds"], "the checked substep rebuilt the table: not a steady-state substep"
+    assert s1["cell_changers"] > s0["cell_changers"], "no particle changed cell in the checked substep"
+    return SteadyPlastic(before, got, twin, grid, s0, s1)
 
 
 def blocks_in_reach(nf, col, d):

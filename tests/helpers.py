@@ -10,7 +10,7 @@ import re
 import numpy as np
 
 from oracle.orc import Oracle
-from wgsparkl_amd import MpmData, MpmPipeline
+from wgsparkl_amd import MpmData, MpmPipeline, _ffi
 from wgsparkl_amd.selfcheck import rel_rms
 
 _ORACLES = {}
@@ -121,6 +121,11 @@ def restored_colliders(colliders, bodies, dim):
         return dataclasses.replace(c, translation=tuple(b["translation"]), rotation=rot, linvel=tuple(b["linvel"]) + (0.0,) * (3 - dim),
                                    angvel=tuple(b["angvel"]), com=tuple(b["com"]))
     return [restored(c, b) for c, b in zip(colliders, bodies)]
+
+
+def _digest(data):
+    """the state digest of `data` (wgs_read_diagnostics, WGS_DIAG_DIGEST)"""
+    return data.diagnostics(_ffi.DIAG_DIGEST).digest
 
 
 def max_abs(a, b):

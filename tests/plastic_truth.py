@@ -22,7 +22,8 @@ The stress keeps transfer_truth's rule: C' from tau in fp64 of the F the kernel 
 corotated particle the stress of the projected F.
 
 `scene` builds the moving plastic scenes both test files run (`CASES`); `Plastic` is the truth, `judge` the per-particle
-verdict on a result (a kernel's, or the C oracle's)."""
+verdict on a result (a kernel's, or the C oracle's). The fracture decision (`Fracture`) and what a judge asks of the particles that
+were not projected (`gate`) do not depend on the plasticity rule: tests/snow_truth.py uses the same two."""
 from typing import NamedTuple
 
 import numpy as np
@@ -184,19 +185,17 @@ def strip(sc, particles=None):
 
 
 # ------------------------------------------------------------------------------------------------ the truth
-class Plastic:
-    """fp64 fracture and Drucker-Prager decisions and outcomes on a trial deformation gradient.
+class Fracture:
+    """The fp64 fracture decision on a trial deformation gradient, whatever plasticity rule follows it.
 
-    F [n, d, d] float64 (transfer_truth's pt.F, or an exact fp32 matrix), f_err [n] its normwise bound (None: exact);
-    dp [n, 6], state [n, 3], phase [n, 2]: the fp32 inputs of the substep."""
+    F [n, d, d] float64, f_err [n] its normwise bound (None: exact), phase [n, 2] the fp32 input of the substep. breakable: phase > 0
+    and max_stretch > 0; broken: s_max > max_stretch; inside the band `amb_frac` either decision is a legitimate one."""
 
-    def __init__(self, F, f_err, dp, state, phase):
+    def __init__(self, F, f_err, phase):
         F = np.asarray(F, np.float64)
         self.n, self.d = F.shape[0], F.shape[1]
-        self.F = F
         self.f_err = np.zeros(self.n) if f_err is None else np.asarray(f_err, np.float64)
-        self.dp32, self.state32, self.phase32 = (np.asarray(a, np.float32) for a in (dp, state, phase))
-        self.dp, self.state, ph = (a.astype(np.float64) for a in (self.dp32, self.state32, self.phase32))
+        ph = np.asarray(phase, np.float32).astype(np.float64)
         self.svd = DM.svd_lapack(T.unmat(F))
         s = self.svd[1]
         _, smax, _ = DM.sv_stats(s)
@@ -206,6 +205,22 @@ class Plastic:
         self.broken = self.breakable & (self.s_max > self.max_stretch)
         self.amb_frac = self.breakable & (np.abs(self.s_max - self.max_stretch) <= DM.C_DEC * U32 * smax + self.f_err)
         self.phase64 = np.where(self.broken, 0.0, self.phase_in)
+
+
+class Plastic:
+    """fp64 fracture and Drucker-Prager decisions and outcomes on a trial deformation gradient.
+
+    F [n, d, d] float64 (transfer_truth's pt.F, or an exact fp32 matrix), f_err [n] its normwise bound (None: exact);
+    dp [n, 6], state [n, 3], phase [n, 2]: the fp32 inputs of the substep."""
+
+    def __init__(self, F, f_err, dp, state, phase):
+        F = np.asarray(F, np.float64)
+        self.F = F
+        self.fr = fr = Fracture(F, f_err, phase)
+        for k in ("n", "d", "f_err", "svd", "s_max", "phase_in", "max_stretch", "breakable", "broken", "amb_frac", "phase64"):
+            setattr(self, k, getattr(fr, k))
+        self.dp32, self.state32 = np.asarray(dp, np.float32), np.asarray(state, np.float32)
+        self.dp, self.state = self.dp32.astype(np.float64), self.state32.astype(np.float64)
         self.has_dp = self.dp[:, 4] != 0.0
         self.cand64 = (self.phase64 == 0.0) & self.has_dp
         self.res = DM.dp_outcomes64(self.dp, self.state, F, self.svd, f_err)
@@ -238,23 +253,22 @@ def _get(got):
     return (lambda k: got[k]) if isinstance(got, dict) else (lambda k: getattr(got, k))
 
 
-def judge(tag, pl: Plastic, got, fails, F_trial32=None, exact=False, fam=None):
-    """Every particle's phase, def_grad and dp_state of a run against the truth `pl`.
-    - phase[:, 1] is bit-unchanged; phase[:, 0] is the fp64 decision outside the fracture band, inside it the old value or 0;
-    - a particle the run did not attempt to project (its phase != 0 or dp[4] == 0) keeps its state bit for bit;
-    - one it did is matched against the allowed branches (devmath_truth.dp_match). "Projected" is read off the state (it moved),
-      and with `F_trial32` (the twin's def_grad: the run's own F_trial) also off F: an unprojected particle then holds exactly
-      F_trial32, which is asserted;
-    - `exact` (an fp64 run against the fp64 truth): the fp64 decisions themselves, no band, and every error within
-      C u64 of the scales instead of C u32.
-    F of the particles that were not projected is the caller's (transfer_truth.check_particles with own_F = changed)."""
+class Gate(NamedTuple):
+    cand: np.ndarray        # [n] the judged run's own gate: its phase == 0 and the particle's switch on
+    changed: np.ndarray     # [n] the plastic state moved or (with F_trial32) F is not the twin's
+    bad: np.ndarray         # [n] any complaint so far; `complain` goes on marking it
+    complain: object        # complain(mask, what): marks `bad` and appends one line to `fails`
+
+
+def gate(tag, fr: Fracture, has, state32, got, fails, F_trial32=None, exact=False, name=None):
+    """What every plasticity rule's judge asks first of a run (ParticleSet or dict), with `has` the particles' switch (dp[4] != 0) and
+    `state32` their plastic state before the substep:
+    - phase[:, 1] is bit-unchanged; phase[:, 0] is the fp64 decision of `fr` outside its band, inside it the old value or 0 (`exact`: no band);
+    - a particle the run did not send through the projection (its phase != 0 or the switch off) keeps its state bit for bit and, with
+      `F_trial32` (the twin's def_grad: the run's own F_trial), holds exactly that matrix."""
     g = _get(got)
-    n, d = pl.n, pl.d
-    F32 = np.asarray(g("def_grad"))
-    F_out = T.mat(np.asarray(F32, np.float64), d)
-    st_out = np.asarray(g("dp_state"))
-    ph = np.asarray(g("phase"), np.float64)
-    name = (lambda i: f"#{i}" + (f" ({fam[i]})" if fam is not None else ""))
+    n = fr.n
+    name = name or (lambda i: f"#{i}")
     bad = np.zeros(n, bool)
 
     def complain(mask, what):
@@ -262,19 +276,38 @@ def judge(tag, pl: Plastic, got, fails, F_trial32=None, exact=False, fam=None):
             bad[mask] = True
             fails.append(f"{tag}: {what}: {int(mask.sum())} particles (first {name(int(np.argmax(mask)))})")
 
-    complain(ph[:, 1] != pl.max_stretch, "max_stretch changed")
+    ph = np.asarray(g("phase"), np.float64)
+    complain(ph[:, 1] != fr.max_stretch, "max_stretch changed")
     phase = ph[:, 0]
-    legit = (phase == pl.phase_in) | (pl.breakable & (phase == 0.0))
-    band = np.zeros(n, bool) if exact else pl.amb_frac
-    complain(~legit | ((phase != pl.phase64) & ~band), "phase is not the fp64 fracture decision on F_trial")
-    cand = (phase == 0.0) & pl.has_dp
-    st_moved = ~np.all(st_out.astype(np.float64) == pl.state, axis=1)
+    legit = (phase == fr.phase_in) | (fr.breakable & (phase == 0.0))
+    band = np.zeros(n, bool) if exact else fr.amb_frac
+    complain(~legit | ((phase != fr.phase64) & ~band), "phase is not the fp64 fracture decision on F_trial")
+    cand = (phase == 0.0) & has
+    st_moved = ~np.all(np.asarray(g("dp_state")) == state32, axis=1)
     changed = st_moved.copy()
     if F_trial32 is not None:
-        changed |= ~np.all(F32 == np.asarray(F_trial32), axis=1)
+        changed |= ~np.all(np.asarray(g("def_grad")) == np.asarray(F_trial32), axis=1)
     complain(~cand & st_moved, "plastic state changed without a projection")
     if F_trial32 is not None:
         complain(~cand & changed, "F is not the elastic twin's F_trial although no projection was attempted")
+    return Gate(cand, changed, bad, complain)
+
+
+def judge(tag, pl: Plastic, got, fails, F_trial32=None, exact=False, fam=None):
+    """Every particle's phase, def_grad and dp_state of a run against the truth `pl`.
+    - phase, and the state and F of a particle the run did not attempt to project: `gate`;
+    - one it did attempt is matched against the allowed branches (devmath_truth.dp_match). "Projected" is read off the state (it moved),
+      and with `F_trial32` (the twin's def_grad: the run's own F_trial) also off F: an unprojected particle then holds exactly
+      F_trial32, which is asserted;
+    - `exact` (an fp64 run against the fp64 truth): the fp64 decisions themselves, no band, and every error within
+      C u64 of the scales instead of C u32.
+    F of the particles that were not projected is the caller's (transfer_truth.check_particles with own_F = changed)."""
+    g = _get(got)
+    n, d = pl.n, pl.d
+    F_out = T.mat(np.asarray(g("def_grad"), np.float64), d)
+    st_out = np.asarray(g("dp_state"))
+    name = (lambda i: f"#{i}" + (f" ({fam[i]})" if fam is not None else ""))
+    cand, changed, bad, _ = gate(tag, pl.fr, pl.has_dp, pl.state32, got, fails, F_trial32, exact, name)
     branch = np.full(n, "-", dtype="<U1")
     ratio = np.zeros(n)
     lines = []

@@ -1,4 +1,4 @@
-"""fp64 truth of the SNOW plastic update (include/wgsparkl_hip_plasticity.h; wgsparkl_amd/csrc/device_math.h snow_project,
+"""fp64 truth of the SNOW plastic update (include/wgsparkl_hip.h; wgsparkl_amd/csrc/device_math.h snow_project,
 the MODEL 4 instantiations of g2p_body.inc), inside one substep. Shared by tests/test_snow_truth.py (CPU: the truth's own
 properties, deliberate mistakes against the judge, the scenes' conditions) and tests/test_gpu_snow.py (the HIP kernels per particle).
 
@@ -7,8 +7,7 @@ It composes the truths the suite already trusts and restates none of them:
   bounds, as for plastic_truth. The primary check is plastic_truth's isolated one: the scene stripped of plasticity
   (plastic_truth.strip) leaves the kernel's own fp32 F_trial in the twin's def_grad bit for bit, and the truth is taken of that
   exact matrix;
-- the fracture decision: plastic_truth.Plastic on that matrix — breakable, broken, its band `amb_frac` and its caps, unchanged. (Its
-  Drucker-Prager outcomes are computed on stand-in parameters and never read.)
+- the fracture decision: plastic_truth.Fracture on that matrix — breakable, broken, its band `amb_frac` and its caps, unchanged;
 - the SVD and the stress: devmath_truth.svd_lapack (U, V proper, the sign on the smallest value) and tau_corotated64.
 
 The rule itself, in fp64, for a particle that passes the gate (phase == 0 after the fracture test, dp[4] != 0), with
@@ -104,15 +103,12 @@ class Snow:
     dp [n, 6], state [n, 3], phase [n, 2] of the substep."""
 
     def __init__(self, F, dp, state, phase):
-        from wgsparkl_amd.models import DruckerPrager
         F = np.asarray(F, np.float64)
         self.n, self.d = n, d = F.shape[0], F.shape[1]
         self.F = F
-        self.dp32, self.state32, self.phase32 = (np.asarray(a, np.float32) for a in (dp, state, phase))
+        self.dp32, self.state32 = np.asarray(dp, np.float32), np.asarray(state, np.float32)
         self.dp, self.state = self.dp32.astype(np.float64), self.state32.astype(np.float64)
-        standin = np.tile(DruckerPrager.new(1e6, 0.25).as_array(), (n, 1))
-        standin[:, 4] = self.dp32[:, 4]
-        self.fr = fr = PT.Plastic(F, None, standin, np.tile(np.array([1.0, 1.0, 0.0], np.float32), (n, 1)), phase)   # fracture only
+        self.fr = fr = PT.Fracture(F, None, phase)
         self.has = self.dp[:, 4] != 0.0
         self.cand64 = (fr.phase64 == 0.0) & self.has
         self.F_E, self.jp, self.sh, self.svd = project64(F, self.dp, self.state[:, 0], fr.svd)
@@ -154,33 +150,14 @@ class Judged(NamedTuple):
 
 def judge(tag, sn: Snow, got, fails, F_trial32=None):
     """Every particle's phase, def_grad and dp_state of a run (ParticleSet or dict) against the truth.
-    - phase[:, 1] is bit-unchanged; phase[:, 0] is the fp64 fracture decision outside plastic_truth's band, inside it either;
-    - a particle that did not pass the gate keeps its plastic state bit for bit and (with `F_trial32`, the twin's def_grad) holds
-      exactly that matrix;
+    - phase, and the state and F of a particle that did not pass the gate: plastic_truth.gate;
     - one that did: state words 1 and 2 bit for bit, Jp', s^ (the singular values of the stored F), |det F_E| and — unless its
       direction is arbitrary — F_E, each within its bound."""
-    g = (lambda k: got[k]) if isinstance(got, dict) else (lambda k: getattr(got, k))
-    n, d = sn.n, sn.d
-    F32 = np.asarray(g("def_grad"))
-    F_out = T.mat(F32.astype(np.float64), d)
+    g = PT._get(got)
+    d = sn.d
+    F_out = T.mat(np.asarray(g("def_grad"), np.float64), d)
     st = np.asarray(g("dp_state"))
-    ph = np.asarray(g("phase"), np.float64)
-    bad = np.zeros(n, bool)
-
-    def complain(mask, what):
-        if mask.any():
-            bad[mask] = True
-            fails.append(f"{tag}: {what}: {int(mask.sum())} particles (first #{int(np.argmax(mask))})")
-
-    fr = sn.fr
-    complain(ph[:, 1] != fr.max_stretch, "max_stretch changed")
-    phase = ph[:, 0]
-    legit = (phase == fr.phase_in) | (fr.breakable & (phase == 0.0))
-    complain(~legit | ((phase != fr.phase64) & ~fr.amb_frac), "phase is not the fp64 fracture decision on F_trial")
-    cand = (phase == 0.0) & sn.has
-    complain(~cand & ~np.all(st == sn.state32, axis=1), "plastic state changed without passing the gate")
-    if F_trial32 is not None:
-        complain(~cand & ~np.all(F32 == np.asarray(F_trial32), axis=1), "F is not the elastic twin's F_trial although the gate was not passed")
+    cand, _, bad, complain = PT.gate(tag, sn.fr, sn.has, sn.state32, got, fails, F_trial32)
     complain(cand & ~np.all(st[:, 1:] == sn.state32[:, 1:], axis=1), "state word 1 or 2 (plastic_hardening, log_vol_gain) touched")
     ratio = {}
 
@@ -229,7 +206,7 @@ def check_particles(tag, pt, got, jd: Judged, fails, sel=None):
     T.check_particles(tag, ph, got, 0, fails, sel=_without(sel, jd.cand))
     m = jd.cand if sel is None else jd.cand & np.asarray(sel, bool)
     if m.any():
-        g = (lambda k: got[k]) if isinstance(got, dict) else (lambda k: getattr(got, k))
+        g = PT._get(got)
         # (x and v of the gate's particles: transfer_truth.check_particles' own two lines, its C' with the term above)
         T.check(f"{tag}: x of the snow particles", np.linalg.norm(np.asarray(g("pos"), np.float64) - pt.x, axis=1), pt.b_x, fails, m)
         T.check(f"{tag}: v of the snow particles", np.linalg.norm(np.asarray(g("vel"), np.float64) - pt.vel, axis=1), pt.b_vel, fails, m)

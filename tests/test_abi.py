@@ -48,6 +48,7 @@ PY_CONSTANTS = [
     *((getattr(_ffi, "DIAG_" + k), "WGS_DIAG_" + k) for k in ("PARTICLES", "ENERGY", "GRID", "DIGEST")),
     *((getattr(m, "WALL_" + k), "WGS_WALL_" + k) for m in (_ffi, models) for k in ("NONE", "STICKY", "SLIP", "SEPARATE")),
     *((getattr(models, "MODEL_" + k), "WGS_MODEL_" + k) for k in ("COROTATED", "NEO_HOOKEAN", "FLUID", "PER_PARTICLE")),
+    *((getattr(models, "PLASTICITY_" + k), "WGS_PLASTICITY_" + k) for k in ("DRUCKER_PRAGER", "SNOW")),
     *((getattr(solver, "SHAPE_" + k), "WGS_SHAPE_" + k) for k in ("BALL", "CUBOID", "CAPSULE", "MESH")),
 ]
 RUST_OPAQUE = {"wgs_pipeline", "wgs_data", "wgs_comm"}           # handles: never a layout
@@ -145,7 +146,7 @@ def cpp_problems(hdr, hpp):
 
 # ------------------------------------------------------------------------------------------------ the header itself
 def test_the_table_is_the_whole_header():
-    assert (len(HDR.structs), sum(map(len, HDR.structs.values())), len(HDR.constants), len(HDR.functions)) == (23, 112, 57, 56)
+    assert (len(HDR.structs), sum(map(len, HDR.structs.values())), len(HDR.constants), len(HDR.functions)) == (23, 112, 59, 58)
     assert set(CTYPES_TWIN) == set(HDR.structs), "the twin map names every struct, and nothing else"
     for dim in DIMS:
         lay = abi.layout(dim)
@@ -169,9 +170,10 @@ def test_abi_version_is_seven_and_the_header_says_how_to_detect_what_came_since(
     assert {abi.layout(dim).const["WGS_ABI_VERSION"] for dim in DIMS} == {_ffi.ABI_VERSION} and _ffi.ABI_VERSION == 7
     text = " ".join(abi.read(abi.HEADER_PATH).replace("\n *", " ").split())
     history = text[text.index("History: 5 ="):text.index("#define WGS_ABI_VERSION")]
-    for symbol in ("wgs_set_fluid_eos", "wgs_set_particle_models", "wgs_sample_grid", "wgs_read_particle_fields", "wgs_set_domain_walls"):
+    for symbol in ("wgs_set_fluid_eos", "wgs_set_particle_models", "wgs_sample_grid", "wgs_read_particle_fields", "wgs_set_domain_walls",
+                   "wgs_set_plasticity_model"):
         assert re.search(rf"detects? {symbol} by symbol lookup", history), symbol
-    assert history.count("Still 7:") == 5
+    assert history.count("Still 7:") == 6
 
 
 # ------------------------------------------------------------------------------------------------ ctypes
@@ -209,7 +211,7 @@ def test_python_constants_are_the_headers():
         for value, name in PY_CONSTANTS:
             assert value == const[name], name
     mirrored = {name for _, name in PY_CONSTANTS}
-    for family in ("WGS_ERR_", "WGS_SUM_", "WGS_DIAG_", "WGS_WALL_", "WGS_MODEL_", "WGS_SHAPE_"):
+    for family in ("WGS_ERR_", "WGS_SUM_", "WGS_DIAG_", "WGS_WALL_", "WGS_MODEL_", "WGS_PLASTICITY_", "WGS_SHAPE_"):
         assert {c for c in HDR.constants if c.startswith(family)} <= mirrored, family
     assert _ffi.DIAG_ALL == sum(v for c, v in abi.layout(3).const.items() if c.startswith("WGS_DIAG_"))
 
@@ -309,3 +311,12 @@ def test_a_struct_a_constant_and_a_function_without_mirrors_are_named_by_every_c
     assert rust_constant_problems(grown, lay, rust) == ["WGS_NEW_LIMIT: not declared in lib.rs"]
     assert rust_function_problems(grown, abi.rust_functions(RUST)) == ["wgs_new_call: not in the extern block"]
     assert cpp_problems(grown, HPP) == ["wgs_new_call: neither wrapped by wgsparkl_hip.hpp nor listed"]
+    # ... and the newest entry point of the real header, taken out of a copy of each mirror, is named by that mirror's check
+    gone = "wgs_get_plasticity_model"
+    protos = {n: p for n, p in _ffi.prototypes(_ffi.make_types(3)).items() if n != gone}
+    bad = ctypes_prototype_problems(HDR, protos)
+    assert len(bad) == 1 and f"only header ['{gone}']" in bad[0], bad
+    less = RUST.replace(f"    pub fn {gone}(d: *mut wgs_data, out: *mut i32) -> wgs_status;\n", "")
+    assert less != RUST and rust_function_problems(HDR, abi.rust_functions(less)) == [f"{gone}: not in the extern block"]
+    less = HPP.replace(gone + "(", "(")
+    assert less != HPP and cpp_problems(HDR, less) == [f"{gone}: neither wrapped by wgsparkl_hip.hpp nor listed"]

@@ -16,7 +16,7 @@ import diag_truth as dt_
 import fluid_truth as ft
 import mixed_truth as mt
 from gpu_common import GRID_V_TOL, PART_TOL
-from helpers import BASE_FIELDS, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, report_margin
+from helpers import BASE_FIELDS, _digest, assert_close_to_truth, assert_same_bits, debug, new_data, pipeline, report_margin
 from oracle import np_oracle
 from test_gpu_fluid import ELASTIC_ROUNDINGS, FIELDS, SHAPES
 from wgsparkl_amd import _ffi, scenes
@@ -38,10 +38,6 @@ def _run(sc, calls=(15, 15), **overrides):
         data.pipeline.step(data, k)
     data.sync()
     return data
-
-
-def _digest(data):
-    return data.diagnostics(_ffi.DIAG_DIGEST).digest
 
 
 def _assert_same_particles(a, b, what=""):

@@ -17,7 +17,7 @@ import pytest
 
 import transfer_truth as T
 import wall_truth as W
-from helpers import debug, new_data, pipeline, report_margin
+from helpers import _digest, debug, new_data, pipeline, report_margin
 from wgsparkl_amd import _ffi, scenes
 from wgsparkl_amd.models import WALL_NONE, WALL_SEPARATE, WALL_SLIP, WALL_STICKY, Wall
 from wgsparkl_amd.sharded import lockstep_slabs
@@ -243,10 +243,6 @@ def test_the_same_cloud_without_walls_leaves_the_box(hip_libs, d, h):
 
 
 # ------------------------------------------------------------------------------------------------ 5. same bits
-def _digest(data):
-    return data.diagnostics(_ffi.DIAG_DIGEST).digest
-
-
 @pytest.mark.parametrize("d,h,which", [(2, 0.3, "B"), (3, 1.0, "A")])
 def test_same_bits(hip_libs, monkeypatch, d, h, which):
     sc = _cloud(d, h, which, seed=5, n=4000 if d == 3 else 2000)

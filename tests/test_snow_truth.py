@@ -3,10 +3,6 @@ restatement (numpy, LAPACK's fp32 SVD: another algorithm than the kernel's, and 
 deliberate mistakes in it, the GPU scenes meet their conditions from the truth alone, and what surrounds the kernel — the Python
 dataclass, the constants, the scene key, the header's prose — is in place."""
 import functools
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -16,7 +12,7 @@ import devmath_truth as DM
 import plastic_truth as PT
 import snow_truth as ST
 import transfer_truth as T
-from wgsparkl_amd import MpmData, _ffi, models, scenes
+from wgsparkl_amd import MpmData, models, scenes
 from wgsparkl_amd.sharded import NativeShard
 
 DP = np.array([ST.THETA_C, ST.THETA_S, ST.XI, ST.CAP, 1.0, 0.0])
@@ -199,6 +195,24 @@ def test_the_gpu_scenes_meet_their_conditions_from_the_truth_alone(case, d):
         assert 0.2 * ps.n < (~sn.has).sum() < 0.5 * ps.n
 
 
+def test_the_fracture_rule_is_one_truth_inside_snow_and_inside_drucker_prager():
+    """plastic_truth.Fracture built by Snow and by Plastic from the same (F, phase) agrees array for array, on a snow scene and on a
+    Drucker-Prager scene; Snow computes no Drucker-Prager outcome."""
+    for mod, case in ((ST, "layout1_fracture"), (PT, "mode1_fracture_corotated")):
+        sc, _ = mod.scene(case, 3)
+        ps = sc["particles"]
+        pt = T.substep(T.Inputs.of(ps), sc["cell_width"], sc["params"].dt, sc["params"].gravity)[2]
+        F = T.mat(T.unmat(pt.F).astype(np.float32), 3)
+        sn = ST.Snow(F, _rows(ps.n), ps.dp_state, ps.phase)
+        pl = PT.Plastic(F, None, ps.dp, ps.dp_state, ps.phase)
+        assert isinstance(sn.fr, PT.Fracture) and isinstance(pl.fr, PT.Fracture) and not isinstance(sn.fr, PT.Plastic)
+        assert 0 < sn.fr.broken.sum() < sn.fr.breakable.sum()
+        for k in ("s_max", "phase_in", "max_stretch", "breakable", "broken", "amb_frac", "phase64", "f_err"):
+            assert np.array_equal(getattr(sn.fr, k), getattr(pl.fr, k)) and getattr(pl, k) is getattr(pl.fr, k), k
+        assert all(np.array_equal(a, b) for a, b in zip(sn.fr.svd, pl.fr.svd)) and sn.svd[1] is sn.fr.svd[1]
+        assert not any(hasattr(o, k) for o in (sn, sn.fr) for k in ("res", "allowed")) and hasattr(pl, "res")
+
+
 # ------------------------------------------------------------------------------------------------ around the kernel
 def test_snow_dataclass_packs_the_six_slots_and_checks_the_preconditions():
     s = models.Snow()
@@ -213,67 +227,23 @@ def test_snow_dataclass_packs_the_six_slots_and_checks_the_preconditions():
     assert np.array_equal(ps.dp[0], s.as_array()) and ps.has_plasticity.all()
 
 
-EXT_PATH = os.path.join(abi.INCLUDE, "wgsparkl_hip_plasticity.h")
-
-
-def _gcc_values(names, dim):
-    """the values gcc gives the named constants through include/wgsparkl_hip.h alone (which includes the extension), -DWGS_DIM=dim"""
-    lines = ["#include <stdio.h>", '#include "wgsparkl_hip.h"', "int main(void) {"]
-    lines += [f'  printf("%lld\\n", (long long)({c}));' for c in names] + ["  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, "ext.c"), os.path.join(tmp, "ext")
-        with open(src, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", f"-DWGS_DIM={dim}", f"-I{abi.INCLUDE}", src, "-o", exe], check=True)
-        return [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-
-
-def test_the_extension_header_and_its_mirrors():
-    """include/wgsparkl_hip_plasticity.h with the means of tests/abi.py (the main header's table, tests/test_abi.py, is the surface of
-    version 7 as first fixed; the extension is read the same way here): its constants as gcc sees them through the main header, its
-    two prototypes against ctypes, the Rust block and the C++ wrapper, and the prose the header promises."""
-    raw = abi.read(EXT_PATH)
-    ext = abi.header(raw)
-    assert ext.structs == {} and ext.constants == ["WGS_PLASTICITY_DRUCKER_PRAGER", "WGS_PLASTICITY_SNOW"]
-    assert list(ext.functions) == ["wgs_set_plasticity_model", "wgs_get_plasticity_model"]
-    assert '#include "wgsparkl_hip_plasticity.h"' in abi.read(abi.HEADER_PATH) and not set(ext.functions) & set(abi.header().functions)
-    rust = abi.read(abi.RUST_PATH)
-    rs = abi.rust_layout(rust, 3).const
-    for dim in (2, 3):
-        assert _gcc_values(ext.constants + ["WGS_ABI_VERSION"], dim) == [0, 1, 7]
-    assert (models.PLASTICITY_DRUCKER_PRAGER, models.PLASTICITY_SNOW) == (rs["WGS_PLASTICITY_DRUCKER_PRAGER"], rs["WGS_PLASTICITY_SNOW"]) == (0, 1)
-    # ctypes: the same names in the same order, every kind the declared one; and what load() puts on the library is that
-    protos = _ffi.plasticity_prototypes()
-    assert list(protos) == list(ext.functions)
-    for name, (ret, params) in ext.functions.items():
-        want = (abi.return_kind(ret), abi.param_kinds(params))
-        assert (abi.ctypes_kind(protos[name][0]), [abi.ctypes_kind(t) for t in protos[name][1]]) == want, name
-    # Rust: the block behind the main extern block declares exactly these, with these kinds
-    blocks = rust.split('extern "C" {')
-    assert len(blocks) == 3
-    fns = abi.rust_functions('extern "C" {' + blocks[2])
-    assert fns == {n: (abi.return_kind(r), abi.param_kinds(p)) for n, (r, p) in ext.functions.items()}
-    assert not set(fns) & set(abi.rust_functions(rust))
-    # C++: both wrapped
-    hpp = abi.read(abi.HPP_PATH)
-    assert all(n + "(" in hpp for n in ext.functions)
-    # prose
-    text = " ".join(abi.read(abi.HEADER_PATH).replace("\n *", " ").split())
-    history = text[text.index("History: 5 ="):text.index("#define WGS_ABI_VERSION")]
-    assert re.search(r"still 7, the plasticity extension of wgsparkl_hip_plasticity\.h .* detect wgs_set_plasticity_model by symbol lookup\.", history)
+def test_the_header_states_the_snow_rule_its_declarations_and_its_two_values():
+    """What only snow can know of include/wgsparkl_hip.h (that its constants, prototypes and mirrors agree is tests/test_abi.py's, for
+    every entry of the header): the prose the section promises, its three declaration lines verbatim, and the two values."""
+    raw = abi.read(abi.HEADER_PATH)
     assert "wgs_status wgs_set_plasticity_model(wgs_data *data, int32_t kind);" in raw
     assert "wgs_status wgs_get_plasticity_model(wgs_data *data, int32_t *out);" in raw
     assert "enum { WGS_PLASTICITY_DRUCKER_PRAGER = 0, WGS_PLASTICITY_SNOW = 1 };" in raw
-    ext_text = " ".join(raw.replace("\n *", " ").split())
-    for phrase in ("0 <= theta_c < 1, theta_s >= 0, xi and h3 finite", "hf is taken of the UPDATED Jp", "detects wgs_set_plasticity_model by symbol lookup"):
-        assert phrase in ext_text, phrase
+    text = " ".join(raw.replace("\n *", " ").split())
+    section = text[text.index("/* Snow plasticity."):text.index("enum { WGS_PLASTICITY_DRUCKER_PRAGER")]
+    for phrase in ("0 <= theta_c < 1, theta_s >= 0, xi and h3 finite", "hf is taken of the UPDATED Jp"):
+        assert phrase in section, phrase
+    assert (models.PLASTICITY_DRUCKER_PRAGER, models.PLASTICITY_SNOW) == (0, 1)
 
 
 def test_library_exports_the_switch(hip_libs):
     for dim in (2, 3):
         lib, _ = hip_libs.load(dim)
-        for name, (restype, argtypes) in hip_libs.plasticity_prototypes().items():
-            assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes, name
         assert lib.wgs_set_plasticity_model(None, 0) == hip_libs.ERR_INVALID_ARGUMENT
         assert lib.wgs_get_plasticity_model(None, None) == hip_libs.ERR_INVALID_ARGUMENT
 

@@ -187,6 +187,9 @@ def prototypes(T):
         "wgs_set_grid_growth": (st, [vp, i32]),
         "wgs_set_domain_walls": (st, [vp, P(Wall)]),
         "wgs_get_domain_walls": (st, [vp, P(Wall)]),
+        # the plasticity rule of the data (Drucker-Prager | snow; no reference counterpart)
+        "wgs_set_plasticity_model": (st, [vp, i32]),
+        "wgs_get_plasticity_model": (st, [vp, P(i32)]),
         "wgs_debug_scan": (st, [vp, u32p, u32, u32p, u32p]),
         # multi-GPU (x-slab decomposition; new design, no reference counterpart)
         "wgs_data_create_sharded": (st, [vp, P(T.SimParams), P(T.Particle), size, u32p, P(T.Collider), size, f32, u32, u32,
@@ -216,15 +219,6 @@ def prototypes(T):
     }
 
 
-def plasticity_prototypes():
-    """name -> (restype, argtypes) of the entry points of include/wgsparkl_hip_plasticity.h, the plasticity extension the main header
-    includes (the plasticity rule of the data: Drucker-Prager | snow; no reference counterpart), in that header's order."""
-    return {
-        "wgs_set_plasticity_model": (C.c_int32, [C.c_void_p, C.c_int32]),
-        "wgs_get_plasticity_model": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
-    }
-
-
 EXPORTS = tuple(prototypes(make_types(3)))   # the names do not depend on the dimension
 
 _LIBS = {}
@@ -249,7 +243,7 @@ def load(dim: int):
         print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
-    for name, (restype, argtypes) in {**prototypes(T), **plasticity_prototypes()}.items():
+    for name, (restype, argtypes) in prototypes(T).items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)

@@ -86,7 +86,7 @@ class DruckerPrager:
         return np.array([self.h0, self.h1, self.h2, self.h3, self.lambda_, self.mu], dtype=F32)
 
 
-# Plasticity rule of an MpmData (include/wgsparkl_hip_plasticity.h WGS_PLASTICITY_*; `MpmData.set_plasticity_model`): what the six plasticity
+# Plasticity rule of an MpmData (include/wgsparkl_hip.h WGS_PLASTICITY_*; `MpmData.set_plasticity_model`): what the six plasticity
 # slots of a particle mean and which projection the plastic particle update applies.
 PLASTICITY_DRUCKER_PRAGER = 0   # models/drucker_prager.wgsl (reference default)
 PLASTICITY_SNOW = 1             # singular-value clamp with hardening (Stomakhin et al. 2013; no reference counterpart)
@@ -94,7 +94,7 @@ PLASTICITY_SNOW = 1             # singular-value clamp with hardening (Stomakhin
 
 @dataclass(frozen=True)
 class Snow:
-    """Parameters of PLASTICITY_SNOW, carried in the six slots of `DruckerPrager` reinterpreted (include/wgsparkl_hip_plasticity.h
+    """Parameters of PLASTICITY_SNOW, carried in the six slots of `DruckerPrager` reinterpreted (include/wgsparkl_hip.h
     "Snow plasticity"): h0 = theta_c (critical compression), h1 = theta_s (critical stretch), h2 = xi (hardening coefficient),
     h3 = the cap on the hardening exponent xi (1 - Jp), lambda = the switch (non-zero: on), mu unused. The elastic lambda, mu of
     the particle are its ElasticCoefficients. Usable wherever a DruckerPrager is (`ParticleSet.uniform(plasticity=Snow())`).
