@@ -145,6 +145,19 @@ class MpmData {
         check(wgs_get_domain_walls(h_, out.data()));
         return out;
     }
+    // force fields (no reference counterpart; wgsparkl_hip_forces.h): up to WGS_MAX_FORCE_FIELDS uniform / radial / vortex / drag rules on
+    // the grid nodes' velocities, each inside a region, applied in this order behind the grid update and in front of the walls. An empty
+    // vector removes them. Stream-ordered; no device memory; not part of a checkpoint.
+    void set_force_fields(const std::vector<wgs_force_field> &fields) {
+        check(wgs_set_force_fields(h_, fields.empty() ? nullptr : fields.data(), (uint32_t)fields.size()));
+    }
+    std::vector<wgs_force_field> force_fields() {
+        std::vector<wgs_force_field> out(WGS_MAX_FORCE_FIELDS);
+        uint32_t n = 0;
+        check(wgs_get_force_fields(h_, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
     // the plasticity rule (no reference counterpart): WGS_PLASTICITY_DRUCKER_PRAGER (default) or WGS_PLASTICITY_SNOW — singular-value clamp
     // with hardening on the corotated stress; the wgs_drucker_prager slots of a particle then read theta_c, theta_s, xi, exponent cap,
     // switch, unused. Stream-ordered; single-domain data under WGS_MODEL_COROTATED.

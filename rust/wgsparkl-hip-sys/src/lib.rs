@@ -7,6 +7,9 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_void};
 
+/// The force-field extension (include/wgsparkl_hip_forces.h): its struct, constants and two entry points live in a file of their own.
+pub mod forces;
+
 pub const DIM: usize = if cfg!(feature = "dim2") { 2 } else { 3 };
 pub type wgs_status = i32;
 pub const WGS_OK: wgs_status = 0;

@@ -6,10 +6,10 @@ The CPU oracle under /oracle is test infrastructure and is never imported here.
 """
 from . import models, scenes, solver  # noqa: F401
 from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, MODEL_PER_PARTICLE, DruckerPrager,  # noqa: F401
-                     ElasticCoefficients, FluidCoefficients, ParticlePhase, Wall)
+                     ElasticCoefficients, FluidCoefficients, ForceField, ParticlePhase, Wall)
 from .pipeline import KernelInvocationQueue, MpmData, MpmPipeline  # noqa: F401
 from .solver import Collider, Particle, ParticleDynamics, ParticleSet, SimulationParams  # noqa: F401
 
 __all__ = ["MpmPipeline", "MpmData", "KernelInvocationQueue", "Particle", "ParticleDynamics", "ParticleSet",
            "SimulationParams", "Collider", "ElasticCoefficients", "DruckerPrager", "ParticlePhase",
-           "MODEL_COROTATED", "MODEL_NEO_HOOKEAN", "MODEL_FLUID", "MODEL_PER_PARTICLE", "FluidCoefficients", "Wall", "models", "solver", "scenes"]
+           "MODEL_COROTATED", "MODEL_NEO_HOOKEAN", "MODEL_FLUID", "MODEL_PER_PARTICLE", "FluidCoefficients", "Wall", "ForceField", "models", "solver", "scenes"]

@@ -221,6 +221,27 @@ def prototypes(T):
 
 EXPORTS = tuple(prototypes(make_types(3)))   # the names do not depend on the dimension
 
+
+class ForceField(C.Structure):
+    """wgs_force_field (include/wgsparkl_hip_forces.h): one force field; the same 68 bytes in both dimensions."""
+    _fields_ = [("kind", C.c_uint32), ("falloff", C.c_uint32), ("region", C.c_uint32), ("strength", C.c_float), ("softening", C.c_float),
+                ("center", C.c_float * 3), ("vec", C.c_float * 3), ("region_center", C.c_float * 3), ("region_half", C.c_float * 3)]
+
+
+FORCE_NONE, FORCE_UNIFORM, FORCE_RADIAL, FORCE_VORTEX, FORCE_DRAG = 0, 1, 2, 3, 4   # WGS_FORCE_*
+REGION_ALL, REGION_BOX, REGION_BALL = 0, 1, 2                                        # WGS_REGION_*
+MAX_FORCE_FIELDS = 8                                                                 # WGS_MAX_FORCE_FIELDS
+
+
+def forces_prototypes():
+    """name -> (restype, argtypes) of the entry points of the extension header include/wgsparkl_hip_forces.h, in its order (apart from
+    prototypes(): that table is the main header's, entry for entry)."""
+    vp, st, u32 = C.c_void_p, C.c_int32, C.c_uint32
+    return {
+        "wgs_set_force_fields": (st, [vp, C.POINTER(ForceField), u32]),
+        "wgs_get_force_fields": (st, [vp, C.POINTER(ForceField), C.POINTER(u32)]),
+    }
+
 _LIBS = {}
 
 
@@ -243,7 +264,7 @@ def load(dim: int):
         print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
-    for name, (restype, argtypes) in prototypes(T).items():
+    for name, (restype, argtypes) in {**prototypes(T), **forces_prototypes()}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)

@@ -56,3 +56,5 @@ using namespace wgs;
 #include "capi_walls.inc"        // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_domain_walls
 #include "capi_plasticity.inc"   // the plasticity rule: the snow instantiations of the fused G2P, the field read-out and the energy passes (behind
                                  // them, likewise; their launch sites reach them by declaration) and extern "C": wgs_set / wgs_get_plasticity_model
+#include "kernels_forces.h"      // force fields: the rule on the nodes' velocities (behind every kernel that existed, likewise) ...
+#include "capi_forces.inc"       // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_force_fields

@@ -282,6 +282,11 @@ struct wgs_data {
     // enqueue_finish then launches k_grid_walls behind the grid update, with these as its argument (no device memory)
     wgs_wall walls[2 * WGS_DIM] = {};
     bool walls_set = false;
+    // force fields (capi_forces.inc): what wgs_set_force_fields last took, in its order, and how many; `forces_set`: some entry is not
+    // WGS_FORCE_NONE — enqueue_finish then launches k_grid_forces in front of the walls, with these as its argument (no device memory)
+    wgs_force_field forces[WGS_MAX_FORCE_FIELDS] = {};
+    uint32_t forces_n = 0;
+    bool forces_set = false;
     // the plasticity rule (capi_plasticity.inc, wgs_set_plasticity_model): WGS_PLASTICITY_*. A host-side choice of instantiation —
     // launch_g2p, the field read-out and the energy sum pick the snow kernels by it —, not a field of Dev: no kernel that existed
     // gets another argument block

@@ -9,6 +9,7 @@ namespace {
 wgs_status allreduce_impulses(wgs_data *d);  // host_sharded.inc
 void launch_bodies_integrate(wgs_data *d);   // behind the stages
 void launch_grid_walls(wgs_data *d);         // capi_walls.inc
+void launch_grid_forces(wgs_data *d);        // capi_forces.inc
 
 #ifndef WGS_PCDF_WAVES_MAX_VISITS
 #define WGS_PCDF_WAVES_MAX_VISITS 256
@@ -512,6 +513,9 @@ template <int DIM> wgs_status enqueue_finish(wgs_data *d) {
     // ---- "grid_update" (single-domain simulations: done by waves of the P2G launch above)
     if (n > 0 && !sub.gu_fused)
         launch_grid_update<DIM>(dev, s, dim3(grid_for(d, WGS_GU_WG_PER_CU)), epoch, sub.in_sharded_step, d->two_way, sub.shard_fused ? 1u : 0u);
+    // ---- force fields (wgs_set_force_fields; no reference counterpart): behind either form of the grid update and in front of the
+    // walls, whose postconditions keep holding; a launch of its own — data without fields launches what it always did
+    if (n > 0 && d->forces_set) launch_grid_forces(d);
     // ---- domain walls (wgs_set_domain_walls; no reference counterpart): the wall nodes' velocities are projected behind either
     // form of the grid update, in nodes and slabs alike, in a launch of its own — data without walls launches what it always did
     if (n > 0 && d->walls_set) launch_grid_walls(d);

@@ -6,7 +6,7 @@ src/models/drucker_prager.rs:6-53 (DruckerPrager, DruckerPragerPlasticState).
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -164,3 +164,67 @@ class Wall:
     def high(coordinate: float, h: float, type: int = WALL_SLIP, friction: float = 0.0) -> "Wall":
         """The high face whose first node is the one at or above `coordinate`: plane = ceil(coordinate / h)."""
         return Wall(int(type), float(friction), int(math.ceil(coordinate / h)))
+
+
+# Force fields (include/wgsparkl_hip_forces.h WGS_FORCE_* / WGS_REGION_*; no reference counterpart: the reference's only body force is
+# the gravity of its SimulationParams)
+FORCE_NONE = 0
+FORCE_UNIFORM = 1    # v += dt * vec
+FORCE_RADIAL = 2     # toward `center` (strength > 0 attracts)
+FORCE_VORTEX = 3     # about the axis `vec` through `center` (2D: +z)
+FORCE_DRAG = 4       # backward Euler relaxation toward the velocity `vec` at the rate `strength`
+REGION_ALL = 0
+REGION_BOX = 1       # |x_k - region_center_k| <= region_half_k on every axis
+REGION_BALL = 2      # |x - region_center|^2 <= region_half[0]^2
+MAX_FORCE_FIELDS = 8
+
+
+def _vec3(v):
+    v = tuple(float(x) for x in v)
+    if not 1 <= len(v) <= 3:
+        raise ValueError("a vector of a force field has 2 or 3 components")
+    return v + (0.0,) * (3 - len(v))
+
+
+@dataclass(frozen=True)
+class ForceField:
+    """One entry of `MpmData.set_force_fields`: a rule on the grid nodes' velocities (the header's "The rule"), applied once per substep
+    behind the grid update and in front of the domain walls, to the nodes with mass inside its region. Made by `uniform`, `radial`,
+    `vortex` or `drag`; `.within_box` / `.within_ball` give the same field confined to a region. Vectors take 2 or 3 components (the
+    third is ignored in 2D). A region face meant to lie between two nodes goes at (k + 1/2) h."""
+    kind: int = FORCE_NONE
+    falloff: int = 0
+    region: int = REGION_ALL
+    strength: float = 0.0
+    softening: float = 0.0
+    center: tuple = (0.0, 0.0, 0.0)
+    vec: tuple = (0.0, 0.0, 0.0)
+    region_center: tuple = (0.0, 0.0, 0.0)
+    region_half: tuple = (0.0, 0.0, 0.0)
+
+    @staticmethod
+    def uniform(acceleration) -> "ForceField":
+        """v += dt * acceleration"""
+        return ForceField(FORCE_UNIFORM, vec=_vec3(acceleration))
+
+    @staticmethod
+    def radial(center, strength: float, falloff: int = 0, softening: float = 0.0) -> "ForceField":
+        """r = center - x, q = |r|^2 + softening^2: v += dt * strength * w_falloff(q) * r — strength > 0 attracts; falloff 0: a spring
+        toward the centre, 3: an inverse-square attraction"""
+        return ForceField(FORCE_RADIAL, int(falloff), strength=float(strength), softening=float(softening), center=_vec3(center))
+
+    @staticmethod
+    def vortex(center, strength: float, axis=(0.0, 0.0, 1.0), falloff: int = 0, softening: float = 0.0) -> "ForceField":
+        """a swirl about the line through `center` along `axis` (2D: about +z); falloff 0: a rigid spin-up, 2: a line vortex"""
+        return ForceField(FORCE_VORTEX, int(falloff), strength=float(strength), softening=float(softening), center=_vec3(center), vec=_vec3(axis))
+
+    @staticmethod
+    def drag(rate: float, toward=(0.0, 0.0, 0.0)) -> "ForceField":
+        """relaxation toward the velocity `toward` at `rate` per second (backward Euler: stable for any rate; a huge rate prescribes it)"""
+        return ForceField(FORCE_DRAG, strength=float(rate), vec=_vec3(toward))
+
+    def within_box(self, center, half) -> "ForceField":
+        return replace(self, region=REGION_BOX, region_center=_vec3(center), region_half=_vec3(half))
+
+    def within_ball(self, center, radius: float) -> "ForceField":
+        return replace(self, region=REGION_BALL, region_center=_vec3(center), region_half=(float(radius), 0.0, 0.0))

@@ -449,13 +449,13 @@ class MpmData(DataHandle):
     @classmethod
     def from_scene(cls, pipeline, scene, **overrides):
         """The data one of the dicts `wgsparkl_amd.scenes` returns describes (the key table in that module's docstring): `new` with
-        its "model", then its "plasticity", "fluid_gamma", "models" and "walls" through their setters, in that order, each only where
+        its "model", then its "plasticity", "fluid_gamma", "models", "walls" and "forces" through their setters, in that order, each only where
         the scene has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
         `particles=snap`); `None` for one of the optional keys builds the scene without it (`models=None`: no table)."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
         data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
         for key, apply in (("plasticity", data.set_plasticity_model), ("fluid_gamma", data.set_fluid_eos),
-                           ("models", data.set_particle_models), ("walls", data.set_domain_walls)):
+                           ("models", data.set_particle_models), ("walls", data.set_domain_walls), ("forces", data.set_force_fields)):
             if sc.get(key) is not None:
                 apply(sc[key])
         return data
@@ -498,6 +498,32 @@ class MpmData(DataHandle):
         arr = (_ffi.Wall * (2 * self.dim))()
         _ffi.check(self.lib, self.lib.wgs_get_domain_walls(self._h, arr))
         return [Wall(int(w.type), float(w.friction), int(w.plane)) for w in arr]
+
+    def set_force_fields(self, fields):
+        """`wgs_set_force_fields`: up to `models.MAX_FORCE_FIELDS` `models.ForceField` (uniform, radial, vortex, drag; each everywhere, in a
+        box or in a ball), applied to the grid nodes' velocities in this order once per substep, behind the grid update and in front of
+        the domain walls; an entry None is kept as a FORCE_NONE entry and skipped; `None` or an empty list removes every field.
+        Stream-ordered; no device memory; not part of a checkpoint."""
+        fields = [] if fields is None else list(fields)
+        arr = (_ffi.ForceField * max(len(fields), 1))()
+        for a, f in zip(arr, fields):
+            if f is None:
+                continue
+            a.kind, a.falloff, a.region = int(f.kind), int(f.falloff), int(f.region)
+            a.strength, a.softening = float(f.strength), float(f.softening)
+            for name in ("center", "vec", "region_center", "region_half"):
+                v = tuple(getattr(f, name))
+                getattr(a, name)[:] = [float(x) for x in v + (0.0,) * (3 - len(v))]
+        _ffi.check(self.lib, self.lib.wgs_set_force_fields(self._h, arr if fields else None, len(fields)))
+
+    def force_fields(self):
+        """`wgs_get_force_fields`: what `set_force_fields` last took, as `models.ForceField` (FORCE_NONE entries included)."""
+        from .models import ForceField
+        arr = (_ffi.ForceField * _ffi.MAX_FORCE_FIELDS)()
+        n = C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_get_force_fields(self._h, arr, C.byref(n)))
+        return [ForceField(int(a.kind), int(a.falloff), int(a.region), float(a.strength), float(a.softening), tuple(a.center), tuple(a.vec),
+                           tuple(a.region_center), tuple(a.region_half)) for a in arr[:n.value]]
 
     def set_particle_models(self, models):
         """`wgs_set_particle_models`: one MODEL_COROTATED / MODEL_NEO_HOOKEAN / MODEL_FLUID per particle (np.uint8, the caller's order) —

@@ -16,6 +16,7 @@ The scene contract. Every builder returns a dict, and `MpmData.from_scene` (a wh
 | `fluid_gamma` | optional | the Tait exponent of `MODEL_FLUID`: `set_fluid_eos` |
 | `models` | optional | the per-particle table (np.uint8): `MpmData.set_particle_models`; an error on a slab |
 | `walls` | optional | the 2 * dim domain walls: `MpmData.set_domain_walls`; an error on a slab |
+| `forces` | optional | the force fields (a list of `models.ForceField`): `MpmData.set_force_fields`; an error on a slab |
 | `global_ids`, `partition` | slab scenes | the particles' names in the whole scene; the `SlabPartition` the slab's block range and neighbours come from |
 | `uniform_material` | slab scenes, optional | (mass, init_volume, lambda, mu) shared by every particle of every rank |
 
@@ -28,7 +29,7 @@ from __future__ import annotations
 import numpy as np
 
 from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, PLASTICITY_DRUCKER_PRAGER, PLASTICITY_SNOW, WALL_SLIP, WALL_STICKY,
-                     DruckerPrager, ElasticCoefficients, FluidCoefficients, ParticlePhase, Snow, Wall)
+                     DruckerPrager, ElasticCoefficients, FluidCoefficients, ForceField, ParticlePhase, Snow, Wall)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -440,6 +441,60 @@ def snowball(dim=3, radius=6.0, cell_width=1.0, speed=0.01, gap=0.5, snow=None, 
     return dict(particles=ps, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED,
                 plasticity=int(plasticity), walls=walls,
                 name=f"snowball {dim}D: {ps.n} particles, radius {radius} cells, thrown at a sticky wall at {speed} h/dt")
+
+
+def planetoid(dim=3, radius=5.0, cell_width=1.0, speed=0.05, attraction=None, jitter=0.05, young_modulus=10.0, density=10.0, with_field=True):
+    """A ball thrown apart and held together by a central attraction (scene key "forces"): particles at spacing h/2 inside a ball of
+    `radius` cells, each moving away from the centre at `speed` times the grid's cap h / dt times its distance over the radius; no
+    gravity, no colliders, no walls; one RADIAL field of falloff 0 at the centre — a spring of `attraction` per second squared.
+    With alpha = speed h / dt / (radius h) the outward rate, a particle under the spring alone reaches sqrt(1 + alpha^2 / attraction)
+    times its start distance: the default, (0.8 alpha)^2, turns every particle round at 1.6 times its own, inside twice the start
+    radius. The material is next to pressureless (the corotated energy grows with the sixth power of a dilation: anything stiffer
+    holds the ball together by itself), so nothing but the field does. `with_field=False`: the control, which flies apart."""
+    h = float(cell_width)
+    n_side = int(np.ceil(4.0 * radius)) + 1
+    origin = (6.0 * h,) * dim
+    pos = lattice((n_side,) * dim, origin, h, jitter)
+    centre = np.asarray(origin, np.float64) + 0.25 * n_side * h
+    rel = pos.astype(np.float64) - centre
+    keep = np.linalg.norm(rel, axis=1) <= radius * h
+    pos, rel = pos[keep], rel[keep]
+    ps = ParticleSet.uniform(pos, h / 4.0, density, ElasticCoefficients.from_young_modulus(young_modulus, 0.3), phase=ParticlePhase(1.0, FLT_MAX))
+    params = SimulationParams(gravity=(0.0,) * dim, dt=1.0e-3)
+    v_out = speed * h / params.dt
+    ps.vel[:] = (rel * (v_out / (radius * h))).astype(F32)
+    k = float(attraction) if attraction is not None else (0.8 * v_out / (radius * h)) ** 2
+    forces = [ForceField.radial(tuple(float(c) for c in centre), k)] if with_field else None
+    return dict(particles=ps, params=params, colliders=[], cell_width=h, grid_capacity=8192, model=MODEL_COROTATED, forces=forces,
+                centre=centre, start_radius=radius * h,
+                name=f"planetoid {dim}D: {ps.n} particles thrown apart at {speed} h/dt, held by a central spring of {k:.3g} / s^2")
+
+
+def vortex_tank(dim=3, tank=(24, 12, 24), cell_width=1.0, spin=40.0, drag_rate=20.0, jitter=0.05, density=1000.0, bulk_modulus=2.0e5,
+                viscosity=0.0, gamma=7.0):
+    """A stirred tank (scene keys "walls" and "forces"): Tait fluid (MODEL_FLUID), `tank` particles at spacing h/2, between slip domain
+    walls (floor and side faces, open at the top) under gravity; a VORTEX of falloff 0 about the vertical line through the middle of the
+    tank (2D: about +z through its middle) spins it up at `spin` per second squared, and a DRAG zone — a box over the lowest two cells
+    of the tank, its faces half-way between nodes — damps the flow along the floor at `drag_rate` per second."""
+    h = float(cell_width)
+    tank = tuple(tank)[:dim] if dim == 3 else (tank[0], tank[1])
+    origin = (8.3 * h, 2.2 * h, 8.3 * h)[:dim]
+    ps = ParticleSet.uniform(lattice(tank, origin, h, jitter), h / 4.0, density, FluidCoefficients(bulk_modulus, viscosity),
+                             phase=ParticlePhase(1.0, FLT_MAX))
+    lo = [origin[k] - 0.3 * h for k in range(dim)]
+    hi = [origin[k] + tank[k] * h / 2.0 + 0.3 * h for k in range(dim)]
+    walls = [Wall.low(lo[0], h), Wall.high(hi[0], h), Wall.low(2.0 * h, h), None]
+    if dim == 3:
+        walls += [Wall.low(lo[2], h), Wall.high(hi[2], h)]
+    mid = [0.5 * (lo[k] + hi[k]) for k in range(dim)]
+    floor_zone_centre = list(mid)
+    floor_zone_centre[1] = 3.0 * h
+    half = [1000.0 * h] * dim
+    half[1] = 1.5 * h                                            # nodes 2, 3 and 4 along y: faces at 1.5 h and 4.5 h
+    forces = [ForceField.vortex(mid, spin, axis=(0.0, 1.0, 0.0)), ForceField.drag(drag_rate).within_box(floor_zone_centre, half)]
+    return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0), colliders=[], cell_width=h,
+                grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma), walls=walls, forces=forces,
+                name=f"vortex tank {dim}D: {ps.n} fluid particles between grid walls, stirred by a vortex, damped along the floor")
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):
