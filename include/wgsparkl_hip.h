@@ -223,7 +223,8 @@ const char *wgs_build_info(void);
  * same way (one new struct, one enum and two new symbols) — detect wgs_set_domain_walls by symbol lookup. Still 7: WGS_PLASTICITY_*
  * and wgs_set_plasticity_model / wgs_get_plasticity_model were added the same way (one enum and two new symbols) — detect
  * wgs_set_plasticity_model by symbol lookup and, still 7, the force-field extension of wgsparkl_hip_forces.h — detect
- * wgs_set_force_fields by symbol lookup. */
+ * wgs_set_force_fields by symbol lookup and, still 7, the run-time particle extension of wgsparkl_hip_emit.h (reserved capacity,
+ * appended batches, emitters) — detect wgs_add_particles by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -452,6 +453,10 @@ wgs_status wgs_get_plasticity_model(wgs_data *data, int32_t *out);
 /* Force fields (uniform, radial, vortex and drag zones on the grid nodes): an extension header of their own — wgs_force_field,
  * the force and region kinds, the limit of eight fields per data, wgs_set_force_fields / wgs_get_force_fields and the rule. */
 #include "wgsparkl_hip_forces.h"
+/* Particles added at run time (a reserved particle capacity, batches appended by the caller, emitters fired by the library): an
+ * extension header of their own — wgs_data_create_reserved, wgs_get_particle_capacity, wgs_add_particles, wgs_emitter and its
+ * setter, getter and counters, the lattice and the schedule. */
+#include "wgsparkl_hip_emit.h"
 /* Environment (read once per wgs_data_create; developer switches, none of them changes a result): WGS_DEBUG = bit mask of
  * launch-SHAPE choices (two launches instead of one paired launch, the general binning pass on every substep, the grid
  * update and the message packing as launches of their own instead of workgroups of the P2G launch, ...) and

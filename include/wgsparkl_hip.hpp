@@ -111,9 +111,17 @@ class MpmData {
                               cell_width, grid_capacity, &d));
         return MpmData(d, particles.size(), colliders.size());
     }
-    MpmData(MpmData &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), nc_(o.nc_) {}
+    // ... with room for max(particles.size(), particle_capacity) particles in all (wgsparkl_hip_emit.h): add_particles and the emitters fill it
+    static MpmData create_reserved(const MpmPipeline &pipeline, const wgs_sim_params &params, const std::vector<wgs_particle> &particles,
+                                   const std::vector<wgs_collider> &colliders, float cell_width, uint32_t grid_capacity, uint32_t particle_capacity) {
+        wgs_data *d = nullptr;
+        check(wgs_data_create_reserved(pipeline.handle(), &params, particles.data(), particles.size(), colliders.data(), colliders.size(),
+                                       cell_width, grid_capacity, particle_capacity, &d));
+        return MpmData(d, particles.size(), colliders.size());
+    }
+    MpmData(MpmData &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), nc_(o.nc_), emitting_(o.emitting_) {}
     MpmData &operator=(MpmData &&o) noexcept {
-        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; nc_ = o.nc_; }
+        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; nc_ = o.nc_; emitting_ = o.emitting_; }
         return *this;
     }
     MpmData(const MpmData &) = delete;
@@ -125,11 +133,11 @@ class MpmData {
     void set_fluid_eos(float gamma) { check(wgs_set_fluid_eos(h_, gamma)); }
     // per-particle constitutive model: one WGS_MODEL_* (0 / 1 / 2) per particle in the caller's order; an empty vector drops the table
     void set_particle_models(const std::vector<uint8_t> &models) {
-        if (!models.empty() && models.size() != n_) throw Error(WGS_ERR_INVALID_ARGUMENT, "set_particle_models: one entry per particle");
+        if (!models.empty() && models.size() != count()) throw Error(WGS_ERR_INVALID_ARGUMENT, "set_particle_models: one entry per particle");
         check(wgs_set_particle_models(h_, models.empty() ? nullptr : models.data()));
     }
     std::vector<uint8_t> read_particle_models() {
-        std::vector<uint8_t> out(n_);
+        std::vector<uint8_t> out(count());
         check(wgs_read_particle_models(h_, out.data()));
         return out;
     }
@@ -158,6 +166,40 @@ class MpmData {
         out.resize(n);
         return out;
     }
+    // particles added at run time (no reference counterpart; wgsparkl_hip_emit.h). add_particles: `particles` behind the residents, with the
+    // caller's indices num_particles() ..; every reader includes them at once, the next substep rebuilds the block table. `models`: empty,
+    // or one WGS_MODEL_* per new particle (read only while the data carries a per-particle table). Blocking.
+    uint32_t particle_capacity() {
+        uint32_t cap = 0;
+        check(wgs_get_particle_capacity(h_, &cap));
+        return cap;
+    }
+    void add_particles(const std::vector<wgs_particle> &particles, const std::vector<uint8_t> &models = {}) {
+        if (!models.empty() && models.size() != particles.size()) throw Error(WGS_ERR_INVALID_ARGUMENT, "add_particles: one model per new particle");
+        check(wgs_add_particles(h_, particles.data(), models.empty() ? nullptr : models.data(), particles.size()));
+        n_ += particles.size();
+    }
+    // emitters: up to WGS_MAX_EMITTERS lattice boxes re-emitted every `period` substeps inside step(); an empty vector removes them. The
+    // call replaces the whole set and zeroes the counters. Host state of the handle; not part of a checkpoint.
+    void set_emitters(const std::vector<wgs_emitter> &emitters) {
+        const size_t now = count();
+        check(wgs_set_emitters(h_, emitters.empty() ? nullptr : emitters.data(), (uint32_t)emitters.size()));
+        n_ = now;
+        emitting_ = !emitters.empty();
+    }
+    std::vector<wgs_emitter> emitters() {
+        std::vector<wgs_emitter> out(WGS_MAX_EMITTERS);
+        uint32_t n = 0;
+        check(wgs_get_emitters(h_, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    // (particles emitted, batches skipped for lack of room) per emitter slot
+    std::pair<std::vector<uint64_t>, std::vector<uint64_t>> emitter_counts() const {
+        std::vector<uint64_t> emitted(WGS_MAX_EMITTERS), skipped(WGS_MAX_EMITTERS);
+        check(wgs_get_emitter_counts(h_, emitted.data(), skipped.data()));
+        return {emitted, skipped};
+    }
     // the plasticity rule (no reference counterpart): WGS_PLASTICITY_DRUCKER_PRAGER (default) or WGS_PLASTICITY_SNOW — singular-value clamp
     // with hardening on the corotated stress; the wgs_drucker_prager slots of a particle then read theta_c, theta_s, xi, exponent cap,
     // switch, unused. Stream-ordered; single-domain data under WGS_MODEL_COROTATED.
@@ -176,7 +218,7 @@ class MpmData {
     void set_body_mass_properties(const std::vector<wgs_mass_properties> &m) { check(wgs_set_body_mass_properties(h_, m.data(), m.size())); }
     // the blocking reads of src_testbed/step.rs:129-132,175-198 (poses) and of the positions buffer (particle3d.rs:197-201)
     std::vector<float> read_positions() {
-        std::vector<float> out(n_ * WGS_DIM);
+        std::vector<float> out(count() * WGS_DIM);
         check(wgs_read_positions(h_, out.data()));
         return out;
     }
@@ -187,7 +229,7 @@ class MpmData {
         return v;
     }
     std::vector<wgs_particle> read_particles() {
-        std::vector<wgs_particle> out(n_);
+        std::vector<wgs_particle> out(count());
         check(wgs_read_particles(h_, out.data(), nullptr));
         return out;
     }
@@ -218,8 +260,8 @@ class MpmData {
     // particle's stored state, evaluated on the device with the step's own functions; records in the caller's order. The host form
     // blocks; the _device form takes a DEVICE pointer (16-byte aligned), is stream-ordered on the data's stream and returns at once.
     std::vector<wgs_particle_field> particle_fields() {
-        std::vector<wgs_particle_field> out(n_);
-        if (n_) check(wgs_read_particle_fields(h_, out.data()));
+        std::vector<wgs_particle_field> out(count());
+        if (count()) check(wgs_read_particle_fields(h_, out.data()));
         return out;
     }
     void particle_fields_device(wgs_particle_field *device_out) { check(wgs_read_particle_fields_device(h_, device_out)); }
@@ -244,7 +286,7 @@ class MpmData {
     void grid_window_device(const int32_t (&lo)[WGS_DIM], const uint32_t (&dims)[WGS_DIM], float *device_out) {
         check(wgs_read_grid_window_device(h_, lo, dims, device_out));
     }
-    size_t num_particles() const { return n_; }
+    size_t num_particles() const { return count(); }
     wgs_data *handle() const { return h_; }
 
   private:
@@ -254,7 +296,15 @@ class MpmData {
         h_ = nullptr;
     }
     wgs_data *h_ = nullptr;
-    size_t n_ = 0, nc_ = 0;
+    // particles the data holds now: created with, added, emitted (host arithmetic on the emitters' counters)
+    size_t count() const {
+        size_t n = n_;
+        if (emitting_)
+            for (uint64_t e : emitter_counts().first) n += (size_t)e;
+        return n;
+    }
+    size_t n_ = 0, nc_ = 0;   // n_: without what the current emitters emitted
+    bool emitting_ = false;
 };
 
 inline void MpmPipeline::queue_step(MpmData &data, uint32_t num_substeps, bool add_timestamps) const {

@@ -9,6 +9,8 @@ use std::os::raw::{c_char, c_void};
 
 /// The force-field extension (include/wgsparkl_hip_forces.h): its struct, constants and two entry points live in a file of their own.
 pub mod forces;
+/// The run-time particle extension (include/wgsparkl_hip_emit.h): reserved capacity, appended batches, emitters.
+pub mod emit;
 
 pub const DIM: usize = if cfg!(feature = "dim2") { 2 } else { 3 };
 pub type wgs_status = i32;

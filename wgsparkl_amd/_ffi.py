@@ -242,6 +242,46 @@ def forces_prototypes():
         "wgs_get_force_fields": (st, [vp, C.POINTER(ForceField), C.POINTER(u32)]),
     }
 
+
+MAX_EMITTERS = 8   # WGS_MAX_EMITTERS
+
+
+def lowbias32(x):
+    """wgs_lowbias32 (include/wgsparkl_hip_emit.h), on numpy uint32 arrays or Python ints."""
+    import numpy as np
+    x = np.asarray(x, np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def emitter_type(T, D: int):
+    """wgs_emitter (include/wgsparkl_hip_emit.h) over the particle struct of `T` = make_types(D): 240 bytes in 3D, 176 in 2D."""
+    if not hasattr(T, "Emitter"):
+        class Emitter(C.Structure):
+            _fields_ = [("proto", T.Particle), ("model", C.c_uint8), ("lo", C.c_float * D), ("count", C.c_uint32 * D), ("spacing", C.c_float),
+                        ("jitter", C.c_float), ("seed", C.c_uint32), ("start_substep", C.c_uint32), ("period", C.c_uint32), ("batches", C.c_uint32)]
+        T.Emitter = Emitter
+    return T.Emitter
+
+
+def emit_prototypes(T, D: int):
+    """name -> (restype, argtypes) of the entry points of the extension header include/wgsparkl_hip_emit.h, in its order (apart from
+    prototypes(), like forces_prototypes())."""
+    P, vp, st, u32, f32, size = C.POINTER, C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
+    E = emitter_type(T, D)
+    return {
+        "wgs_data_create_reserved": (st, [vp, P(T.SimParams), P(T.Particle), size, P(T.Collider), size, f32, u32, u32, P(vp)]),
+        "wgs_get_particle_capacity": (st, [vp, P(u32)]),
+        "wgs_add_particles": (st, [vp, P(T.Particle), P(C.c_uint8), size]),
+        "wgs_set_emitters": (st, [vp, P(E), u32]),
+        "wgs_get_emitters": (st, [vp, P(E), P(u32)]),
+        "wgs_get_emitter_counts": (st, [vp, P(C.c_uint64), P(C.c_uint64)]),
+    }
+
+
 _LIBS = {}
 
 
@@ -264,7 +304,7 @@ def load(dim: int):
         print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
-    for name, (restype, argtypes) in {**prototypes(T), **forces_prototypes()}.items():
+    for name, (restype, argtypes) in {**prototypes(T), **forces_prototypes(), **emit_prototypes(T, dim)}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)

@@ -58,3 +58,5 @@ using namespace wgs;
                                  // them, likewise; their launch sites reach them by declaration) and extern "C": wgs_set / wgs_get_plasticity_model
 #include "kernels_forces.h"      // force fields: the rule on the nodes' velocities (behind every kernel that existed, likewise) ...
 #include "capi_forces.inc"       // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_force_fields
+#include "kernels_emit.h"        // particles added at run time: the device twin of creation's packing, k_append and k_emit (behind them, likewise) ...
+#include "capi_emit.inc"         // ... fire_emitters (wgs_step reaches it by declaration) and extern "C": wgs_data_create_reserved, wgs_add_particles, the emitters

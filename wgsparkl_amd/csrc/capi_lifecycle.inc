@@ -166,7 +166,21 @@ struct Staged {
     bool plastic = false;
 };
 
+// DruckerPrager::new(-1, -1): the six parameters of a particle without plasticity
+void default_dp_params(float out[6]) {
+    const float deg = 3.14159265358979323846f / 180.0f;
+    const float default_dp[6] = {35.0f * deg, 9.0f * deg, 0.2f, 10.0f * deg, -1.0f, -1.0f};
+    for (int k = 0; k < 6; k++) out[k] = default_dp[k];
+}
+
+// Does the plasticity / fracture branch ever run for this particle? `dp`: its six parameters or the defaults.
+// (particle_update.wgsl:98-122; max_stretch >= FLT_MAX can never be exceeded by a finite F)
+bool particle_is_plastic(const float *dp, float phase, float max_stretch) {
+    return (phase == 0.0f && dp[4] != 0.0f) || (phase > 0.0f && max_stretch > 0.0f && max_stretch < FLT_MAX);
+}
+
 // AoS -> SoA staging (GpuParticles::from_particles + GpuModels::from_particles, particle3d.rs:192-210, models/mod.rs:20-49).
+// (kernels_emit.h pack_particle does the same on the device for the particles that come later)
 Staged stage_particles(const CreateSpec &c, uint32_t npad) {
     Staged st;
     st.image.assign(buffer_floats<D>(npad), 0.f);
@@ -174,8 +188,8 @@ Staged stage_particles(const CreateSpec &c, uint32_t npad) {
     st.dp.assign((size_t)npad * 6, 0.f);
     st.phase.assign((size_t)npad * 2, 0.f);
     st.flags.assign(npad, 0u);
-    const float deg = 3.14159265358979323846f / 180.0f;
-    const float default_dp[6] = {35.0f * deg, 9.0f * deg, 0.2f, 10.0f * deg, -1.0f, -1.0f};  // DruckerPrager::new(-1, -1)
+    float default_dp[6];
+    default_dp_params(default_dp);
     uint32_t *pids = pid_plane<D>(st.image.data(), npad);
     for (uint32_t i = 0; i < (uint32_t)c.n; i++) {
         const wgs_particle &q = c.particles[i];
@@ -189,9 +203,7 @@ Staged stage_particles(const CreateSpec &c, uint32_t npad) {
         st.phase[(size_t)i * 2 + 1] = max_stretch;
         st.radius[i] = q.dynamics.init_radius;
         st.flags[i] = (q.has_plasticity ? 1u : 0u) | (q.has_phase ? 2u : 0u);
-        // Does the plasticity / fracture branch ever run for this particle?
-        // (particle_update.wgsl:98-122; max_stretch >= FLT_MAX can never be exceeded by a finite F)
-        if ((phase == 0.0f && dp[4] != 0.0f) || (phase > 0.0f && max_stretch > 0.0f && max_stretch < FLT_MAX)) st.plastic = true;
+        if (particle_is_plastic(dp, phase, max_stretch)) st.plastic = true;
     }
     return st;
 }
@@ -387,6 +399,7 @@ wgs_status wgs_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_substeps, 
     if (timestamps) {
         WGS_TRY(d->timing.events.create());   // (the first timestamped call)
         d->timing.events.used = 0;
+        d->timing.emit_marks.clear();
     }
     WGS_TRY(maintain_grid(d));
     {
@@ -403,6 +416,8 @@ wgs_status wgs_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_substeps, 
             }
             // (a whole substep: the four stages of host_substep.inc; the first substeps of a timestamped call record their marks)
             const int ts_slot = timestamps && d->timing.events.used < Events::MAX_SUBSTEPS ? d->timing.events.used++ : -1;
+            // (the emitters whose batch is due in front of this substep: new slots behind the residents, and the substep rebuilds the table)
+            if (d->emit_set) WGS_TRY(fire_emitters(d, ts_slot >= 0));
             WGS_TRY(begin_substep(d, false, ts_slot));
             WGS_TRY(enqueue_sort<D>(d));
             WGS_TRY(enqueue_p2g<D>(d, P2gLayers::all));

@@ -231,6 +231,11 @@ void resolve_timings(wgs_data *d) {
             if (hipEventElapsedTime(&ms, d->timing.events.ev[s][m], d->timing.events.ev[s][m + 1]) == hipSuccess)
                 d->timing.ms[pass_of_mark[m]] += ms;
         }
+    // (the emitting launches of the call, in front of their substeps' first mark: the table rebuild they ask for is "grid sort" too)
+    for (size_t m = 0; m + 1 < d->timing.emit_marks.size(); m += 2) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, d->timing.emit_marks[m], d->timing.emit_marks[m + 1]) == hipSuccess) d->timing.ms[WGS_PASS_GRID_SORT] += ms;
+    }
     d->timing.pending = false;
 }
 

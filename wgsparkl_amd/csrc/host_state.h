@@ -291,6 +291,12 @@ struct wgs_data {
     // launch_g2p, the field read-out and the energy sum pick the snow kernels by it —, not a field of Dev: no kernel that existed
     // gets another argument block
     int32_t plasticity = WGS_PLASTICITY_DRUCKER_PRAGER;
+    // emitters (capi_emit.inc): what wgs_set_emitters last took, in its order, and how many; `emit_set`: there is one — wgs_step then asks
+    // fire_emitters in front of every substep. Host state like the walls and the fields; the counters are those of wgs_get_emitter_counts
+    wgs_emitter emitters[WGS_MAX_EMITTERS] = {};
+    uint32_t emit_n = 0;
+    bool emit_set = false;
+    uint64_t emitted[WGS_MAX_EMITTERS] = {}, emit_skipped[WGS_MAX_EMITTERS] = {};
 
     // ---- allocation: every device buffer above and in `dev` (dev_alloc; wgs_data_destroy releases them all)
     DeviceMemory mem;
@@ -347,6 +353,7 @@ struct wgs_data {
         Events events;
         float ms[WGS_NUM_PASSES] = {0};
         float mark_overhead_ms = 0.f;   // average distance of two adjacent timing marks in the last timestamped step
+        std::vector<Event> emit_marks;  // pairs of marks around the emitting launches of a timestamped wgs_step (capi_emit.inc): "grid sort" time
         bool pending = false;
     } timing;
 };

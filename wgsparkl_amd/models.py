@@ -228,3 +228,65 @@ class ForceField:
 
     def within_ball(self, center, radius: float) -> "ForceField":
         return replace(self, region=REGION_BALL, region_center=_vec3(center), region_half=(float(radius), 0.0, 0.0))
+
+
+# Particles added at run time (include/wgsparkl_hip_emit.h; no reference counterpart: the reference's MpmData holds what it was created with)
+MAX_EMITTERS = 8
+
+
+@dataclass(frozen=True)
+class Emitter:
+    """One entry of `MpmData.set_emitters`: an axis-aligned lattice box of prod(count) particles, emitted again every `period` substeps
+    (the header's "Schedule" and "Positions"). `proto`: a `ParticleSet` of ONE particle — everything but its position is copied, its
+    velocity is the emission velocity; `model`: the MODEL_* of the emitted particles, read only while the data carries a per-particle
+    table. Point (i_0, ..) of a batch sits at lo_k + (i_k + 1/2) spacing + jitter * spacing * u_k, u_k in [-1/2, 1/2) from the hash of
+    (seed, emitter index, batch number, point index, axis). `batches` = 0: no limit. A batch that does not fit whole into the remaining
+    particle capacity is skipped and counted (`MpmData.emitter_counts`)."""
+    proto: object
+    lo: tuple
+    count: tuple
+    spacing: float
+    model: int = MODEL_COROTATED
+    jitter: float = 0.0
+    seed: int = 0
+    start_substep: int = 0
+    period: int = 1
+    batches: int = 0
+
+    def __post_init__(self):
+        dim = int(self.proto.dim)
+        if self.proto.n != 1:
+            raise ValueError("Emitter: proto is a ParticleSet of exactly one particle")
+        if len(self.lo) != dim or len(self.count) != dim:
+            raise ValueError("Emitter: lo and count have one entry per axis of the proto")
+        if any(int(c) != c or int(c) < 1 for c in self.count):
+            raise ValueError("Emitter: every count is an integer >= 1")
+        if int(self.period) != self.period or int(self.period) < 1:
+            raise ValueError("Emitter: period is an integer >= 1")
+        if not (math.isfinite(self.jitter) and 0.0 <= self.jitter <= 0.5):
+            raise ValueError("Emitter: jitter in [0, 0.5] (a fraction of the spacing)")
+        if not math.isfinite(self.spacing):
+            raise ValueError("Emitter: spacing finite")
+        if int(self.model) not in (MODEL_COROTATED, MODEL_NEO_HOOKEAN, MODEL_FLUID):
+            raise ValueError("Emitter: model is a MODEL_* value")
+        for name in ("seed", "start_substep", "batches"):
+            v = getattr(self, name)
+            if int(v) != v or not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"Emitter: {name} is an unsigned 32-bit integer")
+
+    @property
+    def batch_size(self) -> int:
+        return int(np.prod([int(c) for c in self.count], dtype=np.int64))
+
+    @staticmethod
+    def nozzle(proto, lo, count, spacing: float, dt: float, thickness: float = None, **kw) -> "Emitter":
+        """An emitter whose batches follow each other without a gap or an overlap: a slab of `thickness` (default: the lattice's extent
+        along the largest component of the emission velocity) leaves the nozzle every period = ceil(thickness / (|v| dt)) substeps."""
+        v = np.asarray(proto.vel[0], np.float64)
+        speed = float(np.linalg.norm(v))
+        if not speed > 0.0 or not dt > 0.0:
+            raise ValueError("Emitter.nozzle: the proto needs a velocity and dt must be > 0")
+        if thickness is None:
+            thickness = int(count[int(np.argmax(np.abs(v)))]) * float(spacing)
+        period = max(1, int(math.ceil(float(thickness) / (speed * float(dt)) - 1e-9)))
+        return Emitter(proto, tuple(float(x) for x in lo), tuple(int(c) for c in count), float(spacing), period=period, **kw)

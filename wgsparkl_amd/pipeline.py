@@ -421,16 +421,21 @@ class MpmData(DataHandle):
 
     def __init__(self, pipeline: MpmPipeline, params: SimulationParams, particles: ParticleSet,
                  colliders: Sequence[Collider], cell_width: float, grid_capacity: int,
-                 model: int = MODEL_COROTATED):
+                 model: int = MODEL_COROTATED, particle_capacity: Optional[int] = None):
         super().__init__(pipeline, colliders)
         if particles.dim != self.dim:
             raise ValueError("particle dimension does not match the pipeline")
-        self.n = particles.n
+        self._n_static, self._emitting = particles.n, False
         raw = _pack_particles(self.T, particles)
         h = C.c_void_p()
-        _ffi.check(self.lib, self.lib.wgs_data_create(
-            pipeline._h, C.byref(self._sim_params(params)), raw.ctypes.data_as(C.POINTER(self.T.Particle)), self.n,
-            self._collider_array(colliders), len(colliders), float(cell_width), int(grid_capacity), C.byref(h)))
+        args = (pipeline._h, C.byref(self._sim_params(params)), raw.ctypes.data_as(C.POINTER(self.T.Particle)), particles.n,
+                self._collider_array(colliders), len(colliders), float(cell_width), int(grid_capacity))
+        if particle_capacity is None:
+            _ffi.check(self.lib, self.lib.wgs_data_create(*args, C.byref(h)))
+        else:   # room for particles added at run time (add_particles, set_emitters)
+            if int(particle_capacity) != particle_capacity or not 0 <= int(particle_capacity) < 2 ** 32:
+                raise ValueError("particle_capacity is an unsigned 32-bit integer")
+            _ffi.check(self.lib, self.lib.wgs_data_create_reserved(*args, int(particle_capacity), C.byref(h)))
         self._h = h
         if model != MODEL_COROTATED:
             self.set_constitutive_model(model)
@@ -439,23 +444,95 @@ class MpmData(DataHandle):
         self._set_mesh_samples(colliders, cell_width)
 
     @classmethod
-    def new(cls, pipeline, params, particles, colliders, cell_width, grid_capacity, model=MODEL_COROTATED):
+    def new(cls, pipeline, params, particles, colliders, cell_width, grid_capacity, model=MODEL_COROTATED, particle_capacity=None):
         """MpmData::new(device, params, &particles, &bodies, &colliders, cell_width, grid_capacity)
-        (src/pipeline.rs:98-128). `particles` may be a ParticleSet or a list of Particle."""
+        (src/pipeline.rs:98-128). `particles` may be a ParticleSet or a list of Particle. `particle_capacity`: room for that many
+        particles in all (`wgs_data_create_reserved`), to be filled by `add_particles` or emitters."""
         if not isinstance(particles, ParticleSet):
             particles = ParticleSet.from_particles(particles)
-        return cls(pipeline, params, particles, colliders, cell_width, grid_capacity, model)
+        return cls(pipeline, params, particles, colliders, cell_width, grid_capacity, model, particle_capacity)
+
+    @property
+    def n(self) -> int:
+        """Particles the data holds now: those it was created with, those added, those its emitters emitted (host arithmetic)."""
+        return self._n_static + (sum(self.emitter_counts()[0]) if self._emitting else 0)
+
+    @property
+    def particle_capacity(self) -> int:
+        """`wgs_get_particle_capacity`: the particle slots reserved at creation."""
+        cap = C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_get_particle_capacity(self._h, C.byref(cap)))
+        return int(cap.value)
+
+    def add_particles(self, particles: ParticleSet, models=None):
+        """`wgs_add_particles`: `particles` behind the ones the data holds, with the caller's indices n .. n + k - 1; every reader
+        includes them at once, and the next substep rebuilds the block table. `models`: one MODEL_* per new particle (np.uint8), read
+        only while the data carries a per-particle table (None: the data's model). Needs room (`particle_capacity`). Blocking."""
+        if particles.dim != self.dim:
+            raise ValueError("particle dimension does not match the pipeline")
+        raw = _pack_particles(self.T, particles)
+        m = None
+        if models is not None:
+            m = np.ascontiguousarray(models, np.uint8).reshape(-1)
+            if m.shape[0] != particles.n:
+                raise ValueError("add_particles: one model per new particle")
+        _ffi.check(self.lib, self.lib.wgs_add_particles(self._h, raw.ctypes.data_as(C.POINTER(self.T.Particle)),
+                                                       m.ctypes.data_as(C.POINTER(C.c_uint8)) if m is not None else None, particles.n))
+        self._n_static += particles.n
+
+    def set_emitters(self, emitters):
+        """`wgs_set_emitters`: up to `models.MAX_EMITTERS` `models.Emitter`, fired in this order in front of the substeps their schedule
+        names, inside `MpmPipeline.step`; `None` or an empty list removes them. Replaces the whole set and zeroes `emitter_counts`.
+        Host state of the handle: no device memory, not part of a checkpoint."""
+        emitters = [] if emitters is None else list(emitters)
+        E = _ffi.emitter_type(self.T, self.dim)
+        arr = (E * max(len(emitters), 1))()
+        for a, e in zip(arr, emitters):
+            if e.proto.dim != self.dim:
+                raise ValueError("set_emitters: the proto's dimension does not match the pipeline")
+            words = _pack_particles(self.T, e.proto)
+            C.memmove(C.byref(a.proto), words.ctypes.data, C.sizeof(self.T.Particle))
+            a.model, a.spacing, a.jitter, a.seed = int(e.model), float(e.spacing), float(e.jitter), int(e.seed)
+            a.lo[:] = [float(x) for x in e.lo]
+            a.count[:] = [int(c) for c in e.count]
+            a.start_substep, a.period, a.batches = int(e.start_substep), int(e.period), int(e.batches)
+        n_now = self.n
+        _ffi.check(self.lib, self.lib.wgs_set_emitters(self._h, arr if emitters else None, len(emitters)))
+        self._n_static, self._emitting = n_now, bool(emitters)   # (the call zeroed the counters)
+
+    def emitters(self):
+        """`wgs_get_emitters`: what `set_emitters` last took, as `models.Emitter`."""
+        from .models import Emitter
+        E = _ffi.emitter_type(self.T, self.dim)
+        arr = (E * _ffi.MAX_EMITTERS)()
+        n = C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_get_emitters(self._h, arr, C.byref(n)))
+        out = []
+        for a in arr[:n.value]:
+            words = np.frombuffer(bytes(a.proto), F32).reshape(1, -1).copy()
+            out.append(Emitter(_unpack_particles(self.T, words, self.dim, None), tuple(a.lo), tuple(a.count), float(a.spacing), int(a.model),
+                               float(a.jitter), int(a.seed), int(a.start_substep), int(a.period), int(a.batches)))
+        return out
+
+    def emitter_counts(self):
+        """`wgs_get_emitter_counts`: (particles emitted, batches skipped for lack of room) per emitter of the set, as two lists."""
+        emitted, skipped = (C.c_uint64 * _ffi.MAX_EMITTERS)(), (C.c_uint64 * _ffi.MAX_EMITTERS)()
+        _ffi.check(self.lib, self.lib.wgs_get_emitter_counts(self._h, emitted, skipped))
+        k = len(self.emitters()) if self._emitting else 0
+        return [int(x) for x in emitted[:k]], [int(x) for x in skipped[:k]]
 
     @classmethod
     def from_scene(cls, pipeline, scene, **overrides):
         """The data one of the dicts `wgsparkl_amd.scenes` returns describes (the key table in that module's docstring): `new` with
-        its "model", then its "plasticity", "fluid_gamma", "models", "walls" and "forces" through their setters, in that order, each only where
-        the scene has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
+        its "model" and "particle_capacity", then its "plasticity", "fluid_gamma", "models", "walls", "forces" and "emitters" through their
+        setters, in that order, each only where the scene has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
         `particles=snap`); `None` for one of the optional keys builds the scene without it (`models=None`: no table)."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
-        data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"])
+        reserve = {} if sc.get("particle_capacity") is None else {"particle_capacity": sc["particle_capacity"]}
+        data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"], **reserve)
         for key, apply in (("plasticity", data.set_plasticity_model), ("fluid_gamma", data.set_fluid_eos),
-                           ("models", data.set_particle_models), ("walls", data.set_domain_walls), ("forces", data.set_force_fields)):
+                           ("models", data.set_particle_models), ("walls", data.set_domain_walls), ("forces", data.set_force_fields),
+                           ("emitters", data.set_emitters)):
             if sc.get(key) is not None:
                 apply(sc[key])
         return data

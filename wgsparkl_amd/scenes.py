@@ -17,11 +17,13 @@ The scene contract. Every builder returns a dict, and `MpmData.from_scene` (a wh
 | `models` | optional | the per-particle table (np.uint8): `MpmData.set_particle_models`; an error on a slab |
 | `walls` | optional | the 2 * dim domain walls: `MpmData.set_domain_walls`; an error on a slab |
 | `forces` | optional | the force fields (a list of `models.ForceField`): `MpmData.set_force_fields`; an error on a slab |
+| `particle_capacity` | optional | room for that many particles in all, to be filled at run time (`MpmData.add_particles`, emitters): `wgs_data_create_reserved`; an error on a slab |
+| `emitters` | optional | the emitters (a list of `models.Emitter`): `MpmData.set_emitters`; an error on a slab |
 | `global_ids`, `partition` | slab scenes | the particles' names in the whole scene; the `SlabPartition` the slab's block range and neighbours come from |
 | `uniform_material` | slab scenes, optional | (mass, init_volume, lambda, mu) shared by every particle of every rank |
 
-The optional keys are applied at creation in the order of the table, each only where the scene has the key and its value is not
-None. Any other key (`fluid`, `solid_model`, `global_particles`, `name`, `bytes_per_particle`, ...) is information for the
+The optional keys are applied at creation in the order of the table (`particle_capacity` with the creation itself), each only where
+the scene has the key and its value is not None. Any other key (`fluid`, `solid_model`, `global_particles`, `name`, `bytes_per_particle`, ...) is information for the
 caller; the constructors ignore it.
 """
 from __future__ import annotations
@@ -29,7 +31,7 @@ from __future__ import annotations
 import numpy as np
 
 from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, PLASTICITY_DRUCKER_PRAGER, PLASTICITY_SNOW, WALL_SLIP, WALL_STICKY,
-                     DruckerPrager, ElasticCoefficients, FluidCoefficients, ForceField, ParticlePhase, Snow, Wall)
+                     DruckerPrager, ElasticCoefficients, Emitter, FluidCoefficients, ForceField, ParticlePhase, Snow, Wall)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -495,6 +497,59 @@ def vortex_tank(dim=3, tank=(24, 12, 24), cell_width=1.0, spin=40.0, drag_rate=2
     return dict(particles=ps, params=SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0), colliders=[], cell_width=h,
                 grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma), walls=walls, forces=forces,
                 name=f"vortex tank {dim}D: {ps.n} fluid particles between grid walls, stirred by a vortex, damped along the floor")
+
+
+def _nozzle(dim, proto, centre, across, rows, h, dt, speed, batches, jitter, seed, **kw):
+    """an emitter pouring along -y: a lattice of `across` points per horizontal axis and `rows` layers at spacing h/2, centred on
+    `centre` (its low corner kept on the h/4 lattice), its prototype falling at `speed` times h / dt, one slab per period"""
+    count = tuple(rows if k == 1 else across for k in range(dim))
+    lo = tuple(float(np.floor((centre[k] - count[k] * h / 4.0) / (h / 4.0)) * (h / 4.0)) for k in range(dim))
+    proto.vel[0, 1] = F32(-speed * h / dt)
+    return Emitter.nozzle(proto, lo, count, h / 2.0, dt, jitter=jitter, seed=seed, batches=batches, **kw)
+
+
+def faucet(dim=3, tank=8, across=4, rows=1, height=10.0, speed=0.0625, batches=32, cell_width=1.0, jitter=0.1, density=1000.0,
+           bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, seed=2024):
+    """A faucet filling a tank (scene keys "particle_capacity" and "emitters"): the data starts EMPTY; one emitter `height` cells above
+    the floor pours Tait fluid (MODEL_FLUID) — `across`^(dim-1) x `rows` particles per batch at spacing h/2, falling at `speed` times the
+    grid's cap h / dt, a new slab whenever the last one has cleared the nozzle (`Emitter.nozzle`) — into a tank of slip domain walls
+    `tank` cells wide (floor and side faces, open at the top). Room for `batches` batches, which is also the emitter's limit."""
+    h = float(cell_width)
+    params = SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0)
+    fluid = FluidCoefficients(bulk_modulus, viscosity)
+    empty = ParticleSet.uniform(np.zeros((0, dim), F32), h / 4.0, density, fluid, phase=ParticlePhase(1.0, FLT_MAX))
+    proto = ParticleSet.uniform(np.zeros((1, dim), F32), h / 4.0, density, fluid, phase=ParticlePhase(1.0, FLT_MAX))
+    lo_plane, hi_plane, floor = 4, 4 + int(tank), 2
+    centre = [0.5 * (lo_plane + hi_plane) * h] * dim
+    centre[1] = (floor + height) * h
+    em = _nozzle(dim, proto, centre, across, rows, h, params.dt, speed, batches, jitter, seed)
+    walls = [Wall(WALL_SLIP, 0.0, lo_plane), Wall(WALL_SLIP, 0.0, hi_plane), Wall(WALL_SLIP, 0.0, floor), None]
+    if dim == 3:
+        walls += [Wall(WALL_SLIP, 0.0, lo_plane), Wall(WALL_SLIP, 0.0, hi_plane)]
+    return dict(particles=empty, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma),
+                walls=walls, particle_capacity=int(batches) * em.batch_size, emitters=[em],
+                name=f"faucet {dim}D: {em.batch_size} fluid particles every {em.period} substeps into a tank of grid walls, starting empty")
+
+
+def sand_pour(dim=3, heap=(8, 2, 8), across=3, rows=1, height=8.0, speed=0.0625, batches=32, cell_width=1.0, jitter=0.1, density=2700.0,
+              young_modulus=1.0e7, poisson=0.2, seed=2025):
+    """Sand running onto a heap (scene keys "particle_capacity" and "emitters"): Drucker-Prager sand, a small starting heap of `heap`
+    particles at spacing h/2 on the floor cuboid — so that the data's step carries plastic state from its creation on — and one emitter
+    `height` cells above the floor pouring the same sand (bit for bit the heap's material: the uniform layouts hold it) onto it."""
+    h = float(cell_width)
+    heap = tuple(heap)[:dim] if dim == 3 else (heap[0], heap[1])
+    params = SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0)
+    sand = dict(model=ElasticCoefficients.from_young_modulus(young_modulus, poisson), plasticity=DruckerPrager.new(young_modulus, poisson), phase=None)
+    origin = (8.0 * h, 2.2 * h, 8.0 * h)[:dim]                  # floor top at y = 2 h
+    ps = ParticleSet.uniform(lattice(heap, origin, h, 0.05), h / 4.0, density, **sand)
+    proto = ParticleSet.uniform(np.zeros((1, dim), F32), h / 4.0, density, **sand)
+    centre = [origin[k] + heap[k] * h / 4.0 for k in range(dim)]
+    centre[1] = (2.0 + height) * h
+    em = _nozzle(dim, proto, centre, across, rows, h, params.dt, speed, batches, jitter, seed)
+    floor = Collider.cuboid((1000.0 * h, 2.0 * h, 1000.0 * h), (0.0, 0.0, 0.0)) if dim == 3 else Collider.cuboid((1000.0 * h, 2.0 * h), (0.0, 0.0), rotation=(0.0,))
+    return dict(particles=ps, params=params, colliders=[floor], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED,
+                particle_capacity=ps.n + int(batches) * em.batch_size, emitters=[em],
+                name=f"sand pour {dim}D: {em.batch_size} sand particles every {em.period} substeps onto a heap of {ps.n} on a floor collider")
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):
