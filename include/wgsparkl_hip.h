@@ -224,7 +224,8 @@ const char *wgs_build_info(void);
  * and wgs_set_plasticity_model / wgs_get_plasticity_model were added the same way (one enum and two new symbols) — detect
  * wgs_set_plasticity_model by symbol lookup and, still 7, the force-field extension of wgsparkl_hip_forces.h — detect
  * wgs_set_force_fields by symbol lookup and, still 7, the run-time particle extension of wgsparkl_hip_emit.h (reserved capacity,
- * appended batches, emitters) — detect wgs_add_particles by symbol lookup. */
+ * appended batches, emitters) — detect wgs_add_particles by symbol lookup and, still 7, the particle-removal extension of
+ * wgsparkl_hip_remove.h (masks, regions, scheduled sinks) — detect wgs_remove_particles by symbol lookup. */
 #define WGS_ABI_VERSION 7
 uint32_t wgs_abi_version(void);
 
@@ -457,6 +458,10 @@ wgs_status wgs_get_plasticity_model(wgs_data *data, int32_t *out);
  * extension header of their own — wgs_data_create_reserved, wgs_get_particle_capacity, wgs_add_particles, wgs_emitter and its
  * setter, getter and counters, the lattice and the schedule. */
 #include "wgsparkl_hip_emit.h"
+/* Particles removed at run time (a mask of the caller's, regions evaluated on the device, sinks the library evaluates on a schedule):
+ * an extension header of their own — wgs_remove_particles[_device], wgs_remove_particles_in, wgs_sink and its setter, getter and
+ * counters, the membership rule, the renumbering and the schedule. */
+#include "wgsparkl_hip_remove.h"
 /* Environment (read once per wgs_data_create; developer switches, none of them changes a result): WGS_DEBUG = bit mask of
  * launch-SHAPE choices (two launches instead of one paired launch, the general binning pass on every substep, the grid
  * update and the message packing as launches of their own instead of workgroups of the P2G launch, ...) and

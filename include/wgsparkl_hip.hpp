@@ -119,9 +119,9 @@ class MpmData {
                                        cell_width, grid_capacity, particle_capacity, &d));
         return MpmData(d, particles.size(), colliders.size());
     }
-    MpmData(MpmData &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), nc_(o.nc_), emitting_(o.emitting_) {}
+    MpmData(MpmData &&o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), nc_(o.nc_), emitting_(o.emitting_), sinking_(o.sinking_) {}
     MpmData &operator=(MpmData &&o) noexcept {
-        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; nc_ = o.nc_; emitting_ = o.emitting_; }
+        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; nc_ = o.nc_; emitting_ = o.emitting_; sinking_ = o.sinking_; }
         return *this;
     }
     MpmData(const MpmData &) = delete;
@@ -184,8 +184,8 @@ class MpmData {
     void set_emitters(const std::vector<wgs_emitter> &emitters) {
         const size_t now = count();
         check(wgs_set_emitters(h_, emitters.empty() ? nullptr : emitters.data(), (uint32_t)emitters.size()));
-        n_ = now;
         emitting_ = !emitters.empty();
+        rebase(now);
     }
     std::vector<wgs_emitter> emitters() {
         std::vector<wgs_emitter> out(WGS_MAX_EMITTERS);
@@ -199,6 +199,51 @@ class MpmData {
         std::vector<uint64_t> emitted(WGS_MAX_EMITTERS), skipped(WGS_MAX_EMITTERS);
         check(wgs_get_emitter_counts(h_, emitted.data(), skipped.data()));
         return {emitted, skipped};
+    }
+    // particles removed at run time (no reference counterpart; wgsparkl_hip_remove.h). remove_particles: `remove` has one byte per particle
+    // in the caller's order, nonzero = remove; the survivors keep their relative order and are renumbered densely, every reader answers
+    // them under the new indices at once, the next substep rebuilds the block table. Returns kept_from: the old index of every new
+    // index. Blocking (the new particle count is read back). remove_particles_in: the regions of `regions` evaluated on the device, now.
+    std::vector<uint32_t> remove_particles(const std::vector<uint8_t> &remove) {
+        if (remove.size() != count()) throw Error(WGS_ERR_INVALID_ARGUMENT, "remove_particles: one mask byte per particle");
+        if (remove.empty()) return {};
+        std::vector<uint32_t> kept_from(remove.size());
+        uint32_t removed = 0;
+        check(wgs_remove_particles(h_, remove.data(), kept_from.data(), &removed));
+        kept_from.resize(remove.size() - removed);
+        n_ -= removed;
+        return kept_from;
+    }
+    std::vector<uint32_t> remove_particles_in(const std::vector<wgs_sink> &regions) {
+        const size_t now = count();
+        std::vector<uint32_t> kept_from(now + 1);
+        uint32_t removed = 0;
+        check(wgs_remove_particles_in(h_, regions.empty() ? nullptr : regions.data(), (uint32_t)regions.size(), kept_from.data(), &removed));
+        kept_from.resize(now - removed);
+        n_ -= removed;
+        return kept_from;
+    }
+    // sinks: up to WGS_MAX_SINKS regions evaluated in one pass in front of the substeps their schedule names, ahead of the emitters, inside
+    // step() — which waits for the stream there; an empty vector removes them. The call replaces the whole set and zeroes the counters.
+    // Host state of the handle; not part of a checkpoint.
+    void set_sinks(const std::vector<wgs_sink> &sinks) {
+        const size_t now = count();
+        check(wgs_set_sinks(h_, sinks.empty() ? nullptr : sinks.data(), (uint32_t)sinks.size()));
+        sinking_ = !sinks.empty();
+        rebase(now);
+    }
+    std::vector<wgs_sink> sinks() {
+        std::vector<wgs_sink> out(WGS_MAX_SINKS);
+        uint32_t n = 0;
+        check(wgs_get_sinks(h_, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    // particles removed per sink slot (a particle in several sinks counts for the first)
+    std::vector<uint64_t> sink_counts() const {
+        std::vector<uint64_t> removed(WGS_MAX_SINKS);
+        check(wgs_get_sink_counts(h_, removed.data()));
+        return removed;
     }
     // the plasticity rule (no reference counterpart): WGS_PLASTICITY_DRUCKER_PRAGER (default) or WGS_PLASTICITY_SNOW — singular-value clamp
     // with hardening on the corotated stress; the wgs_drucker_prager slots of a particle then read theta_c, theta_s, xi, exponent cap,
@@ -296,15 +341,23 @@ class MpmData {
         h_ = nullptr;
     }
     wgs_data *h_ = nullptr;
-    // particles the data holds now: created with, added, emitted (host arithmetic on the emitters' counters)
+    // particles the data holds now: created with, added, emitted, less those removed and those the sinks took (host arithmetic on the
+    // emitters' and the sinks' counters)
     size_t count() const {
         size_t n = n_;
         if (emitting_)
             for (uint64_t e : emitter_counts().first) n += (size_t)e;
+        if (sinking_)
+            for (uint64_t r : sink_counts()) n -= (size_t)r;
         return n;
     }
-    size_t n_ = 0, nc_ = 0;   // n_: without what the current emitters emitted
-    bool emitting_ = false;
+    // after a setter zeroed counters: count() answers `now` again
+    void rebase(size_t now) {
+        n_ = now;
+        n_ += now - count();
+    }
+    size_t n_ = 0, nc_ = 0;   // n_: without what the current emitters emitted and the current sinks took (modulo 2^64: the sum is what counts)
+    bool emitting_ = false, sinking_ = false;
 };
 
 inline void MpmPipeline::queue_step(MpmData &data, uint32_t num_substeps, bool add_timestamps) const {

@@ -11,6 +11,8 @@ use std::os::raw::{c_char, c_void};
 pub mod forces;
 /// The run-time particle extension (include/wgsparkl_hip_emit.h): reserved capacity, appended batches, emitters.
 pub mod emit;
+/// The particle-removal extension (include/wgsparkl_hip_remove.h): masks, regions, scheduled sinks.
+pub mod remove;
 
 pub const DIM: usize = if cfg!(feature = "dim2") { 2 } else { 3 };
 pub type wgs_status = i32;

@@ -282,6 +282,31 @@ def emit_prototypes(T, D: int):
     }
 
 
+class Sink(C.Structure):
+    """wgs_sink (include/wgsparkl_hip_remove.h): a region, a side and a schedule; the same 40 bytes in both dimensions."""
+    _fields_ = [("region", C.c_uint32), ("side", C.c_uint32), ("center", C.c_float * 3), ("half", C.c_float * 3),
+                ("start_substep", C.c_uint32), ("period", C.c_uint32)]
+
+
+MAX_SINKS = 8                        # WGS_MAX_SINKS
+SINK_INSIDE, SINK_OUTSIDE = 0, 1     # WGS_SINK_*
+
+
+def remove_prototypes():
+    """name -> (restype, argtypes) of the entry points of the extension header include/wgsparkl_hip_remove.h, in its order (apart from
+    prototypes(), like forces_prototypes())."""
+    P, vp, st, u32, u8p = C.POINTER, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint8)
+    return {
+        "wgs_remove_particles": (st, [vp, u8p, P(u32), P(u32)]),
+        "wgs_remove_particles_device": (st, [vp, vp, vp, P(u32)]),
+        "wgs_remove_particles_in": (st, [vp, P(Sink), u32, P(u32), P(u32)]),
+        "wgs_set_sinks": (st, [vp, P(Sink), u32]),
+        "wgs_get_sinks": (st, [vp, P(Sink), P(u32)]),
+        "wgs_get_sink_counts": (st, [vp, P(C.c_uint64)]),
+        "wgs_debug_compact_map": (st, [vp, u8p, u32, P(u32), P(u32)]),
+    }
+
+
 _LIBS = {}
 
 
@@ -304,7 +329,7 @@ def load(dim: int):
         print(f"wgsparkl_amd: WGS_LIB_DIR in force, loading {os.path.basename(path)} from {_LIB_DIR}", file=sys.stderr, flush=True)
     lib = C.CDLL(path)
     T = make_types(dim)
-    for name, (restype, argtypes) in {**prototypes(T), **forces_prototypes(), **emit_prototypes(T, dim)}.items():
+    for name, (restype, argtypes) in {**prototypes(T), **forces_prototypes(), **emit_prototypes(T, dim), **remove_prototypes()}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.wgs_abi_version() != ABI_VERSION:   # (the structs carry no size field: include/wgsparkl_hip.h WGS_ABI_VERSION)

@@ -19,7 +19,7 @@ FLAGS="-O3 -std=c++17 -fPIC -shared --offload-arch=${ARCH} -fno-fast-math -ffp-c
 # library's __hip_cuid_* symbol, so another spelling of the same path gives other bytes around the same code object)
 OUT=${WGS_OUT_DIR:+$WGS_OUT_DIR/}
 [[ -n "$OUT" ]] && mkdir -p "$OUT"
-sources=$(sha256sum capi.hip *.h *.inc ../../include/wgsparkl_hip.h ../../include/wgsparkl_hip_forces.h ../../include/wgsparkl_hip_emit.h)
+sources=$(sha256sum capi.hip *.h *.inc ../../include/wgsparkl_hip.h ../../include/wgsparkl_hip_forces.h ../../include/wgsparkl_hip_emit.h ../../include/wgsparkl_hip_remove.h)
 pids=()
 for dim in 3 2; do
   out="${OUT}libwgsparkl${dim}d_hip.so"

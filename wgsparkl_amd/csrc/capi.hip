@@ -60,3 +60,5 @@ using namespace wgs;
 #include "capi_forces.inc"       // ... its launch (enqueue_finish reaches it by declaration) and extern "C": wgs_set / wgs_get_force_fields
 #include "kernels_emit.h"        // particles added at run time: the device twin of creation's packing, k_append and k_emit (behind them, likewise) ...
 #include "capi_emit.inc"         // ... fire_emitters (wgs_step reaches it by declaration) and extern "C": wgs_data_create_reserved, wgs_add_particles, the emitters
+#include "kernels_remove.h"      // particles removed at run time: mark, the keep-scan, the compaction (behind them, likewise) ...
+#include "capi_remove.inc"       // ... fire_sinks (wgs_step reaches it by declaration) and extern "C": wgs_remove_particles[_device / _in], the sinks

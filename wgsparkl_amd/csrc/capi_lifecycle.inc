@@ -417,6 +417,8 @@ wgs_status wgs_step(wgs_pipeline *pipeline, wgs_data *d, uint32_t num_substeps, 
             // (a whole substep: the four stages of host_substep.inc; the first substeps of a timestamped call record their marks)
             const int ts_slot = timestamps && d->timing.events.used < Events::MAX_SUBSTEPS ? d->timing.events.used++ : -1;
             // (the emitters whose batch is due in front of this substep: new slots behind the residents, and the substep rebuilds the table)
+            // (ahead of them the sinks that are due: the room they free is the emitters' — the one place a substep may wait for the stream)
+            if (d->sinks_set) WGS_TRY(fire_sinks(d, ts_slot >= 0));
             if (d->emit_set) WGS_TRY(fire_emitters(d, ts_slot >= 0));
             WGS_TRY(begin_substep(d, false, ts_slot));
             WGS_TRY(enqueue_sort<D>(d));

@@ -297,6 +297,12 @@ struct wgs_data {
     uint32_t emit_n = 0;
     bool emit_set = false;
     uint64_t emitted[WGS_MAX_EMITTERS] = {}, emit_skipped[WGS_MAX_EMITTERS] = {};
+    // sinks (capi_remove.inc): what wgs_set_sinks last took, in its order, and how many; `sinks_set`: there is one — wgs_step then asks
+    // fire_sinks in front of every substep, ahead of the emitters. Host state likewise; the counters are those of wgs_get_sink_counts
+    wgs_sink sinks[WGS_MAX_SINKS] = {};
+    uint32_t sink_n = 0;
+    bool sinks_set = false;
+    uint64_t sink_removed[WGS_MAX_SINKS] = {};
 
     // ---- allocation: every device buffer above and in `dev` (dev_alloc; wgs_data_destroy releases them all)
     DeviceMemory mem;

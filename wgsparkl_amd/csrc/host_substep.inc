@@ -11,6 +11,7 @@ void launch_bodies_integrate(wgs_data *d);   // behind the stages
 void launch_grid_walls(wgs_data *d);         // capi_walls.inc
 void launch_grid_forces(wgs_data *d);        // capi_forces.inc
 wgs_status fire_emitters(wgs_data *d, bool timed);   // capi_emit.inc (wgs_step, in front of begin_substep)
+wgs_status fire_sinks(wgs_data *d, bool timed);      // capi_remove.inc (wgs_step, in front of fire_emitters)
 
 #ifndef WGS_PCDF_WAVES_MAX_VISITS
 #define WGS_PCDF_WAVES_MAX_VISITS 256

@@ -290,3 +290,54 @@ class Emitter:
             thickness = int(count[int(np.argmax(np.abs(v)))]) * float(spacing)
         period = max(1, int(math.ceil(float(thickness) / (speed * float(dt)) - 1e-9)))
         return Emitter(proto, tuple(float(x) for x in lo), tuple(int(c) for c in count), float(spacing), period=period, **kw)
+
+
+# Particles removed at run time (include/wgsparkl_hip_remove.h WGS_SINK_*; no reference counterpart, like the emitters)
+SINK_INSIDE = 0      # removes the particles inside the region
+SINK_OUTSIDE = 1     # removes the particles that are NOT inside it: an outflow boundary (takes a particle with a NaN position)
+MAX_SINKS = 8
+
+
+@dataclass(frozen=True)
+class Sink:
+    """One entry of `MpmData.set_sinks` / `MpmData.remove_particles_in`: a region (`REGION_BOX`: |x_k - center_k| <= half_k on every
+    axis, `REGION_BALL`: |x - center|^2 <= half[0]^2, both in fp32 from the stored position, a face counting as inside), the `side` it
+    removes, and — read by `set_sinks` only — the schedule: due in front of substep s if s >= start_substep and (s - start_substep) %
+    period == 0. Vectors take 2 or 3 components (the third is ignored in 2D). Made by `box`, `ball` or `outside_box`."""
+    region: int = REGION_BOX
+    side: int = SINK_INSIDE
+    center: tuple = (0.0, 0.0, 0.0)
+    half: tuple = (0.0, 0.0, 0.0)
+    start_substep: int = 0
+    period: int = 1
+
+    def __post_init__(self):
+        if int(self.region) not in (REGION_BOX, REGION_BALL):
+            raise ValueError("Sink: region is REGION_BOX or REGION_BALL")
+        if int(self.side) not in (SINK_INSIDE, SINK_OUTSIDE):
+            raise ValueError("Sink: side is SINK_INSIDE or SINK_OUTSIDE")
+        if len(self.center) != 3 or len(self.half) != 3:
+            raise ValueError("Sink: center and half have three components (Sink.box / Sink.ball pad them)")
+        if not all(math.isfinite(x) for x in self.center):
+            raise ValueError("Sink: center finite")
+        if not all(math.isfinite(x) and x >= 0.0 for x in self.half):
+            raise ValueError("Sink: half finite and >= 0")
+        if int(self.period) != self.period or not 1 <= int(self.period) < 2 ** 32:
+            raise ValueError("Sink: period is an integer >= 1")
+        if int(self.start_substep) != self.start_substep or not 0 <= int(self.start_substep) < 2 ** 32:
+            raise ValueError("Sink: start_substep is an unsigned 32-bit integer")
+
+    @staticmethod
+    def box(center, half, **kw) -> "Sink":
+        """removes what is inside the axis-aligned box"""
+        return Sink(REGION_BOX, SINK_INSIDE, _vec3(center), _vec3(half), **kw)
+
+    @staticmethod
+    def ball(center, radius: float, **kw) -> "Sink":
+        """removes what is inside the ball (a disc in 2D)"""
+        return Sink(REGION_BALL, SINK_INSIDE, _vec3(center), (float(radius), 0.0, 0.0), **kw)
+
+    @staticmethod
+    def outside_box(center, half, **kw) -> "Sink":
+        """removes what is NOT inside the box: everything that leaves it"""
+        return Sink(REGION_BOX, SINK_OUTSIDE, _vec3(center), _vec3(half), **kw)

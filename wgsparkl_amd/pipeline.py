@@ -425,7 +425,7 @@ class MpmData(DataHandle):
         super().__init__(pipeline, colliders)
         if particles.dim != self.dim:
             raise ValueError("particle dimension does not match the pipeline")
-        self._n_static, self._emitting = particles.n, False
+        self._n_static, self._emitting, self._num_sinks = particles.n, False, 0
         raw = _pack_particles(self.T, particles)
         h = C.c_void_p()
         args = (pipeline._h, C.byref(self._sim_params(params)), raw.ctypes.data_as(C.POINTER(self.T.Particle)), particles.n,
@@ -454,8 +454,14 @@ class MpmData(DataHandle):
 
     @property
     def n(self) -> int:
-        """Particles the data holds now: those it was created with, those added, those its emitters emitted (host arithmetic)."""
-        return self._n_static + (sum(self.emitter_counts()[0]) if self._emitting else 0)
+        """Particles the data holds now: those it was created with, those added and those its emitters emitted, less those removed and
+        those its sinks took (host arithmetic on the library's counters: `stats()["num_particles"]` without its wait for the stream)."""
+        return self._n_static + (sum(self.emitter_counts()[0]) if self._emitting else 0) - (sum(self.sink_counts()) if self._num_sinks else 0)
+
+    def _rebase_n(self, n_now: int):
+        """after a setter zeroed counters: `n` answers `n_now` again"""
+        self._n_static = n_now
+        self._n_static += n_now - self.n
 
     @property
     def particle_capacity(self) -> int:
@@ -498,7 +504,8 @@ class MpmData(DataHandle):
             a.start_substep, a.period, a.batches = int(e.start_substep), int(e.period), int(e.batches)
         n_now = self.n
         _ffi.check(self.lib, self.lib.wgs_set_emitters(self._h, arr if emitters else None, len(emitters)))
-        self._n_static, self._emitting = n_now, bool(emitters)   # (the call zeroed the counters)
+        self._emitting = bool(emitters)
+        self._rebase_n(n_now)   # (the call zeroed the counters)
 
     def emitters(self):
         """`wgs_get_emitters`: what `set_emitters` last took, as `models.Emitter`."""
@@ -521,10 +528,82 @@ class MpmData(DataHandle):
         k = len(self.emitters()) if self._emitting else 0
         return [int(x) for x in emitted[:k]], [int(x) for x in skipped[:k]]
 
+    def _removed(self, kept_from, removed: int, n_old: int):
+        self._n_static -= removed
+        return kept_from[:n_old - removed].copy()
+
+    def remove_particles(self, mask):
+        """`wgs_remove_particles`: `mask` has one entry per particle in the caller's order, nonzero (True) = remove. The survivors keep
+        their relative order and are renumbered densely; every reader answers them under the new indices at once, and the next
+        substep rebuilds the block table. Returns `kept_from` (np.uint32): the old index of every new index, for the caller's own
+        per-particle arrays (`mine = mine[kept_from]`). Blocking: the new particle count is read back."""
+        n_old = self.n
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, np.uint8)
+        if m.shape[0] != n_old:
+            raise ValueError("remove_particles: one mask entry per particle")
+        kept_from, removed = np.zeros(max(n_old, 1), np.uint32), C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_remove_particles(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                          kept_from.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(removed)))
+        return self._removed(kept_from, int(removed.value), n_old)
+
+    def remove_particles_device(self, mask_ptr: int, kept_from_ptr: int = 0) -> int:
+        """`wgs_remove_particles_device`: the same with the mask (one byte per particle) and, if wanted, `kept_from` (room for the old
+        particle count, uint32) in device memory, read and written on the data's stream. Returns the number removed. Blocking."""
+        removed = C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_remove_particles_device(self._h, C.c_void_p(int(mask_ptr)), C.c_void_p(int(kept_from_ptr)) if kept_from_ptr else None,
+                                                                 C.byref(removed)))
+        self._n_static -= int(removed.value)
+        return int(removed.value)
+
+    @staticmethod
+    def _sink_array(sinks):
+        sinks = [] if sinks is None else list(sinks)
+        arr = (_ffi.Sink * max(len(sinks), 1))()
+        for a, k in zip(arr, sinks):
+            a.region, a.side, a.start_substep, a.period = int(k.region), int(k.side), int(k.start_substep), int(k.period)
+            a.center[:] = [float(x) for x in k.center]
+            a.half[:] = [float(x) for x in k.half]
+        return sinks, arr
+
+    def remove_particles_in(self, sinks):
+        """`wgs_remove_particles_in`: the regions of up to `models.MAX_SINKS` `models.Sink` evaluated on the device, once, now (their
+        schedule is ignored); otherwise `remove_particles`. Returns `kept_from`."""
+        sinks, arr = self._sink_array(sinks)
+        n_old = self.n
+        kept_from, removed = np.zeros(max(n_old, 1), np.uint32), C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_remove_particles_in(self._h, arr if sinks else None, len(sinks),
+                                                             kept_from.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(removed)))
+        return self._removed(kept_from, int(removed.value), n_old)
+
+    def set_sinks(self, sinks):
+        """`wgs_set_sinks`: up to `models.MAX_SINKS` `models.Sink`, evaluated in one pass in front of the substeps their schedule names,
+        ahead of the emitters, inside `MpmPipeline.step` — which then waits for the stream in front of those substeps; `None` or an empty
+        list removes them. Replaces the whole set and zeroes `sink_counts`. Host state of the handle: no device memory, not part of a
+        checkpoint."""
+        sinks, arr = self._sink_array(sinks)
+        n_now = self.n
+        _ffi.check(self.lib, self.lib.wgs_set_sinks(self._h, arr if sinks else None, len(sinks)))
+        self._num_sinks = len(sinks)
+        self._rebase_n(n_now)   # (the call zeroed the sinks' counters, not the emitters')
+
+    def sinks(self):
+        """`wgs_get_sinks`: what `set_sinks` last took, as `models.Sink`."""
+        from .models import Sink
+        arr = (_ffi.Sink * _ffi.MAX_SINKS)()
+        n = C.c_uint32(0)
+        _ffi.check(self.lib, self.lib.wgs_get_sinks(self._h, arr, C.byref(n)))
+        return [Sink(int(a.region), int(a.side), tuple(a.center), tuple(a.half), int(a.start_substep), int(a.period)) for a in arr[:n.value]]
+
+    def sink_counts(self):
+        """`wgs_get_sink_counts`: particles removed per sink of the set (a particle in several counts for the first), as a list."""
+        removed = (C.c_uint64 * _ffi.MAX_SINKS)()
+        _ffi.check(self.lib, self.lib.wgs_get_sink_counts(self._h, removed))
+        return [int(x) for x in removed[:self._num_sinks]]
+
     @classmethod
     def from_scene(cls, pipeline, scene, **overrides):
         """The data one of the dicts `wgsparkl_amd.scenes` returns describes (the key table in that module's docstring): `new` with
-        its "model" and "particle_capacity", then its "plasticity", "fluid_gamma", "models", "walls", "forces" and "emitters" through their
+        its "model" and "particle_capacity", then its "plasticity", "fluid_gamma", "models", "walls", "forces", "emitters" and "sinks" through their
         setters, in that order, each only where the scene has the key. A keyword replaces the scene's entry of that name for this call (`colliders=[]`, `grid_capacity=128`,
         `particles=snap`); `None` for one of the optional keys builds the scene without it (`models=None`: no table)."""
         sc = {"model": MODEL_COROTATED, **scene, **overrides}
@@ -532,7 +611,7 @@ class MpmData(DataHandle):
         data = cls.new(pipeline, sc["params"], sc["particles"], sc["colliders"], sc["cell_width"], sc["grid_capacity"], sc["model"], **reserve)
         for key, apply in (("plasticity", data.set_plasticity_model), ("fluid_gamma", data.set_fluid_eos),
                            ("models", data.set_particle_models), ("walls", data.set_domain_walls), ("forces", data.set_force_fields),
-                           ("emitters", data.set_emitters)):
+                           ("emitters", data.set_emitters), ("sinks", data.set_sinks)):
             if sc.get(key) is not None:
                 apply(sc[key])
         return data

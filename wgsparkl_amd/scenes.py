@@ -19,6 +19,7 @@ The scene contract. Every builder returns a dict, and `MpmData.from_scene` (a wh
 | `forces` | optional | the force fields (a list of `models.ForceField`): `MpmData.set_force_fields`; an error on a slab |
 | `particle_capacity` | optional | room for that many particles in all, to be filled at run time (`MpmData.add_particles`, emitters): `wgs_data_create_reserved`; an error on a slab |
 | `emitters` | optional | the emitters (a list of `models.Emitter`): `MpmData.set_emitters`; an error on a slab |
+| `sinks` | optional | the sinks (a list of `models.Sink`): `MpmData.set_sinks`; an error on a slab |
 | `global_ids`, `partition` | slab scenes | the particles' names in the whole scene; the `SlabPartition` the slab's block range and neighbours come from |
 | `uniform_material` | slab scenes, optional | (mass, init_volume, lambda, mu) shared by every particle of every rank |
 
@@ -31,7 +32,7 @@ from __future__ import annotations
 import numpy as np
 
 from .models import (MODEL_COROTATED, MODEL_FLUID, MODEL_NEO_HOOKEAN, PLASTICITY_DRUCKER_PRAGER, PLASTICITY_SNOW, WALL_SLIP, WALL_STICKY,
-                     DruckerPrager, ElasticCoefficients, Emitter, FluidCoefficients, ForceField, ParticlePhase, Snow, Wall)
+                     DruckerPrager, ElasticCoefficients, Emitter, FluidCoefficients, ForceField, ParticlePhase, Sink, Snow, Wall)
 from .solver import SHAPE_CAPSULE, Collider, ParticleSet, SimulationParams
 
 F32 = np.float32
@@ -550,6 +551,72 @@ def sand_pour(dim=3, heap=(8, 2, 8), across=3, rows=1, height=8.0, speed=0.0625,
     return dict(particles=ps, params=params, colliders=[floor], cell_width=h, grid_capacity=4096, model=MODEL_COROTATED,
                 particle_capacity=ps.n + int(batches) * em.batch_size, emitters=[em],
                 name=f"sand pour {dim}D: {em.batch_size} sand particles every {em.period} substeps onto a heap of {ps.n} on a floor collider")
+
+
+def ballistic_transit(position, velocity, gravity, dt, left, limit=100000):
+    """Substeps a free particle (v += g dt, x += v dt: what an isolated MPM particle does) takes from `position` until `left(x)` is
+    true — the scenes below size their particle capacity by it, and their tests the number of substeps to run."""
+    x, v, g = np.asarray(position, np.float64).copy(), np.asarray(velocity, np.float64).copy(), np.asarray(gravity, np.float64)
+    for k in range(1, limit + 1):
+        v += g * dt
+        x += v * dt
+        if left(x):
+            return k
+    raise ValueError("ballistic_transit: the particle never leaves")
+
+
+def _steady_capacity(em, transit, sink_period):
+    """twice the particles in flight at a steady state: a batch every em.period substeps, each alive for `transit` substeps and up to
+    one sink period more"""
+    return 2 * (-(-(transit + sink_period) // em.period) + 1) * em.batch_size
+
+
+def drain(dim=3, tank=8, across=4, rows=1, height=6.0, speed=0.0625, sink_period=4, cell_width=1.0, jitter=0.1, density=1000.0,
+          bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, seed=2026):
+    """A faucet over a drain (scene keys "emitters" and "sinks"): `faucet`'s emitter and walled tank, without a limit of batches, and a
+    box sink over the two cell layers above and below the tank's floor, evaluated every `sink_period` substeps — what falls in is
+    removed, so the run goes on at a bounded particle count. The capacity is twice the particles in flight at the steady state of a
+    free fall (`ballistic_transit`; "transit_substeps" is that fall's length, for the caller)."""
+    sc = faucet(dim, tank, across, rows, height, speed, 0, cell_width, jitter, density, bulk_modulus, viscosity, gamma, seed)
+    h, em, params = float(cell_width), sc["emitters"][0], sc["params"]
+    floor, mid = 2, (4 + 0.5 * tank) * h
+    sink_top = (floor + 2) * h
+    top = [em.lo[k] + em.count[k] * em.spacing for k in range(dim)]                      # the lattice's far corner, jitter included
+    transit = ballistic_transit(top, em.proto.vel[0], params.gravity, params.dt, lambda x: x[1] <= sink_top - 0.25 * h)
+    centre = [mid] * dim
+    centre[1] = floor * h
+    half = [(0.5 * tank + 2.0) * h] * dim
+    half[1] = 2.0 * h
+    sink = Sink.box(centre, half, period=int(sink_period))
+    sc.update(particle_capacity=_steady_capacity(em, transit, int(sink_period)), sinks=[sink], transit_substeps=transit,
+              name=f"drain {dim}D: {em.batch_size} fluid particles every {em.period} substeps into a walled tank, a sink over its floor every {sink_period}")
+    return sc
+
+
+def channel(dim=3, length=6.0, across=4, rows=1, speed=0.0625, sink_period=4, cell_width=1.0, jitter=0.1, density=1000.0,
+            bulk_modulus=2.0e5, viscosity=0.0, gamma=7.0, seed=2027):
+    """An open channel (scene keys "emitters" and "sinks"): the data starts EMPTY; an emitter on the low-x side throws Tait fluid along
+    +x at `speed` times h / dt, and an OUTSIDE-box sink — the region of interest, `length` cells long behind the nozzle, 8 cells
+    high and wide — removes everything that has left it, through its far face or, falling, through its bottom: inflow and outflow at
+    a bounded particle count. Capacity and "transit_substeps" as in `drain`."""
+    h = float(cell_width)
+    params = SimulationParams(gravity=(0.0, -9.81, 0.0)[:dim], dt=1.0 / 1200.0)
+    fluid = FluidCoefficients(bulk_modulus, viscosity)
+    empty = ParticleSet.uniform(np.zeros((0, dim), F32), h / 4.0, density, fluid, phase=ParticlePhase(1.0, FLT_MAX))
+    proto = ParticleSet.uniform(np.zeros((1, dim), F32), h / 4.0, density, fluid, phase=ParticlePhase(1.0, FLT_MAX))
+    proto.vel[0, 0] = F32(speed * h / params.dt)
+    count = tuple(rows if k == 0 else across for k in range(dim))
+    lo = (8.0 * h,) + (12.0 * h - across * h / 4.0,) * (dim - 1)
+    em = Emitter.nozzle(proto, lo, count, h / 2.0, params.dt, jitter=jitter, seed=seed)
+    centre = [8.0 * h + 0.5 * length * h] + [12.0 * h] * (dim - 1)
+    half = [0.5 * length * h + h] + [4.0 * h] * (dim - 1)                                 # one cell of room behind the nozzle
+    far, bottom = centre[0] + half[0], centre[1] - half[1]
+    start = [lo[0] - 0.5 * h] + [lo[k] for k in range(1, dim)]                            # the slowest to leave: the nozzle's back, jitter included
+    transit = ballistic_transit(start, proto.vel[0], params.gravity, params.dt, lambda x: x[0] > far + 0.25 * h or x[1] < bottom - 0.25 * h)
+    sink = Sink.outside_box(centre, half, period=int(sink_period))
+    return dict(particles=empty, params=params, colliders=[], cell_width=h, grid_capacity=4096, model=MODEL_FLUID, fluid_gamma=float(gamma),
+                particle_capacity=_steady_capacity(em, transit, int(sink_period)), emitters=[em], sinks=[sink], transit_substeps=transit,
+                name=f"channel {dim}D: {em.batch_size} fluid particles every {em.period} substeps along +x, an outflow box {length:g} cells long")
 
 
 def config_scene(config="c2", world=1, rank=None, scaling="weak", n_side=None, jitter=0.05):

@@ -152,13 +152,13 @@ class NativeShard(DataHandle):
                    force_plastic: bool = False, halo_capacity_records: int = 4096, migrant_capacity: int = 4096, **overrides):
         """The slab of `rank` from a slab scene (the key table in the docstring of `wgsparkl_amd.scenes`): its block range and
         its neighbours from the scene's "partition", its "global_ids", "model" and "uniform_material", then its "fluid_gamma".
-        A keyword replaces the scene's entry of that name, as in `MpmData.from_scene`. "plasticity", "models", "walls", "forces" and
-        "emitters" are single-domain features the library refuses on a slab: a scene that holds one is an error unless the caller passes
-        `plasticity=None` / `models=None` / `walls=None` / `forces=None` / `emitters=None`. `particle_capacity` = 0: room for the slab's
+        A keyword replaces the scene's entry of that name, as in `MpmData.from_scene`. "plasticity", "models", "walls", "forces",
+        "emitters" and "sinks" are single-domain features the library refuses on a slab: a scene that holds one is an error unless the caller
+        passes `plasticity=None` / `models=None` / `walls=None` / `forces=None` / `emitters=None` / `sinks=None`. `particle_capacity` = 0: room for the slab's
         own particles only — the argument is the slab's room for migrants; a SCENE's "particle_capacity" (its reservation for particles
         added at run time, which a slab cannot take) is refused like the other keys."""
         sc = {"model": MODEL_COROTATED, **slab_scene, **overrides}
-        for key in ("plasticity", "models", "walls", "forces", "emitters"):
+        for key in ("plasticity", "models", "walls", "forces", "emitters", "sinks"):
             if sc.get(key) is not None:
                 raise ValueError(f"NativeShard.from_scene: the scene's {key!r} cannot be applied to a slab; pass {key}=None to build it without")
         if slab_scene.get("particle_capacity") is not None:
