@@ -12,15 +12,12 @@ helper accepts a canonical order and rejects it after one swap."""
 import numpy as np
 import pytest
 
-from wgsparkl_amd.models import MODEL_NEO_HOOKEAN, ElasticCoefficients, ParticlePhase
-from wgsparkl_amd.solver import Collider, ParticleSet, SimulationParams
+from wgsparkl_amd.solver import Collider
 
-from oracle.np_oracle import assoc_cell, bw_of
+from oracle.np_oracle import assoc_cell
 from helpers import debug, new_data, oracle
 from gpu_common import assert_canonical_order, assert_runs_canonical
-
-H, DT = 1.0, 1.0e-3
-RUNCAP, BLK_ARR, ARRC, NEWC = 768, 64, 4, 4    # kernels_sort.h / layout.h
+from sort_truth import ARRC, BLK_ARR, H, NEWC, RUNCAP, _clump, _lexsorted_runs, _scene, facts     # (the constants: read from kernels_sort.h / layout.h)
 
 
 def _lattice(lo_cell, ncells, ppc, jitter, rng, shift=0.0):
@@ -31,41 +28,6 @@ def _lattice(lo_cell, ncells, ppc, jitter, rng, shift=0.0):
     pos = pos + rng.uniform(-1.0, 1.0, pos.shape) * np.asarray(jitter)
     pos[:, 0] += shift
     return pos * H
-
-
-def _scene(pos, cells_per_substep, colliders=()):
-    pos = np.asarray(pos, np.float32)
-    dim = pos.shape[1]
-    ps = ParticleSet.uniform(pos, H / 4.0, 1000.0, ElasticCoefficients.from_young_modulus(1.0e3, 0.3), phase=ParticlePhase(1.0, -1.0))
-    ps.vel[:] = (np.asarray(cells_per_substep, np.float64) * (H / DT)).astype(np.float32)
-    return dict(particles=ps, params=SimulationParams(gravity=(0.0,) * dim, dt=DT), colliders=list(colliders), cell_width=H,
-                grid_capacity=1024, model=MODEL_NEO_HOOKEAN)
-
-
-def _clump(centre, count, rng, spread=0.004):
-    return np.asarray(centre) * H + rng.uniform(-spread, spread, (count, len(centre))) * H
-
-
-def facts(pos_a, pos_b, dim):
-    """What the sort that orders `pos_b` meets; `pos_a`: the positions one substep earlier (None: the first substep)."""
-    bw = bw_of(dim)
-    cb = assoc_cell(pos_b, H)
-    cells, inv, per_cell = np.unique(cb, axis=0, return_inverse=True, return_counts=True)
-    inv = inv.reshape(-1)
-    blocks, binv, per_block = np.unique(cb // bw, axis=0, return_inverse=True, return_counts=True)
-    binv = binv.reshape(-1)
-    f = dict(per_cell=per_cell, per_block=per_block)
-    if pos_a is not None:
-        ca = assoc_cell(pos_a, H)
-        moved = (ca != cb).any(1)
-        hopped = (ca // bw != cb // bw).any(1)
-        f["changed_cell_in_block"] = int((moved & ~hopped).sum())
-        f["changed_block"] = int(hopped.sum())
-        f["new_same"] = np.bincount(inv[moved & ~hopped], minlength=len(cells))     # newcomers per cell, from its own block ...
-        f["new_other"] = np.bincount(inv[hopped], minlength=len(cells))             # ... and from other blocks
-        f["arrivals"] = np.bincount(binv[hopped], minlength=len(blocks))            # per block, from other blocks
-        f["prev_run"] = np.unique(ca // bw, axis=0, return_counts=True)[1]          # the blocks' previous runs
-    return f
 
 
 # ---- the scenes: name -> (scene, substeps, precondition on facts())
@@ -241,17 +203,6 @@ def test_scene_drives_its_path_on_the_oracle(oracle_libs, name):
     st.step(1)
     assert not st.overflow
     precondition(facts(pos_a, pos_b, ps.dim))
-
-
-def _lexsorted_runs(pos, dim):
-    bw = bw_of(dim)
-    bshift = bw.bit_length() - 1
-    c = assoc_cell(pos, H)
-    blocks, binv, num = np.unique(c // bw, axis=0, return_inverse=True, return_counts=True)
-    t = c % bw
-    key = sum(t[:, k] << (bshift * k) for k in range(dim))
-    ids = np.lexsort((np.arange(len(pos)), key, binv.reshape(-1)))
-    return blocks, np.concatenate([[0], np.cumsum(num)[:-1]]), num, ids
 
 
 @pytest.mark.parametrize("dim", [2, 3])
