@@ -527,7 +527,24 @@ void wgs_comm_destroy(wgs_comm *comm);
  * `halo_capacity_records`: halo records per message — about twice the active blocks of a face of the slab (every block
  * of the interface layer sends one x-layer pair, the blocks migrating particles touch a few more);
  * `migrant_capacity`: particles that can cross one face in one substep. A slab with TWO neighbours must be at least
- * 3 blocks wide. Two-way coupled (dynamic) bodies: every rank accumulates the fixed-point impulses of its own
+ * 3 blocks wide.
+ * What each capacity must cover, exactly (a capacity that is exactly reached is enough and changes no result; one short
+ * is reported by the next wgs_sync, and from then on the run is wrong: a pair or a particle was dropped):
+ *   halo_capacity_records  the records of ONE message of one substep. The message to the upper neighbour holds, for
+ *                          every ACTIVE block (a block that holds a particle of this slab, guests included, or is the
+ *                          "+" neighbour of one) of block layer block_hi, its first x-layer pair always and every other
+ *                          pair with a non-zero node, and for layer block_hi + 1 its first pair when non-zero; the message
+ *                          to the lower neighbour likewise the first pair of every active block of layer block_lo and
+ *                          every non-zero pair of layer block_lo - 1. The table is never cleared: only the records of
+ *                          the current substep count. The smallest non-empty message holds 2^(D-1) records.
+ *   migrant_capacity       the particles that leave through ONE face in ONE substep (each face has its own area).
+ *   particle_capacity      (wgs_data_create_sharded) the residents of a substep INCLUDING the guests — the particles that
+ *                          left the core range in the previous substep and are handed over in this one — plus the
+ *                          particles that arrive in the same substep: the arrivals are written behind all residents
+ *                          before the guests' slots are given up.
+ *   the leavers' list      is not the caller's to size: max(4096, particle_capacity / 16) particles can leave a slab's
+ *                          core range (through both faces together) in one substep.
+ * Two-way coupled (dynamic) bodies: every rank accumulates the fixed-point impulses of its own
  * particles (src/solver/p2g.wgsl:142-155) and the 16 x 8 int32 sums are all-reduced before integrate_bodies
  * (src/solver/rigid_impulses.wgsl:94-137) — integers, so the result does not depend on the order. */
 wgs_status wgs_shard_attach(wgs_data *data, wgs_comm *comm, int32_t has_lower, int32_t has_upper,
